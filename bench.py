@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- cell-updates/s per RK4 step + achieved HBM GB/s of the fused stage kernel.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one full 4-stage RK4 step of the shallow-water dycore over the whole synthetic mesh
 (BASELINE.json metric).  Default workload = BASELINE config 4: ~1 M-cell (1 024 002) icosahedral
@@ -10,14 +10,21 @@ For N > 1 the driver launches this file under torch.distributed.run (one rank pe
 partitioned across ranks (strong scaling) and halos are exchanged once per RK stage.
 Prints ONE JSON line on rank 0.
 
-What the line carries beyond the contract:
+A plain run does what the headline needs and no more: set-up (mesh, plan, upload, the library's placement search; for N > 1
+the halo transport choice), W warm-up steps, K timed steps, the outputs (--dump-outputs), the line.
   * `value` / `ms_per_step` come from the MEDIAN of the K per-step times (one HIP event per step on the library's compute
     stream, max over ranks per step); the mean over the barrier-bracketed wall region is kept as `ms_per_step_wall_mean`;
+  * `n_gpus` = DISTINCT devices the ranks use (`ranks`, `n_devices_visible`, `ranks_per_device`, `rehearsal`);
+  * --dump-outputs DIR: the prognostic state the last timed step left (ssh, normalVelocity, layerThickness of the current
+    time level) as DIR/<name>.npy in float64 -- every row, or a fixed seeded sample of rows where that exceeds 64 MiB.
+--full adds what takes runs of its own, after the timed region:
   * `calibration`: a plain 16-byte-per-lane copy and a read-only sweep of a 4 GiB buffer timed with HIP events on the same
-    stream right before the warm-up and right after the timed region, plus the device's clock / power files from sysfs --
+    stream right before the set-up and right after the timed region, plus the device's clock / power files from sysfs --
     so a slow box and a slow build can be told apart (`roofline.frac_of_copy_this_run`);
-  * `config5`: BASELINE config 5 (3 696 642 cells x 80 layers, fp32 storage / fp64 arithmetic) timed in the same default run;
-  * `n_gpus` = DISTINCT devices the ranks use (`ranks`, `n_devices_visible`, `ranks_per_device`, `rehearsal`).
+  * per-stage rooflines, the tendency / Forward-Euler / 13-stream entries and clocks under load (N = 1), the exchange report
+    (N > 1), the CPU baselines (N = 1; --no-cpu drops them);
+  * `config5`: BASELINE config 5 (3 696 642 cells x 80 layers, fp32 storage / fp64 arithmetic) timed in the same run
+    (--no-config5 drops it).
 """
 import argparse
 import datetime as dt
@@ -41,6 +48,8 @@ import numpy as np  # noqa: E402,F401
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec
 HBM_COPY_GBS = 6290.0          # the guide's float4 copy ceiling; the same-run probe is what frac_of_copy_this_run uses
 PROBE_BYTES = 4 << 30          # footprint of the same-run bandwidth probe (2 GiB source + 2 GiB destination)
+DUMP_BYTES = 64 << 20          # --dump-outputs: upper limit of all files together
+DUMP_SEED = 20251016           # --dump-outputs: the row sample where the whole state exceeds DUMP_BYTES
 
 WORKLOADS = {
     # name: (icosahedral frequency m, layers[, state bytes, Schmidt stretch])  -- SURVEY.md section 8 size table
@@ -624,6 +633,53 @@ def config5_leg(mk, backend, args, copy_gbs):
     return out
 
 
+def dump_rows(nCells, nEdges, K):
+    """Global ids of the rows --dump-outputs writes: every row when ssh, normalVelocity and layerThickness fit DUMP_BYTES as
+    float64, else the same fraction of the cells and of the edges, drawn with DUMP_SEED (the same rows in every run)."""
+    total = 8 * (nCells + K * (nEdges + nCells))
+    if total <= DUMP_BYTES:
+        return np.arange(nCells), np.arange(nEdges)
+    frac = DUMP_BYTES * 15 / 16 / total
+    rng = np.random.default_rng(DUMP_SEED)
+    cells = np.sort(rng.choice(nCells, max(1, int(nCells * frac)), replace=False))
+    edges = np.sort(rng.choice(nEdges, max(1, int(nEdges * frac)), replace=False))
+    return cells, edges
+
+
+def output_rows(Prog, cells, edges, lm=None):
+    """name -> (positions in the id list, rows) of the current time level at the global ids `cells` / `edges`: every listed
+    row, or with `lm` (the LocalMesh of a rank of a partitioned run) those the rank owns -- its halo rows are not final."""
+    out = {}
+    for name, field, ids, kind in (("ssh", Prog.ssh[-1], cells, "c"), ("normalVelocity", Prog.normalVelocity[-1], edges, "e"),
+                                   ("layerThickness", Prog.layerThickness[-1], cells, "c")):
+        pos, loc = np.arange(ids.size), ids
+        if lm is not None:
+            g2l, owned = (lm.g2l_c, lm.owned_cell_mask) if kind == "c" else (lm.g2l_e, lm.owned_edge_mask)
+            loc = g2l[ids]
+            keep = loc >= 0
+            keep[keep] = owned[loc[keep]]
+            pos, loc = pos[keep], loc[keep]
+        out[name] = (pos, field.rows(loc) if loc.size else np.empty((0,) + field.shape[1:]))
+    return out
+
+
+def write_outputs(path, parts, cells, edges, K):
+    """Assemble output_rows() of every rank (a list) and write DIR/<name>.npy, float64."""
+    os.makedirs(path, exist_ok=True)
+    shapes = {"ssh": (cells.size,), "normalVelocity": (edges.size, K), "layerThickness": (cells.size, K)}
+    for name, shape in shapes.items():
+        a = np.empty(shape, dtype=np.float64)
+        seen = np.zeros(shape[0], dtype=bool)
+        for p in parts:
+            pos, rows = p[name]
+            a[pos] = rows
+            seen[pos] = True
+        if not seen.all():
+            raise RuntimeError(f"--dump-outputs: {int((~seen).sum())} rows of {name} are owned by no rank")
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"[bench] outputs of the last timed step: {', '.join(shapes)} ({cells.size} cells, {edges.size} edges) in {path}")
+
+
 def main():
     if "--rccl-probe" in sys.argv:
         rccl_probe_child(sys.argv[sys.argv.index("--rccl-probe") + 1] if len(sys.argv) > sys.argv.index("--rccl-probe") + 1 else "nccl")
@@ -635,9 +691,16 @@ def main():
     ap.add_argument("--variant", type=int, default=0, help="kernel variant (moka_set_kernel_variant): 0 auto, 11 default stage kernel, 4 column kernel, 3 generic index kernel")
     ap.add_argument("--patch-cells", type=int, default=0)
     ap.add_argument("--ordering", type=int, default=0)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-config5", action="store_true", help="skip the config-5 leg of the default single-GPU run")
-    ap.add_argument("--tend-iters", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also everything the headline does not need: calibration, per-stage rooflines, "
+                         "tendency / Forward-Euler / 13-stream entries, clocks under load, the config-5 leg and the CPU baselines "
+                         "(N = 1), the exchange report (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write ssh / normalVelocity / layerThickness as the last timed step left them to DIR/<name>.npy (float64; "
+                         "a fixed seeded sample of rows where the whole state exceeds 64 MiB)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-config5", action="store_true", help="--full: skip the config-5 leg of the single-GPU run")
+    ap.add_argument("--tend-iters", type=int, default=20, help="--full: launches of the tendency / Forward-Euler entries")
     ap.add_argument("--placement-tries", type=int, default=24,
                     help="upper limit of the per-array re-allocations moka_state_optimize_placement tries at set-up (the library's own "
                          "search, behind the C ABI: one array at a time gets a second allocation, the faster is kept; where the "
@@ -651,6 +714,8 @@ def main():
                          "into the neighbours' IPC-mapped fields over xGMI) and the RCCL forms (nccl-a2a, nccl-p2p); nccl = the RCCL "
                          "forms only; gloo = host-staged (rehearsal on one GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -732,7 +797,8 @@ def main():
     # package leave the state the stage launches run in -- 1400 W, shader clock 2.1-2.2 GHz -- and the first 100-200 ms of
     # launches behind such a pause run 1-2 % slower than the steady state; W = 5 warm-up steps are 35 ms.  The probes measure the
     # box, not the model: they lose nothing by coming first, and the timed region then starts from the state a running model is in.)
-    cal_before = calibrate(backend, "before")
+    # --full only: the headline does not need them.
+    cal_before = calibrate(backend, "before") if args.full else None
     transport_trials = {}
     model = None
     if world > 1:
@@ -778,20 +844,32 @@ def main():
             dist.barrier(group=gloo_group)
 
     wall, step_ms = timed_steps(backend, step, args.steps, args.warmup, sync_all)
+    if args.dump_outputs:
+        # what the last timed step left, before anything else steps the state on
+        cells, edges = dump_rows(mesh.nCells, mesh.nEdges, K)
+        mine = output_rows(model.Prog, cells, edges, model.lm) if world > 1 else output_rows(Prog, cells, edges)
+        parts = [mine]
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, mine, group=gloo_group)
+        if rank == 0:
+            write_outputs(args.dump_outputs, parts, cells, edges, K)
+        del mine, parts
     # ---- ... and after: right behind the timed region ----
-    cal_after = calibrate(backend, "after")
+    cal_after = calibrate(backend, "after") if args.full else None
     if world > 1:
         # per step: the slowest rank's time (the step is over when the last rank is done); wall: max over ranks
         tt = torch.tensor(step_ms + [wall], dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX, group=gloo_group)
         step_ms, wall = [float(x) for x in tt[:-1]], float(tt[-1])
-        cc = torch.tensor([cal_before["copy_GBs"], cal_after["copy_GBs"], cal_before["read_GBs"]], dtype=torch.float64)
-        dist.all_reduce(cc, op=dist.ReduceOp.MIN, group=gloo_group)
-        copy_min_over_ranks = [float(x) for x in cc]
+        if args.full:
+            cc = torch.tensor([cal_before["copy_GBs"], cal_after["copy_GBs"], cal_before["read_GBs"]], dtype=torch.float64)
+            dist.all_reduce(cc, op=dist.ReduceOp.MIN, group=gloo_group)
+            copy_min_over_ranks = [float(x) for x in cc]
     st = step_stats(step_ms)
     ms_per_step = st["median"]
     value = mesh.nCells * K / (ms_per_step * 1e-3)
-    copy_this_run = 0.5 * (cal_before["copy_GBs"] + cal_after["copy_GBs"])
+    copy_this_run = 0.5 * (cal_before["copy_GBs"] + cal_after["copy_GBs"]) if args.full else None
 
     b_mesh, b_tend, b_step = algorithmic_bytes(mesh.nCells, mesh.nEdges, K, S=sbytes)
     stream_bytes = sbytes * K * (mesh.nEdges + mesh.nCells)
@@ -823,41 +901,43 @@ def main():
             traffic = None
     roofline = {"bound": "hbm", "kernel": "k_stage_rec2c (fused TRiSK tendency + RK4 stage update), mean of the 4 launches of a step",
                 "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                "frac_of_copy_this_run": achieved / copy_this_run, "copy_GBs_this_run": copy_this_run,
+                **({"frac_of_copy_this_run": achieved / copy_this_run, "copy_GBs_this_run": copy_this_run} if args.full else {}),
                 "frac_of_guide_copy_ceiling": achieved / HBM_COPY_GBS, "traffic": traffic, "traffic_source": traffic_source,
                 "algorithmic_bytes_per_launch": per_rank_bytes, "avg_launch_ms": avg_launch_ms,
                 "stray_steps": st["strays"], "frac_at_median_step": per_rank_bytes / (ms_per_step / 4 * 1e-3) / 1e9 / HBM_PEAK_GBS,
                 "launches_timed": launches, "formula": "contract: 18 state streams per step (5, 5, 5, 3) + 4 B_mesh",
                 "frac_kernel_minimum_bytes": achieved_min / HBM_PEAK_GBS,
-                "frac_kernel_minimum_bytes_of_copy_this_run": achieved_min / copy_this_run,
+                **({"frac_kernel_minimum_bytes_of_copy_this_run": achieved_min / copy_this_run} if args.full else {}),
                 "kernel_minimum_note": "16 state streams per step (3, 5, 5, 3): stage 1 aliases Provis = Curr = New"}
-    if world == 1:
+    if world == 1 and args.full:
         per_stage, nst, ssum = stage_rooflines(backend, step, max(5, min(args.steps, 20)), stream_bytes, b_mesh)
         roofline["per_stage"] = per_stage
         roofline["per_stage_steps"] = nst
         roofline["per_stage_sum_ms"] = ssum
 
-    calibration = {"copy_GBs_before": cal_before["copy_GBs"], "copy_GBs_after": cal_after["copy_GBs"],
-                   "copy_GBs_mean_before": cal_before["copy_GBs_mean"], "copy_GBs_mean_after": cal_after["copy_GBs_mean"],
-                   "read_GBs": cal_before["read_GBs"], "read_GBs_after": cal_after["read_GBs"],
-                   "gather_GBs_before": cal_before["gather_GBs"], "gather_GBs_after": cal_after["gather_GBs"],
-                   "streams5_GBs_before": cal_before.get("streams5_GBs"), "streams5_GBs_after": cal_after.get("streams5_GBs"),
-                   "reread128_GBs_before": cal_before.get("reread128_GBs"), "reread128_GBs_after": cal_after.get("reread128_GBs"),
-                   "gather32G_GBs_before": cal_before.get("gather32G_GBs"), "gather32G_GBs_after": cal_after.get("gather32G_GBs"),
-                   "probe": f"{PROBE_BYTES >> 30} GiB footprint (half source, half destination), 16 bytes per lane, best of 5 launches, "
-                            "HIP events on the compute stream; before = in front of the set-up (plan, upload, placement search; the warm-up follows that directly), after = behind the timed region; "
-                            "copy = one word per thread (bytes read + written), read = read-only sweep with nontemporal loads, "
-                            "gather = 480-byte rows in a scattered order, a half-wave per row (the stage kernels' pattern), "
-                            "streams5 = three streams read and two written at once (the mix of the RK stage launches), "
-                            "reread128 = a 128 MiB region read 16 times back to back (what comes back from the Infinity Cache: the stage "
-                            "kernels fetch a fifth of their bytes a second time), gather32G = the row gather over a 32 GiB footprint of its "
-                            "own, a quarter of the rows (address translation for a state-sized span)",
-                   "guide_copy_ceiling_GBs": HBM_COPY_GBS,
-                   "ms_per_step_at_guide_ceiling": ms_per_step * copy_this_run / HBM_COPY_GBS,
-                   "clocks_power_before": cal_before["sysfs"], "clocks_power_after": cal_after["sysfs"]}
-    if world > 1:
-        calibration["min_over_ranks"] = {"copy_GBs_before": copy_min_over_ranks[0], "copy_GBs_after": copy_min_over_ranks[1],
-                                         "read_GBs": copy_min_over_ranks[2]}
+    calibration = None
+    if args.full:
+        calibration = {"copy_GBs_before": cal_before["copy_GBs"], "copy_GBs_after": cal_after["copy_GBs"],
+                       "copy_GBs_mean_before": cal_before["copy_GBs_mean"], "copy_GBs_mean_after": cal_after["copy_GBs_mean"],
+                       "read_GBs": cal_before["read_GBs"], "read_GBs_after": cal_after["read_GBs"],
+                       "gather_GBs_before": cal_before["gather_GBs"], "gather_GBs_after": cal_after["gather_GBs"],
+                       "streams5_GBs_before": cal_before.get("streams5_GBs"), "streams5_GBs_after": cal_after.get("streams5_GBs"),
+                       "reread128_GBs_before": cal_before.get("reread128_GBs"), "reread128_GBs_after": cal_after.get("reread128_GBs"),
+                       "gather32G_GBs_before": cal_before.get("gather32G_GBs"), "gather32G_GBs_after": cal_after.get("gather32G_GBs"),
+                       "probe": f"{PROBE_BYTES >> 30} GiB footprint (half source, half destination), 16 bytes per lane, best of 5 launches, "
+                                "HIP events on the compute stream; before = in front of the set-up (plan, upload, placement search; the warm-up follows that directly), after = behind the timed region; "
+                                "copy = one word per thread (bytes read + written), read = read-only sweep with nontemporal loads, "
+                                "gather = 480-byte rows in a scattered order, a half-wave per row (the stage kernels' pattern), "
+                                "streams5 = three streams read and two written at once (the mix of the RK stage launches), "
+                                "reread128 = a 128 MiB region read 16 times back to back (what comes back from the Infinity Cache: the stage "
+                                "kernels fetch a fifth of their bytes a second time), gather32G = the row gather over a 32 GiB footprint of its "
+                                "own, a quarter of the rows (address translation for a state-sized span)",
+                       "guide_copy_ceiling_GBs": HBM_COPY_GBS,
+                       "ms_per_step_at_guide_ceiling": ms_per_step * copy_this_run / HBM_COPY_GBS,
+                       "clocks_power_before": cal_before["sysfs"], "clocks_power_after": cal_after["sysfs"]}
+        if world > 1:
+            calibration["min_over_ranks"] = {"copy_GBs_before": copy_min_over_ranks[0], "copy_GBs_after": copy_min_over_ranks[1],
+                                             "read_GBs": copy_min_over_ranks[2]}
 
     out = {"metric": "cell-updates/sec per RK4 step", "value": value, "unit": "cell-updates/s",
            "n_gpus": n_distinct, "ranks": world, "n_devices_visible": ndev, "ranks_per_device": ranks_per_device,
@@ -880,11 +960,11 @@ def main():
                       + (" -- REHEARSAL: ranks share a device" if rehearsal else ""),
                       **({"halo_transport": args.transport, "halo_transport_trials_ms_per_step": transport_trials,
                           "rccl_usable": rccl_ok} if world > 1 else {})},
-           "roofline": roofline, "calibration": calibration,
+           "roofline": roofline, **({"calibration": calibration} if args.full else {}),
            "placement": placement_summary(placement)}
 
-    # Everything from here on is an appendix of the line assembled above: none of it may cost the line itself.  (Exception:
-    # exchange_report runs collectives -- a rank that failed alone would leave the others waiting, so it is not caught.)
+    # Everything from here on is an appendix of the line assembled above (--full only): none of it may cost the line itself.
+    # (Exception: exchange_report runs collectives -- a rank that failed alone would leave the others waiting, so it is not caught.)
     def appendix(key, fn):
         try:
             return fn()
@@ -892,10 +972,10 @@ def main():
             log(f"[bench] {key} failed: {exc!r}")
             return {"error": f"{type(exc).__name__}: {exc}"}
 
-    if world > 1:
+    if world > 1 and args.full:
         out["exchange"] = exchange_report(mk, backend, model, step, sync_all, dist, gloo_group, rank, world, args,
                                           (mesh, ssh, u, h, rest, cfg, sbytes), ms_per_step)
-    if world == 1:
+    if world == 1 and args.full:
         ex = appendix("tendency / Forward-Euler entries", lambda: single_gpu_extras(mk, backend, Setup, Diag, Tend, Prog, K, sbytes, dts, b_tend, args.tend_iters))
         out.update(ex if "error" not in ex else {"tendency_kernel": ex, "forward_euler_compat": ex})
         if sbytes == 8:
@@ -924,8 +1004,9 @@ def main():
             cal_end = calibrate(backend, "end of run")
             calibration["copy_GBs_end_of_run"] = cal_end["copy_GBs"]
             calibration["clocks_power_end_of_run"] = cal_end["sysfs"]
-    backend.bw_probe(0)
-    if rank == 0 and world == 1 and not args.no_cpu:       # the CPU leg belongs to the N = 1 line only
+    if args.full:
+        backend.bw_probe(0)
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:       # the CPU leg belongs to the N = 1 line only
         t0 = time.time()
         mixed = sbytes == 4
         if mesh.nCells * K > 1.5e8:        # bounded sample: the same workload family on a quarter of the cells

@@ -2,7 +2,9 @@
 import importlib.util
 import os
 import sys
+import types
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -63,6 +65,77 @@ def test_sysfs_and_statistics_helpers(tmp_path):
     assert abs(st["mean"] - 7.41) < 1e-12
 
 
+def test_dump_rows_fit_the_budget_and_are_the_same_every_run():
+    """--dump-outputs: every row of a small state; a seeded sample of a large one, within 64 MiB, identical from run to run."""
+    nC, nE = 10242, 30720
+    cells, edges = bench.dump_rows(nC, nE, 60)
+    assert np.array_equal(cells, np.arange(nC)) and np.array_equal(edges, np.arange(nE))
+    for nC, nE, K in ((1024002, 3072000, 60), (3696642, 11089920, 80)):
+        cells, edges = bench.dump_rows(nC, nE, K)
+        assert 8 * (cells.size + K * (cells.size + edges.size)) <= bench.DUMP_BYTES
+        assert cells.size > 1000 and edges.size > 1000
+        assert np.all(np.diff(cells) > 0) and np.all(np.diff(edges) > 0) and cells[-1] < nC and edges[-1] < nE
+        c2, e2 = bench.dump_rows(nC, nE, K)
+        assert np.array_equal(cells, c2) and np.array_equal(edges, e2)
+
+
+def test_dumped_rows_of_a_partitioned_run_assemble_to_the_whole(tmp_path):
+    """Each rank reports the listed rows it owns; assembled on rank 0 they are the global arrays, every row exactly once."""
+    from moka_hip import meshgen as mg
+    from moka_hip import parallel as mp
+    mesh, K, world = mg.icosahedral_mesh(6), 3, 3
+    rng = np.random.default_rng(5)
+    glob = {"ssh": rng.random(mesh.nCells), "normalVelocity": rng.random((mesh.nEdges, K)), "layerThickness": rng.random((mesh.nCells, K))}
+
+    class Field:
+        def __init__(self, a, g):
+            self.a, self.g, self.shape = a, g, (g.size,) + a.shape[1:]
+
+        def rows(self, ids):
+            return self.a[self.g[ids]]
+
+    part = mp.partition_cells(mesh, world)
+    cells, edges = np.arange(0, mesh.nCells, 3), np.arange(1, mesh.nEdges, 2)
+    parts = []
+    for r in range(world):
+        lm = mp.build_local(mesh, part, r, world)
+        P = types.SimpleNamespace(ssh=[None, Field(glob["ssh"], lm.cells_g)],
+                                  normalVelocity=[None, Field(glob["normalVelocity"], lm.edges_g)],
+                                  layerThickness=[None, Field(glob["layerThickness"], lm.cells_g)])
+        parts.append(bench.output_rows(P, cells, edges, lm))
+    for name, ids in (("ssh", cells), ("normalVelocity", edges), ("layerThickness", cells)):
+        assert sum(p[name][0].size for p in parts) == ids.size, name
+    bench.write_outputs(str(tmp_path / "out"), parts, cells, edges, K)
+    for name, ids in (("ssh", cells), ("normalVelocity", edges), ("layerThickness", cells)):
+        got = np.load(tmp_path / "out" / f"{name}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, glob[name][ids]), name
+
+
+def _oracle_after(m, K, nsteps, clock_dt=True):
+    """The single-domain oracle's state after `nsteps` RK4 steps of bench.py's synthetic workload on the m-sphere.
+    clock_dt: dt as the one-rank model's clock holds it (microsecond resolution); the partitioned model steps with dt as given."""
+    import datetime as dt
+    import oracle as orc
+    from moka_hip import meshgen as mg
+    mesh = mg.icosahedral_mesh(m)
+    ssh, u, h, rest, dts = mg.sphere_synthetic_state(mesh, K)
+    if clock_dt:
+        dts = dt.timedelta(seconds=dts).total_seconds()
+    st = orc.OracleState(orc.OracleMesh(mesh, K, resting_thickness_sum=rest.sum(1), max_level_edge_top=K), ssh, u, h)
+    for _ in range(nsteps):
+        st.step_rk4(dts)
+    return {"ssh": st.ssh[1], "normalVelocity": st.u[1], "layerThickness": st.h[1]}
+
+
+def _check_outputs(path, expected):
+    total = 0
+    for name, exp in expected.items():
+        got = np.load(os.path.join(path, f"{name}.npy"))
+        total += got.nbytes
+        assert got.dtype == np.float64 and np.array_equal(got, exp), name
+    assert total <= bench.DUMP_BYTES
+
+
 def _run_bench(args, nproc=1, timeout=420):
     """bench.py as the driver launches it (a child process; torch.distributed.run for N > 1): the JSON line it prints."""
     import json
@@ -84,10 +157,25 @@ def _run_bench(args, nproc=1, timeout=420):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_and_dumps_what_the_timed_steps_computed(tmp_path):
+    """A plain run (no --full): the headline line, exactly --steps timed steps, none of the appendices; --dump-outputs holds
+    the state after the warm-up and timed steps, bit for bit the oracle's."""
+    b = _run_bench(["--workload", "small_10k_x60", "--steps", "3", "--warmup", "2", "--dump-outputs", str(tmp_path / "out")])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config", "roofline"):
+        assert k in b, k
+    assert b["steps"] == 3 and b["step_ms"]["n"] == 3 and b["ms_per_step"] == b["step_ms"]["median"] > 0
+    assert b["metric"] == "cell-updates/sec per RK4 step" and b["unit"] == "cell-updates/s" and b["dtype"] == "f64"
+    for k in ("calibration", "cpu_baseline", "tendency_kernel", "forward_euler_compat", "rk4_13_streams", "under_load", "config5"):
+        assert k not in b, k
+    assert "per_stage" not in b["roofline"]
+    _check_outputs(tmp_path / "out", _oracle_after(32, 60, 2 + 3))
+
+
+@pytest.mark.gpu
 def test_bench_line_on_one_gpu_small_workload():
-    """The driver's contract on a small workload: one JSON line with the metric, the roofline (with its calibration) and the
-    CPU baseline; value = cells x layers / median step time."""
-    b = _run_bench(["--workload", "small_10k_x60", "--steps", "6", "--warmup", "2", "--no-config5", "--tend-iters", "3"])
+    """The driver's contract on a small workload with --full: one JSON line with the metric, the roofline (with its calibration)
+    and the CPU baseline; value = cells x layers / median step time."""
+    b = _run_bench(["--workload", "small_10k_x60", "--steps", "6", "--warmup", "2", "--no-config5", "--tend-iters", "3", "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline", "calibration", "step_ms"):
         assert k in b, k
@@ -109,11 +197,13 @@ def test_bench_line_on_one_gpu_small_workload():
 
 
 @pytest.mark.gpu
-def test_bench_two_ranks_on_one_gpu_is_labelled_a_rehearsal():
-    """bench.py --gpus 2 the way the driver starts it, with both ranks on the one GPU of this box: the transport selection must
-    qualify a transport (bitwise against the host-staged exchange), and the line must say what it is -- one distinct device, two
-    ranks, a rehearsal -- instead of claiming two GPUs."""
-    b = _run_bench(["--workload", "small_10k_x60", "--steps", "4", "--warmup", "2"], nproc=2)
+def test_bench_two_ranks_on_one_gpu_is_labelled_a_rehearsal(tmp_path):
+    """bench.py --gpus 2 --full the way the driver starts it, with both ranks on the one GPU of this box: the transport selection
+    must qualify a transport (bitwise against the host-staged exchange), and the line must say what it is -- one distinct device,
+    two ranks, a rehearsal -- instead of claiming two GPUs.  The outputs both ranks own assemble to the oracle's state."""
+    b = _run_bench(["--workload", "small_10k_x60", "--steps", "4", "--warmup", "2", "--full", "--dump-outputs", str(tmp_path / "out")],
+                   nproc=2)
+    _check_outputs(tmp_path / "out", _oracle_after(32, 60, 2 + 4, clock_dt=False))
     assert b["ranks"] == 2 and b["n_gpus"] == 1 and b["n_devices_visible"] == 1 and b["ranks_per_device"] == 2 and b["rehearsal"] is True
     assert b["scaling"] == "strong" and b["config"]["halo_transport"] in ("ipc", "ipc-acq", "gloo", "nccl-a2a", "nccl-p2p")
     assert b["config"]["halo_transport"] in b["config"]["halo_transport_trials_ms_per_step"]

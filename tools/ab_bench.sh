@@ -9,7 +9,7 @@ EXPLIB=$PWD/mpas-ocean.jl_amd/libmoka_hip_exp.so
 for r in $(seq 1 $ROUNDS); do
   for side in A B; do
     if [ $side = B ]; then export MOKA_HIP_LIB=$EXPLIB; else unset MOKA_HIP_LIB; fi
-    python3 bench.py --no-cpu --steps 20 --warmup 5 "$@" > $OUT/${side}_$r.json 2> $OUT/${side}_$r.err || { echo "$side $r failed"; tail -3 $OUT/${side}_$r.err; continue; }
+    python3 bench.py --full --no-cpu --steps 20 --warmup 5 "$@" > $OUT/${side}_$r.json 2> $OUT/${side}_$r.err || { echo "$side $r failed"; tail -3 $OUT/${side}_$r.err; continue; }
     python3 - $OUT/${side}_$r.json $side $r <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().split("\n")[-1])

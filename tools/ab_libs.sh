@@ -7,7 +7,7 @@ OUT=gpurun_out/abl_$TAG; mkdir -p $OUT
 for r in $(seq 1 $ROUNDS); do
   for n in $NAMES; do
     if [ "$n" = "-" ]; then unset MOKA_HIP_LIB; else export MOKA_HIP_LIB=$PWD/mpas-ocean.jl_amd/libmoka_hip_$n.so; fi
-    python3 bench.py --no-cpu "$@" > $OUT/${n}_$r.json 2> $OUT/${n}_$r.err || { echo "$n $r failed"; tail -3 $OUT/${n}_$r.err; continue; }
+    python3 bench.py --full --no-cpu "$@" > $OUT/${n}_$r.json 2> $OUT/${n}_$r.err || { echo "$n $r failed"; tail -3 $OUT/${n}_$r.err; continue; }
     python3 - $OUT/${n}_$r.json $n $r <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().split("\n")[-1])

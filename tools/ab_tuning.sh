@@ -6,7 +6,7 @@ OUT=gpurun_out/abt_$TAG; mkdir -p $OUT
 for r in $(seq 1 $ROUNDS); do
   for side in A B; do
     if [ $side = A ]; then V=$VA; else V=$VB; fi
-    python3 bench.py --no-cpu --steps 20 --warmup 5 --tuning $KEY=$V "$@" > $OUT/${side}_$r.json 2> $OUT/${side}_$r.err || { echo "$side $r failed"; tail -3 $OUT/${side}_$r.err; continue; }
+    python3 bench.py --full --no-cpu --steps 20 --warmup 5 --tuning $KEY=$V "$@" > $OUT/${side}_$r.json 2> $OUT/${side}_$r.err || { echo "$side $r failed"; tail -3 $OUT/${side}_$r.err; continue; }
     python3 - $OUT/${side}_$r.json $side $r $KEY $V <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().split("\n")[-1])

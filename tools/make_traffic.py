@@ -3,7 +3,7 @@
 
 Usage: tools/make_traffic.py gpurun_out/prof_<tag>/summary.txt > profiles/pmc_traffic.json
 
-The profiled command is the default bench.py run, which times BASELINE config 4 (k_stage_rec2c) and config 5
+The profiled command is the bench.py --full run, which times BASELINE config 4 (k_stage_rec2c) and config 5
 (k_stage_rec2c_f32) in one process, so one summary yields both records.
 Counter unit of FETCH_SIZE / WRITE_SIZE is KiB.  gfx950 correction (MI355X_MICROARCH.md, HBM section): FETCH_SIZE reports half
 the bytes of 16-byte-per-lane coalesced reads, so the read side is doubled; WRITE_SIZE is taken as is.  Cross-check without a
@@ -40,7 +40,7 @@ for line in open(src):
 
 modes = [1, 2, 2, 3]  # the four stage launches of one RK4 step
 out = {
-    "_source": f"{src}: rocprofv3 --pmc passes of `python3 bench.py --steps 3 --warmup 1 --no-cpu --tend-iters 3` (tools/profile.sh; one "
+    "_source": f"{src}: rocprofv3 --pmc passes of `python3 bench.py --full --steps 3 --warmup 1 --no-cpu --tend-iters 3` (tools/profile.sh; one "
                "counter group per pass).  FETCH_SIZE / WRITE_SIZE in KiB; gfx950 correction per MI355X_MICROARCH.md section HBM: FETCH_SIZE "
                "reports half the bytes of 16-byte-per-lane coalesced reads, so the read side is doubled; WRITE_SIZE is exact.  Per launch = mean "
                "over the four stage launches of one RK4 step (modes 1,2,2,3).  *_exact = the 32-byte request counters x 32 B (no correction "

@@ -1,7 +1,8 @@
 #!/bin/bash
 # Runs on the GPU box (through gpurun): rocprofv3 kernel trace + separate PMC passes of bench.py, summaries into
 # gpurun_out/prof_<tag>/.  Usage: tools/profile.sh <tag> [bench args...]
-# The trace is taken with the driver's own bench command line (--steps 20 --warmup 5), program directly after `--`, so that
+# The trace is taken with the driver's own bench command line (--steps 20 --warmup 5) plus --full (the config-5 leg, the
+# calibration and the tendency entries are appendices of a --full run), program directly after `--`, so that
 # the kernel durations of profiles/ are comparable with the driver's BENCH record: tools/summarize_prof.py checks that
 # the stage kernels of one step sum to no more than the ms_per_step bench.py printed in the same (traced) run -- for the headline
 # workload (config 4) and for the config-5 leg of the same run -- and prints the run's own calibration beside them.
@@ -12,8 +13,8 @@ TAG=${1:-run}; shift || true
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-TRACE_ARGS="--steps 20 --warmup 5 --no-cpu $*"
-PMC_ARGS="--steps 3 --warmup 1 --no-cpu --tend-iters 3 $*"
+TRACE_ARGS="--full --steps 20 --warmup 5 --no-cpu $*"
+PMC_ARGS="--full --steps 3 --warmup 1 --no-cpu --tend-iters 3 $*"
 echo "bench args (trace): $TRACE_ARGS" > $OUT/command.txt
 echo "bench args (pmc):   $PMC_ARGS" >> $OUT/command.txt
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py $TRACE_ARGS > $OUT/bench_trace.json 2> $OUT/bench_trace.err || exit 1
