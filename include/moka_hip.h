@@ -495,6 +495,23 @@ int  moka_set_nonlinear(moka_state *st, int on);
  * with div = velocityDivCell and relVort = relativeVorticity of the stage's provisional velocity.  0 (default) = off.
  * MOKA_ERR_UNSUPPORTED unless moka_set_nonlinear(st, 1) came first. */
 int  moka_set_viscosity_del2(moka_state *st, double viscDel2);
+/* Del4 (biharmonic) momentum mixing on top of the nonlinear terms (the reference declares Del2 and Del4,
+ * horizontal_momentum_mixing.jl:6-9, and sketches Del2 only).  With L the Del2 bracket above,
+ *   L(u)[k,e] = (div(u)[k,c2] - div(u)[k,c1]) * (1/dcEdge[e]) - (curl(u)[k,v2] - curl(u)[k,v1]) * (1/dvEdge[e])   (0 above maxLevelEdgeTop)
+ * with div = velocityDivCell, curl = relativeVorticity of the stage's provisional velocity, each tendency evaluation forms d2u = L(u),
+ * then div4 = div(d2u), curl4 = curl(d2u) (the same operators, the same operand order), and finishes
+ *   tendU[k,e] = <nonlinear tendency, Del2 term included> - ((div4[k,c2] - div4[k,c1]) * (1/dcEdge[e]) - (curl4[k,v2] - curl4[k,v1]) * (1/dvEdge[e])) * coef4[e]
+ * for k <= maxLevelEdgeTop[e]: the last operation on the tendency.  coef4[e] = viscDel4 * meshScalingDel4[e] in double, formed here
+ * (meshScalingDel4 NULL: coef4 = viscDel4).  A positive viscDel4 damps (MPAS-Ocean's hmix_del4 convention).
+ * meshScalingDel4: NULL or nEdges values >= 0 in the caller's edge numbering.  viscDel4 < 0: MOKA_ERR_ARG; 0 (default) = off, and the
+ * arithmetic is then that of the nonlinear (+ Del2) form, bit for bit.  MOKA_ERR_UNSUPPORTED unless moka_set_nonlinear(st, 1) came
+ * first, and for fp32-storage states and states with a halo (the stencil reaches three cell rings; moka_halo_create and the
+ * moka_rk4_dist_* calls refuse a state with Del4 on in turn).  With moka_set_tuning key 7 a Del4 state keeps the reference's running sum
+ * (moka_state_rk4_streams: 16). */
+int  moka_set_viscosity_del4(moka_state *st, double viscDel4, const double *meshScalingDel4);
+/* which kernels formed div4 / curl4 in the last Del4 stage of this state: 1 the fused patch kernel (even K <= 64, hexagon meshes,
+ * the default and variant-4 forms), 2 the entity kernels, 0 no Del4 stage yet */
+int  moka_state_del4_path(const moka_state *st);
 
 /* ---- reverse mode of the Forward-Euler loop ----------------------------------------------------------------
  * The reference gets d sum(ssh^2) / d (initial normalVelocity, layerThickness) from Enzyme over ocn_run_loop

@@ -26,15 +26,15 @@ namespace mk {
 static std::atomic<bool> g_rk13{false};      // moka_set_tuning key 7: RK4 steps in the 13-stream form where mk::rk13_usable
 static std::mutex g_liveMutex;
 static std::unordered_set<const moka_state *> g_liveStates;
-void state_attach(moka_state *st)
+void state_attach(moka_state *st, bool halo)
 {
     std::lock_guard<std::mutex> lk(g_liveMutex);
-    if (g_liveStates.count(st)) ++st->attached;
+    if (g_liveStates.count(st)) { ++st->attached; st->halos += halo; }
 }
-void state_detach(moka_state *st)
+void state_detach(moka_state *st, bool halo)
 {
     std::lock_guard<std::mutex> lk(g_liveMutex);
-    if (g_liveStates.count(st)) --st->attached;
+    if (g_liveStates.count(st)) { --st->attached; st->halos -= halo; }
 }
 
 int fail(moka_ctx *ctx, int code, const std::string &msg)
@@ -286,17 +286,28 @@ hipError_t run_stage(moka_state *st, const StageArgs &g_in, int pBegin, int pCou
     if (st->nonlinear) {
         // vector-invariant form: potential vorticity at vertices -> edges, kinetic energy at cells, thickness flux at edges
         // (whole mesh: the stencil of the edge pass reaches two cells deep), then the generic stage kernel's nonlinear twin
-        const bool del2 = st->viscDel2 != 0.0;
-        const NlArgs nl{st->nlQv, st->nlQe, st->nlKe, del2 ? st->nlZv : nullptr, del2 ? st->nlDiv : nullptr, st->viscDel2};
+        const bool del2 = st->viscDel2 != 0.0, del4 = st->viscDel4 != 0.0;
+        NlArgs nl{st->nlQv, st->nlQe, st->nlKe, del2 ? st->nlZv : nullptr, del2 ? st->nlDiv : nullptr, st->viscDel2};
         // kernel variants 4 / 3 select the plainer forms of the nonlinear kernels too (tests run every form against the oracle)
         const int form = st->ctx->variant == 4 ? 1 : st->ctx->variant == 3 ? 3 : 0;
         // a patch range (partitioned meshes: moka_rk4_dist_stage) is served by the patch forms only
         if (pCount >= 0 && !nl_patch_forms(dev, m->lpc, form)) return hipErrorNotSupported;
+        // Del4: whole-mesh stages only (its stencil reaches three cell rings; moka_halo_create refuses such states)
+        if (del4 && (pCount >= 0 || st->nlPhase != 0)) return hipErrorNotSupported;
         if (st->nlPhase != 2) {
-            hipError_t e = launch_nl_prepare(dev, g.pu, g.ph, nl, m->lpc, form, s);
+            NlArgs np = nl;                       // Del4 needs velocityDivCell / relativeVorticity even without Del2
+            if (del4) { np.zv = st->nlZv; np.divc = st->nlDiv; }
+            hipError_t e = launch_nl_prepare(dev, g.pu, g.ph, np, m->lpc, form, s);
             if (e != hipSuccess) return e;
         }
         if (st->nlPhase == 1) return hipSuccess;
+        if (del4) {                               // div4 / curl4 of L(u), then the stage kernels' Del4 instances
+            const int path = del4_path(dev, m->d4, m->lpc, form);
+            hipError_t e = launch_del4(dev, m->d4, st->nlDiv, st->nlZv, st->nlDiv4, st->nlCurl4, path, s);
+            if (e != hipSuccess) return e;
+            st->del4Path = path;
+            nl.div4 = st->nlDiv4; nl.curl4 = st->nlCurl4; nl.coef4 = st->coef4;
+        }
         return launch_stage_nl(dev, g, nl, m->lpc, m->plan.ldsOk, form, s);
     }
     if (st->f32) {   // the one fp32-storage kernel (checked at state creation against the patches that are ever launched)
@@ -1375,6 +1386,7 @@ void rk4_end(moka_state *st)
 bool rk13_usable(const moka_state *st)
 {
     if (!g_rk13.load() || st->f32) return false;
+    if (st->nonlinear && st->viscDel4 != 0.0) return false;     // Del4: the reference's running sum (no 13-stream twin)
     const moka_mesh *mm = st->mesh;
     if (mm->plan.nPatchesLaunch != mm->plan.nPatches) return false;
     if (st->nonlinear)             // nonlinear terms: k_stage_nl5 carries the form (StageArgs.rkMode 9), the plainer kernels do not
@@ -1606,6 +1618,83 @@ int moka_set_viscosity_del2(moka_state *st, double viscDel2)
     st->viscDel2 = viscDel2;
     return MOKA_OK;
 }
+
+// the per-patch edge rows of k_d4_patch: the distinct edges of the patch's own cells and own vertices, and per cell / vertex slot the
+// patch-local row of its edge.  Once per mesh.
+static int ensure_d4_rows(moka_mesh *mm)
+{
+    if (mm->d4.start) return MOKA_OK;
+    const Plan &p = mm->plan;
+    const int ME = p.ME, VD = p.VD;
+    std::vector<int32_t> start(p.nPatches + 1, 0), rows, local(p.nE, -1);
+    std::vector<uint16_t> locC((size_t)p.nC * ME, 0), locV((size_t)p.nV * VD, 0);
+    int maxRows = 0;
+    for (int q = 0; q < p.nPatches; ++q) {
+        const size_t base = rows.size();
+        auto lid = [&](int e) {
+            if (local[e] < 0) { local[e] = (int32_t)(rows.size() - base); rows.push_back(e); }
+            return (uint16_t)std::min(local[e], 65535);
+        };
+        for (int c = p.patchCellStart[q]; c < p.patchCellStart[q + 1]; ++c)
+            for (int i = 0; i < ME; ++i)
+                if (const int e = p.eoc[(size_t)c * ME + i]; e >= 0) locC[(size_t)c * ME + i] = lid(e);
+        for (int v = p.patchVertStart[q]; v < p.patchVertStart[q + 1]; ++v)
+            for (int j = 0; j < VD; ++j)
+                if (const int e = p.eov[(size_t)v * VD + j]; e >= 0) locV[(size_t)v * VD + j] = lid(e);
+        const int n = (int)(rows.size() - base);
+        maxRows = std::max(maxRows, n);
+        for (size_t j = base; j < rows.size(); ++j) local[rows[j]] = -1;
+        start[q + 1] = (int32_t)rows.size();
+    }
+    rows.push_back(0);
+    D4Rows d{};
+    d.maxRows = maxRows > 65535 ? INT32_MAX / 2 : maxRows;    // (a patch beyond 16-bit row ids never fits the LDS: entity kernels)
+    int rc;
+    if ((rc = upload_vec(mm, rows, &d.row)) || (rc = upload_vec(mm, locC, &d.locC)) || (rc = upload_vec(mm, locV, &d.locV))) return rc;
+    if ((rc = upload_vec(mm, start, &d.start))) return rc;
+    mm->d4 = d;
+    return MOKA_OK;
+}
+
+int moka_set_viscosity_del4(moka_state *st, double viscDel4, const double *meshScalingDel4)
+{
+    if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
+    if (!(viscDel4 >= 0.0)) return fail(st->ctx, MOKA_ERR_ARG, "viscDel4 must be >= 0");
+    const Plan &p = st->mesh->plan;
+    if (viscDel4 != 0.0) {
+        if (st->f32) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "Del4 mixing: Float64 states only");
+        if (!st->nonlinear)
+            return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "Del4 mixing rides on the nonlinear tendencies: call moka_set_nonlinear first");
+        if (st->halos > 0)
+            return fail(st->ctx, MOKA_ERR_UNSUPPORTED,
+                        "Del4 mixing: not on a state with a halo (its stencil reaches three cell rings, the nonlinear halo two)");
+        if (meshScalingDel4)
+            for (int e = 0; e < p.nE; ++e)
+                if (!(meshScalingDel4[e] >= 0.0)) return fail(st->ctx, MOKA_ERR_ARG, "meshScalingDel4 entries must be >= 0");
+    }
+    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    int rc = flush_lazy(st, true, true);       // pending tendencies belong to the coefficients they were computed with
+    if (rc) return rc;
+    if (viscDel4 == 0.0) { st->viscDel4 = 0.0; return MOKA_OK; }
+    if (!st->nlZv) {
+        if ((rc = alloc_field(st, &st->nlZv, (size_t)p.K * p.nV))) return rc;
+        if ((rc = alloc_field(st, &st->nlDiv, (size_t)p.K * p.nC))) return rc;
+    }
+    if (!st->nlDiv4) {
+        if ((rc = alloc_field(st, &st->nlDiv4, (size_t)p.K * p.nC))) return rc;
+        if ((rc = alloc_field(st, &st->nlCurl4, (size_t)p.K * p.nV))) return rc;
+        if ((rc = alloc_field(st, &st->coef4, (size_t)p.nE))) return rc;
+    }
+    if ((rc = ensure_d4_rows(st->mesh))) return rc;
+    std::vector<double> coef(p.nE, viscDel4);  // viscDel4 * meshScalingDel4[e], in double, in plan order
+    if (meshScalingDel4)
+        for (int e = 0; e < p.nE; ++e) coef[e] = viscDel4 * meshScalingDel4[p.edgeN2O[e]];
+    if ((rc = h2d(st->ctx, st->coef4, coef.data(), coef.size() * sizeof(double)))) return rc;
+    st->viscDel4 = viscDel4;
+    return MOKA_OK;
+}
+
+int moka_state_del4_path(const moka_state *st) { return st ? st->del4Path : 0; }
 
 // ---------------------------------------------------------------------------------------------
 // reverse mode of the Forward-Euler loop.  The reference differentiates

@@ -346,6 +346,8 @@ int moka_halo_create(moka_state *st, int32_t nNeighbors, const int32_t *sendCell
         return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
     *out = nullptr;
     const Plan &p = st->mesh->plan;
+    if (st->viscDel4 != 0.0)
+        return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "Del4 mixing: not on a state with a halo (its stencil reaches three cell rings, the nonlinear halo two)");
     if (nNeighbors > 60) return fail(st->ctx, MOKA_ERR_ARG, "at most 60 neighbours");
     if (nPatchesBoundary < 0 || nPatchesOwned < nPatchesBoundary || nPatchesOwned > p.nPatches)
         return fail(st->ctx, MOKA_ERR_ARG, "patch ranges must satisfy 0 <= boundary <= owned <= nPatches");
@@ -434,7 +436,7 @@ int moka_halo_create(moka_state *st, int32_t nNeighbors, const int32_t *sendCell
         moka_halo_destroy(h);
         return fail(st->ctx, MOKA_ERR_HIP, "hipEventCreate failed");
     }
-    state_attach(st);
+    state_attach(st, true);
     h->counted = true;
     *out = h;
     return MOKA_OK;
@@ -443,7 +445,7 @@ int moka_halo_create(moka_state *st, int32_t nNeighbors, const int32_t *sendCell
 void moka_halo_destroy(moka_halo *h)
 {
     if (!h) return;
-    if (h->counted) state_detach(h->st);
+    if (h->counted) state_detach(h->st, true);
     (void)hipSetDevice(h->st->ctx->device);
     (void)hipStreamSynchronize(h->st->ctx->stream);
     (void)hipStreamSynchronize(h->st->ctx->comm);
@@ -872,6 +874,7 @@ int moka_rk4_dist_begin(moka_halo *h, double dt)
 {
     if (!h) return fail(nullptr, MOKA_ERR_ARG, "halo is NULL");
     moka_state *st = h->st;
+    if (st->viscDel4 != 0.0) return hfail(h, MOKA_ERR_UNSUPPORTED, "Del4 mixing: whole meshes only (no distributed RK4 step)");
     HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
     // like moka_step_rk4: lazily pending diagnostics / stage-4 tendencies of the previous step are superseded, not computed
     h->dt = dt;
@@ -896,6 +899,7 @@ int moka_rk4_dist_stage(moka_halo *h, int stage, int part)
     if (!h) return fail(nullptr, MOKA_ERR_ARG, "halo is NULL");
     if (stage < 1 || stage > 4 || part < 0 || part > 4) return hfail(h, MOKA_ERR_ARG, "stage must be 1..4, part 0..4");
     moka_state *st = h->st;
+    if (st->viscDel4 != 0.0) return hfail(h, MOKA_ERR_UNSUPPORTED, "Del4 mixing: whole meshes only (no distributed RK4 step)");
     HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
     if (part == 2) {
         const StageArgs g = rk4_stage_args(st, stage, h->dt, h->ssh0);
@@ -948,6 +952,8 @@ int moka_rk4_dist_parts_available(const moka_halo *h)
 // direct transport, the device-queue half of a stage: boundary patches, push (comm stream), interior patches
 int moka_rk4_dist_stage_launch(moka_halo *h, int stage)
 {
+    if (!h) return fail(nullptr, MOKA_ERR_ARG, "halo is NULL");
+    if (h->st->viscDel4 != 0.0) return hfail(h, MOKA_ERR_UNSUPPORTED, "Del4 mixing: whole meshes only (no distributed RK4 step)");
     int rc;
     if ((rc = moka_rk4_dist_stage(h, stage, 0))) return rc;
     if ((rc = moka_halo_push_begin(h, stage))) return rc;

@@ -145,6 +145,11 @@ struct NlArgs {
     double *zv;     // (K, nV) relativeVorticity
     double *divc;   // (K, nC) velocityDivCell
     double visc;
+    // Del4 momentum mixing (moka_set_viscosity_del4): read by the stage kernels' Del4 instances only (launch_stage_nl picks them
+    // when coef4 != nullptr).  div4 / curl4 = DivergenceOnCell / CurlOnVertex of L(u), the Del2 bracket of zv / divc (launch_del4)
+    const double *div4;    // (K, nC)
+    const double *curl4;   // (K, nV)
+    const double *coef4;   // (nE) viscDel4 * meshScalingDel4
 };
 // form: 0 = best available, 1 = patch kernels without the LDS q_e rows, 2 = 16-byte-lane entity kernels, 3 = generic lane-group kernels
 // (prepare and stage must be called with the same form: forms 0 / 1 keep F alone in NlArgs.fq, forms 2 / 3 {F, q_e} pairs)
@@ -157,6 +162,20 @@ int nl_cap_limit();
 hipError_t launch_nl_prepare(const MeshDev &m, const double *u, const double *h, const NlArgs &nl, int lpc, int form, hipStream_t s);
 // rowsOk: the plan built the patch row lists (rowStart / rowEdge / leoe; Plan.ldsOk)
 hipError_t launch_stage_nl(const MeshDev &m, const StageArgs &a, const NlArgs &nl, int lpc, bool rowsOk, int form, hipStream_t s);
+// Del4 momentum mixing: div4 / curl4 of d2u = L(u) from divc / zv of the preparation pass (which must have run on the same stream).
+// D4Rows: per-patch lists of the edges whose d2u the patch's own cells and vertices read (built once per mesh, plan order).
+struct D4Rows {
+    const int32_t *start;   // nPatches + 1: rows of patch q are row[start[q] .. start[q+1])
+    const int32_t *row;     // edge ids
+    const uint16_t *locC;   // (ME, nC): patch-local row of the edge in slot i of the cell (0 for empty slots)
+    const uint16_t *locV;   // (VD, nV): patch-local row of the edge in slot j of the vertex
+    int32_t maxRows;
+};
+// 1 = the fused patch kernel k_d4_patch serves this mesh / form (the nonlinear path runs its patch preparation pass and the rows of
+// the largest patch fit the LDS budget), 2 = the entity kernels k_d4_cell / k_d4_vertex
+int del4_path(const MeshDev &m, const D4Rows &r, int lpc, int form);
+hipError_t launch_del4(const MeshDev &m, const D4Rows &r, const double *divc, const double *zv, double *div4, double *curl4, int path,
+                       hipStream_t s);
 
 // ---- reverse mode of one Forward-Euler step: gather form, the oracle's summation order ----
 struct AdjMesh {

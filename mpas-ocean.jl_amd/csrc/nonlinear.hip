@@ -72,8 +72,9 @@ __global__ __launch_bounds__(BLOCK) void k_nl_cell(const MeshDev m, const double
     }
 }
 
-// the stage kernel with the nonlinear velocity tendency; the thickness part is that of k_stage
-template <int LPC>
+// the stage kernel with the nonlinear velocity tendency; the thickness part is that of k_stage.  D4: Del4 momentum mixing (NlArgs.div4 /
+// curl4 / coef4), subtracted after everything else -- a compile-time switch, so that the instances without it are unchanged
+template <int LPC, bool D4 = false>
 __global__ __launch_bounds__(BLOCK) void k_stage_nl(const MeshDev m, const StageArgs a, const NlArgs nl)
 {
     constexpr int NG = BLOCK / LPC;
@@ -123,9 +124,9 @@ __global__ __launch_bounds__(BLOCK) void k_stage_nl(const MeshDev m, const Stage
         const int c1 = cptr(m.ehdr)[(size_t)e * 4], c2 = cptr(m.ehdr)[(size_t)e * 4 + 1], mlt = cptr(m.ehdr)[(size_t)e * 4 + 3];
         const double g = cptr(m.gInvDc)[e], invDc = cptr(m.invDc)[e];
         const double ds = a.ssh[c2] - a.ssh[c1];
-        const bool del2 = nl.zv != nullptr;
-        const double invDv = del2 ? 1.0 / cptr(m.dvEdge)[e] : 0.0;
-        const int v1 = del2 ? cptr(m.voe)[(size_t)e * 2] : 0, v2 = del2 ? cptr(m.voe)[(size_t)e * 2 + 1] : 0;
+        const bool del2 = nl.zv != nullptr, nv = del2 || D4;
+        const double invDv = nv ? 1.0 / cptr(m.dvEdge)[e] : 0.0;
+        const int v1 = nv ? cptr(m.voe)[(size_t)e * 2] : 0, v2 = nv ? cptr(m.voe)[(size_t)e * 2 + 1] : 0;
         for (int k = l; k < K; k += LPC) {
             const size_t off = (size_t)e * K + k;
             double t = 0.0;
@@ -142,6 +143,9 @@ __global__ __launch_bounds__(BLOCK) void k_stage_nl(const MeshDev m, const Stage
                 if (del2)                                                               // horizontal_momentum_mixing.jl:75-78
                     t += ((nl.divc[(size_t)c2 * K + k] - nl.divc[(size_t)c1 * K + k]) * invDc -
                           (nl.zv[(size_t)v2 * K + k] - nl.zv[(size_t)v1 * K + k]) * invDv) * nl.visc;
+                if constexpr (D4)                                                       // Del4: the last operation on t
+                    t -= ((nl.div4[(size_t)c2 * K + k] - nl.div4[(size_t)c1 * K + k]) * invDc -
+                          (nl.curl4[(size_t)v2 * K + k] - nl.curl4[(size_t)v1 * K + k]) * invDv) * cptr(nl.coef4)[e];
             }
             if (a.tendU) a.tendU[off] = t;
             const double ucur = a.cu ? a.cu[off] : a.pu[off];
@@ -216,6 +220,7 @@ __global__ __launch_bounds__(BLOCK) void k_nl_cell2(const MeshDev m, const doubl
     }
 }
 
+template <bool D4 = false>
 __global__ __launch_bounds__(BLOCK) void k_stage_nl2(const MeshDev m, const StageArgs a, const NlArgs nl)
 {
     constexpr int NG = BLOCK / 32;
@@ -290,6 +295,13 @@ __global__ __launch_bounds__(BLOCK) void k_stage_nl2(const MeshDev m, const Stag
             const double2 d1 = ld2(nl.divc, c1, K, l), d2 = ld2(nl.divc, c2, K, l), z1 = ld2(nl.zv, v1, K, l), z2 = ld2(nl.zv, v2, K, l);
             if (ax) t.x += ((d2.x - d1.x) * invDc - (z2.x - z1.x) * invDv) * nl.visc;
             if (ay) t.y += ((d2.y - d1.y) * invDc - (z2.y - z1.y) * invDv) * nl.visc;
+        }
+        if constexpr (D4) {                                             // Del4: the last operation on t
+            const double invDv = 1.0 / m.dvEdge[e], c4 = nl.coef4[e];
+            const int v1 = m.voe[(size_t)e * 2], v2 = m.voe[(size_t)e * 2 + 1];
+            const double2 d1 = ld2(nl.div4, c1, K, l), d2 = ld2(nl.div4, c2, K, l), z1 = ld2(nl.curl4, v1, K, l), z2 = ld2(nl.curl4, v2, K, l);
+            if (ax) t.x -= ((d2.x - d1.x) * invDc - (z2.x - z1.x) * invDv) * c4;
+            if (ay) t.y -= ((d2.y - d1.y) * invDc - (z2.y - z1.y) * invDv) * c4;
         }
         if (a.tendU) st2(a.tendU, e, K, l, t);
         const double2 ucur = a.cu ? ld2(a.cu, e, K, l) : ld2(a.pu, e, K, l);
@@ -648,7 +660,7 @@ static inline size_t np5_lds_bytes(const MeshDev &m)
 
 constexpr int NL3_MAXE = 96;   // own edges of a patch the LDS records of k_stage_nl3 hold (P = 16 cells x 6)
 
-template <int ME_, int ME2_>
+template <int ME_, int ME2_, bool D4 = false>
 __global__ __launch_bounds__(BLOCK, 3) void k_stage_nl3(const MeshDev m, const StageArgs a, const NlArgs nl)
 {
     constexpr int NG = BLOCK / 32;
@@ -767,6 +779,12 @@ __global__ __launch_bounds__(BLOCK, 3) void k_stage_nl3(const MeshDev m, const S
             if (ax) t.x += ((d2.x - d1.x) * invDc - (z2.x - z1.x) * invDv) * nl.visc;
             if (ay) t.y += ((d2.y - d1.y) * invDc - (z2.y - z1.y) * invDv) * nl.visc;
         }
+        if constexpr (D4) {                                             // Del4: the last operation on t
+            const double invDv = 1.0 / m.dvEdge[e], c4 = nl.coef4[e];
+            const double2 d1 = ld2(nl.div4, c1, K, l), d2 = ld2(nl.div4, c2, K, l), z1 = ld2(nl.curl4, vo.x, K, l), z2 = ld2(nl.curl4, vo.y, K, l);
+            if (ax) t.x -= ((d2.x - d1.x) * invDc - (z2.x - z1.x) * invDv) * c4;
+            if (ay) t.y -= ((d2.y - d1.y) * invDc - (z2.y - z1.y) * invDv) * c4;
+        }
         if (a.tendU) st2(a.tendU, e, K, l, t);
         if (a.pu_out) st2(a.pu_out, e, K, l, make_double2(ucur.x + a.a * t.x, ucur.y + a.a * t.y));
         if (a.nu_out) st2(a.nu_out, e, K, l, make_double2(nbu.x + a.b * t.x, nbu.y + a.b * t.y));
@@ -777,7 +795,7 @@ __global__ __launch_bounds__(BLOCK, 3) void k_stage_nl3(const MeshDev m, const S
 // averages the potential vorticity to the edges ONCE per patch: q_e of every edge row the patch touches (its own edges, then
 // the halo edges of the plan's row list, ~110 rows of a 16-cell patch) is built in LDS from 2 qv rows each, and the edge
 // loop reads q_e of its neighbour edges from LDS by the plan's patch-local row ids (leoe).  F rows stay global gathers.
-template <int ME_, int ME2_, int NT>
+template <int ME_, int ME2_, int NT, bool D4 = false>
 __global__ __launch_bounds__(NT, 4) void k_stage_nl4(const MeshDev m, const StageArgs a, const NlArgs nl)
 {
     constexpr int NG = NT / 32, RB = 8;
@@ -910,6 +928,13 @@ __global__ __launch_bounds__(NT, 4) void k_stage_nl4(const MeshDev m, const Stag
             if (ax) t.x += ((d2.x - d1.x) * invDc - (z2.x - z1.x) * invDv) * nl.visc;
             if (ay) t.y += ((d2.y - d1.y) * invDc - (z2.y - z1.y) * invDv) * nl.visc;
         }
+        if constexpr (D4) {                                             // Del4: the last operation on t
+            const int2 vo = reinterpret_cast<const int2 *>(m.voe)[e];
+            const double invDv = 1.0 / m.dvEdge[e], c4 = nl.coef4[e];
+            const double2 d1 = ld2(nl.div4, c1, K, l), d2 = ld2(nl.div4, c2, K, l), z1 = ld2(nl.curl4, vo.x, K, l), z2 = ld2(nl.curl4, vo.y, K, l);
+            if (ax) t.x -= ((d2.x - d1.x) * invDc - (z2.x - z1.x) * invDv) * c4;
+            if (ay) t.y -= ((d2.y - d1.y) * invDc - (z2.y - z1.y) * invDv) * c4;
+        }
         if (a.tendU) st2(a.tendU, e, K, l, t);
         if (a.pu_out) st2(a.pu_out, e, K, l, make_double2(ucur.x + a.a * t.x, ucur.y + a.a * t.y));
         if (a.nu_out) st2(a.nu_out, e, K, l, make_double2(nbu.x + a.b * t.x, nbu.y + a.b * t.y));
@@ -929,7 +954,7 @@ __global__ __launch_bounds__(NT, 4) void k_stage_nl4(const MeshDev m, const Stag
 // 7 %, the F row cache another 1.4 % (a gather that hits the L2 is cheap: rows gathered from memory per patch, 880 -> 660, do not
 // predict the time).  Three workgroups per CU (512 threads bounded to 80 registers, the F gathers in two batches) were built and
 // measured, too: no faster than two with all ten gathers in one batch.
-template <int ME_, int ME2_, int NT, int MINW, bool CF>
+template <int ME_, int ME2_, int NT, int MINW, bool CF, bool D4 = false>
 __global__ __launch_bounds__(NT, MINW) void k_stage_nl5(const MeshDev m, const StageArgs a, const NlArgs nl)
 {
     constexpr int NG = NT / 32;
@@ -1171,6 +1196,14 @@ __global__ __launch_bounds__(NT, MINW) void k_stage_nl5(const MeshDev m, const S
             if (ax) t.x += ((d2.x - d1.x) * invDc - (z2.x - z1.x) * invDv) * nl.visc;
             if (ay) t.y += ((d2.y - d1.y) * invDc - (z2.y - z1.y) * invDv) * nl.visc;
         }
+        if constexpr (D4) {                                             // Del4: the last operation on t
+            const int2 vo = reinterpret_cast<const int2 *>(m.voe)[e];
+            const double invDv = 1.0 / m.dvEdge[e], c4 = nl.coef4[e];
+            const double2 d1 = ldo(nl.div4, (unsigned)(c1) * rowB + lo), d2 = ldo(nl.div4, (unsigned)(c2) * rowB + lo);
+            const double2 z1 = ldo(nl.curl4, (unsigned)(vo.x) * rowB + lo), z2 = ldo(nl.curl4, (unsigned)(vo.y) * rowB + lo);
+            if (ax) t.x -= ((d2.x - d1.x) * invDc - (z2.x - z1.x) * invDv) * c4;
+            if (ay) t.y -= ((d2.y - d1.y) * invDc - (z2.y - z1.y) * invDv) * c4;
+        }
         pOff = (unsigned)(e) * rowB + lo;
         pT = t;
         pA = make_double2(ucur.x + a.a * t.x, ucur.y + a.a * t.y);
@@ -1227,12 +1260,12 @@ static hipError_t launch_nl_prepare_lpc(const MeshDev &m, const double *u, const
     return hipGetLastError();
 }
 
-template <int LPC>
+template <int LPC, bool D4>
 static hipError_t launch_stage_nl_lpc(const MeshDev &m, const StageArgs &a, const NlArgs &nl, hipStream_t s)
 {
     const int ng = BLOCK / LPC;
     const int grid = std::min(std::max((std::max(m.nE, m.nC) + ng - 1) / ng, 1), 65536);
-    hipLaunchKernelGGL((k_stage_nl<LPC>), dim3(grid), dim3(BLOCK), 0, s, m, a, nl);
+    hipLaunchKernelGGL((k_stage_nl<LPC, D4>), dim3(grid), dim3(BLOCK), 0, s, m, a, nl);
     return hipGetLastError();
 }
 
@@ -1269,7 +1302,9 @@ bool nl_stage_is_nl5(const MeshDev &m, int lpc, int form)
     return nl5_cap(m, cf) >= 16;
 }
 
-hipError_t launch_stage_nl(const MeshDev &m, const StageArgs &a, const NlArgs &nl, int lpc, bool rowsOk, int form, hipStream_t s)
+// D4: the instances with Del4 mixing (NlArgs.coef4 != nullptr); their LDS attribute slots are 8 .. 12
+template <bool D4>
+static hipError_t launch_stage_nl_t(const MeshDev &m, const StageArgs &a, const NlArgs &nl, int lpc, bool rowsOk, int form, hipStream_t s)
 {
     const int shape = g_nlShape.load();
     if (lpc == 64 && nl3_ok(m) && form == 0 && shape != 1 && m.pvStart && m.maxPV > 0 &&
@@ -1281,42 +1316,194 @@ hipError_t launch_stage_nl(const MeshDev &m, const StageArgs &a, const NlArgs &n
         mc.pvCap = nl5_cap(m, cf);
         if (mc.pvCap >= 16) {
             const size_t lds = nl5_lds_bytes(mc, mc.pvCap, cf);
-            const int slot = 17 + (shape == 2 ? 2 : 0) + (cf ? 1 : 0);
-            const void *fn = shape == 2 ? (cf ? reinterpret_cast<const void *>(k_stage_nl5<6, 10, 256, 3, true>) : reinterpret_cast<const void *>(k_stage_nl5<6, 10, 256, 3, false>))
-                                        : (cf ? reinterpret_cast<const void *>(k_stage_nl5<6, 10, 512, 4, true>) : reinterpret_cast<const void *>(k_stage_nl5<6, 10, 512, 4, false>));
+            const int slot = (D4 ? 9 : 17) + (shape == 2 ? 2 : 0) + (cf ? 1 : 0);
+            const void *fn = shape == 2 ? (cf ? reinterpret_cast<const void *>(k_stage_nl5<6, 10, 256, 3, true, D4>) : reinterpret_cast<const void *>(k_stage_nl5<6, 10, 256, 3, false, D4>))
+                                        : (cf ? reinterpret_cast<const void *>(k_stage_nl5<6, 10, 512, 4, true, D4>) : reinterpret_cast<const void *>(k_stage_nl5<6, 10, 512, 4, false, D4>));
             if (lds > 64 * 1024 && lds_attr_needed(slot)) {
                 hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
                 if (e != hipSuccess) return e;
             }
             const dim3 g(nl_grid(m.nPatches));
-            if (shape == 2 && cf) hipLaunchKernelGGL((k_stage_nl5<6, 10, 256, 3, true>), g, dim3(256), lds, s, mc, a, nl);
-            else if (shape == 2) hipLaunchKernelGGL((k_stage_nl5<6, 10, 256, 3, false>), g, dim3(256), lds, s, mc, a, nl);
-            else if (cf) hipLaunchKernelGGL((k_stage_nl5<6, 10, 512, 4, true>), g, dim3(512), lds, s, mc, a, nl);
-            else hipLaunchKernelGGL((k_stage_nl5<6, 10, 512, 4, false>), g, dim3(512), lds, s, mc, a, nl);
+            if (shape == 2 && cf) hipLaunchKernelGGL((k_stage_nl5<6, 10, 256, 3, true, D4>), g, dim3(256), lds, s, mc, a, nl);
+            else if (shape == 2) hipLaunchKernelGGL((k_stage_nl5<6, 10, 256, 3, false, D4>), g, dim3(256), lds, s, mc, a, nl);
+            else if (cf) hipLaunchKernelGGL((k_stage_nl5<6, 10, 512, 4, true, D4>), g, dim3(512), lds, s, mc, a, nl);
+            else hipLaunchKernelGGL((k_stage_nl5<6, 10, 512, 4, false, D4>), g, dim3(512), lds, s, mc, a, nl);
             return hipGetLastError();
         }
     }
     if (a.rkMode == 9) return hipErrorNotSupported;      // the 13-stream form's last stage exists in k_stage_nl5 only (mk::rk13_usable asks nl_stage_is_nl5 first)
     if (lpc == 64 && nl3_ok(m) && rowsOk && form == 0 && nl4_lds_bytes(m) <= 80 * 1024) {     // two 512-thread workgroups per CU
         const size_t lds = nl4_lds_bytes(m);
-        if (lds_attr_needed(16)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_stage_nl4<6, 10, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+        if (lds_attr_needed(D4 ? 8 : 16)) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_stage_nl4<6, 10, 512, D4>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
             if (e != hipSuccess) return e;
         }
-        hipLaunchKernelGGL((k_stage_nl4<6, 10, 512>), dim3(nl_grid(m.nPatches)), dim3(512), lds, s, m, a, nl);
+        hipLaunchKernelGGL((k_stage_nl4<6, 10, 512, D4>), dim3(nl_grid(m.nPatches)), dim3(512), lds, s, m, a, nl);
         return hipGetLastError();
     }
     if (lpc == 64 && nl3_ok(m) && form <= 1) {
-        hipLaunchKernelGGL((k_stage_nl3<6, 10>), dim3(nl_grid(m.nPatches)), dim3(BLOCK), 0, s, m, a, nl);
+        hipLaunchKernelGGL((k_stage_nl3<6, 10, D4>), dim3(nl_grid(m.nPatches)), dim3(BLOCK), 0, s, m, a, nl);
         return hipGetLastError();
     }
     if (lpc == 64 && m.K <= 64 && !(m.K & 1) && form <= 2) {
-        hipLaunchKernelGGL(k_stage_nl2, grid2(std::max(m.nE, m.nC)), dim3(BLOCK), 0, s, m, a, nl);
+        hipLaunchKernelGGL(k_stage_nl2<D4>, grid2(std::max(m.nE, m.nC)), dim3(BLOCK), 0, s, m, a, nl);
         return hipGetLastError();
     }
-#define CALL(L) launch_stage_nl_lpc<L>(m, a, nl, s)
+#define CALL(L) launch_stage_nl_lpc<L, D4>(m, a, nl, s)
     DISPATCH_LPC(lpc, CALL)
 #undef CALL
 }
 
+hipError_t launch_stage_nl(const MeshDev &m, const StageArgs &a, const NlArgs &nl, int lpc, bool rowsOk, int form, hipStream_t s)
+{
+    return nl.coef4 ? launch_stage_nl_t<true>(m, a, nl, lpc, rowsOk, form, s) : launch_stage_nl_t<false>(m, a, nl, lpc, rowsOk, form, s);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Del4 (biharmonic) momentum mixing (moka_set_viscosity_del4).  d2u = L(u) is the Del2 bracket of the preparation pass's
+// velocityDivCell / relativeVorticity, exactly 0 above maxLevelEdgeTop:
+//   d2u[k,e] = (divc[k,c2] - divc[k,c1]) * (1/dcEdge) - (zv[k,v2] - zv[k,v1]) * (1/dvEdge)
+// div4 = DivergenceOnCell(d2u) and curl4 = CurlOnVertex(d2u) in the operand order of k_nl_cell / k_nl_vertex; the stage kernels'
+// D4 instances subtract L(d2u) * coef4.  d2u never goes to memory: the patch kernel holds it in LDS, the entity kernels recompute
+// it per use (same expression, same bits).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double d4_d2u(const MeshDev &m, const double *divc, const double *zv, int e, int k)
+{
+    const int4 hd = reinterpret_cast<const int4 *>(m.ehdr)[e];
+    if (k >= hd.w) return 0.0;
+    const int2 vo = reinterpret_cast<const int2 *>(m.voe)[e];
+    const size_t K = (size_t)m.K;
+    return (divc[hd.y * K + k] - divc[hd.x * K + k]) * m.invDc[e] - (zv[vo.y * K + k] - zv[vo.x * K + k]) * (1.0 / m.dvEdge[e]);
+}
+
+// fallback (any K, any mesh): one thread per (entity, level)
+__global__ __launch_bounds__(BLOCK) void k_d4_cell(const MeshDev m, const double *divc, const double *zv, double *div4)
+{
+    const int K = m.K, ME = m.ME;
+    for (int64_t i = blockIdx.x * (int64_t)BLOCK + threadIdx.x; i < (int64_t)m.nC * K; i += (int64_t)gridDim.x * BLOCK) {
+        const int c = (int)(i / K), k = (int)(i % K);
+        double d = 0.0;
+        for (int j = 0; j < ME; ++j) {
+            const int e = m.eoc[(size_t)c * ME + j];
+            if (e < 0) continue;
+            d -= d4_d2u(m, divc, zv, e, k) * m.sdv[(size_t)c * ME + j];                       // Operators.jl:18,36
+        }
+        div4[i] = d / m.areaCell[c];                                                             // Operators.jl:41
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_d4_vertex(const MeshDev m, const double *divc, const double *zv, double *curl4)
+{
+    const int K = m.K, VD = m.VD;
+    for (int64_t i = blockIdx.x * (int64_t)BLOCK + threadIdx.x; i < (int64_t)m.nV * K; i += (int64_t)gridDim.x * BLOCK) {
+        const int v = (int)(i / K), k = (int)(i % K);
+        double z = 0.0;
+        for (int j = 0; j < VD; ++j)
+            z += m.cv[(size_t)v * VD + j] * d4_d2u(m, divc, zv, m.eov[(size_t)v * VD + j], k);   // Operators.jl:137-146
+        curl4[i] = z;
+    }
+}
+
+// hot path (the patch forms of the nonlinear path: even K <= 64, nl3_ok): one workgroup per patch.  d2u of every edge the patch's own
+// cells and own vertices touch (D4Rows) is formed in LDS -- RB rows in flight per half-wave, 16-byte lanes -- then div4 of the own
+// cells and curl4 of the own vertices are read from there.  An edge shared by two patches is formed by both, with the same bits.
+constexpr int D4_NT = 512;
+template <int ME_, int VD_>
+__global__ __launch_bounds__(D4_NT, 2) void k_d4_patch(const MeshDev m, const D4Rows r, const double *__restrict__ divc,
+                                                        const double *__restrict__ zv, double *div4, double *curl4)
+{
+    constexpr int NG = D4_NT / 32, RB = 4;
+    extern __shared__ __align__(16) unsigned char d4_smem[];
+    double *sD = reinterpret_cast<double *>(d4_smem);                      // [maxRows][K]  d2u rows
+    const int grp = threadIdx.x >> 5, l = threadIdx.x & 31, K = m.K, k0 = 2 * l;
+    const bool act = k0 < K;
+    const unsigned rowB = (unsigned)K * 8u, lo = (unsigned)l * 16u;
+    const int pl_ = patch_of_block(m.nPatches);
+    if (pl_ >= m.nPatches) return;
+    const int p = pl_ + m.patchBegin;
+    const int r0 = r.start[p], nRows = r.start[p + 1] - r0;
+    if (act) {
+        for (int i = grp; i < nRows; i += NG * RB) {
+            double2 d1[RB], d2[RB], z1[RB], z2[RB];
+            double idc[RB], idv[RB];
+            int mlt[RB];
+#pragma unroll
+            for (int j = 0; j < RB; ++j) {
+                const int rr = i + j * NG;
+                const int e = r.row[r0 + (rr < nRows ? rr : i)];
+                const int4 hd = reinterpret_cast<const int4 *>(m.ehdr)[e];
+                const int2 vo = reinterpret_cast<const int2 *>(m.voe)[e];
+                mlt[j] = hd.w; idc[j] = m.invDc[e]; idv[j] = 1.0 / m.dvEdge[e];
+                d1[j] = ldo(divc, (unsigned)hd.x * rowB + lo); d2[j] = ldo(divc, (unsigned)hd.y * rowB + lo);
+                z1[j] = ldo(zv, (unsigned)vo.x * rowB + lo); z2[j] = ldo(zv, (unsigned)vo.y * rowB + lo);
+            }
+#pragma unroll
+            for (int j = 0; j < RB; ++j) {
+                const int rr = i + j * NG;
+                if (rr >= nRows) break;
+                const double x = (d2[j].x - d1[j].x) * idc[j] - (z2[j].x - z1[j].x) * idv[j];
+                const double y = (d2[j].y - d1[j].y) * idc[j] - (z2[j].y - z1[j].y) * idv[j];
+                reinterpret_cast<double2 *>(sD + (size_t)rr * K)[l] = make_double2(k0 < mlt[j] ? x : 0.0, k0 + 1 < mlt[j] ? y : 0.0);
+            }
+        }
+    }
+    __syncthreads();
+    if (!act) return;
+    auto row = [&](unsigned id) -> double2 { return reinterpret_cast<const double2 *>(sD + (size_t)id * K)[l]; };
+    const int c0 = m.patchCellStart[p], nc = m.patchCellStart[p + 1] - c0;
+    for (int ci = grp; ci < nc; ci += NG) {
+        const int c = c0 + ci;
+        double2 d = make_double2(0.0, 0.0);
+#pragma unroll
+        for (int i = 0; i < ME_; ++i) {
+            const bool ok = m.eoc[(size_t)c * ME_ + i] >= 0;
+            const double sd = m.sdv[(size_t)c * ME_ + i];
+            const double2 x = row(r.locC[(size_t)c * ME_ + i]);
+            const double dx = d.x - x.x * sd, dy = d.y - x.y * sd;                              // Operators.jl:18,36
+            d.x = ok ? dx : d.x; d.y = ok ? dy : d.y;
+        }
+        const double area = m.areaCell[c];
+        sto(div4, (unsigned)c * rowB + lo, make_double2(d.x / area, d.y / area));               // Operators.jl:41
+    }
+    const int v0 = m.patchVertStart[p], nv = m.patchVertStart[p + 1] - v0;
+    for (int vi = grp; vi < nv; vi += NG) {
+        const int v = v0 + vi;
+        double2 z = make_double2(0.0, 0.0);
+#pragma unroll
+        for (int j = 0; j < VD_; ++j) {
+            const double cvj = m.cv[(size_t)v * VD_ + j];
+            const double2 x = row(r.locV[(size_t)v * VD_ + j]);
+            z.x += cvj * x.x; z.y += cvj * x.y;                                                 // Operators.jl:137-146
+        }
+        sto(curl4, (unsigned)v * rowB + lo, z);
+    }
+}
+
+int del4_path(const MeshDev &m, const D4Rows &r, int lpc, int form)
+{
+    if (nl_patch_forms(m, lpc, form) && r.start && (size_t)r.maxRows * m.K * 8 <= 80 * 1024 &&
+        (uint64_t)std::max(m.nE, std::max(m.nV, m.nC)) * m.K * 8 < (1ull << 32))
+        return 1;
+    return 2;
+}
+
+hipError_t launch_del4(const MeshDev &m, const D4Rows &r, const double *divc, const double *zv, double *div4, double *curl4, int path,
+                       hipStream_t s)
+{
+    if (path == 1) {
+        const size_t lds = (size_t)r.maxRows * m.K * 8;
+        if (lds > 64 * 1024 && lds_attr_needed(13)) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_d4_patch<6, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL((k_d4_patch<6, 3>), dim3(nl_grid(m.nPatches)), dim3(D4_NT), lds, s, m, r, divc, zv, div4, curl4);
+        return hipGetLastError();
+    }
+    auto grid = [](int64_t n) { return dim3((unsigned)std::min<int64_t>(std::max<int64_t>((n + BLOCK - 1) / BLOCK, 1), 65536)); };
+    hipLaunchKernelGGL(k_d4_cell, grid((int64_t)m.nC * m.K), dim3(BLOCK), 0, s, m, divc, zv, div4);
+    hipLaunchKernelGGL(k_d4_vertex, grid((int64_t)m.nV * m.K), dim3(BLOCK), 0, s, m, divc, zv, curl4);
+    return hipGetLastError();
+}
+
 }  // namespace moka
+

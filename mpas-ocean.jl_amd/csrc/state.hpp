@@ -48,6 +48,7 @@ struct moka_mesh {
     // (maxOwnE, maxOwnC) of a launched patch sub-range: a partition's halo-only patches own up to 6 edges per cell
     // and are never launched, so the LDS carve of a boundary / interior launch is sized by the patches it covers
     std::map<std::pair<int, int>, std::pair<int, int>> rangeMax;
+    moka::D4Rows d4{};        // Del4 mixing: per-patch edge rows of k_d4_patch, built at the first moka_set_viscosity_del4 (start == nullptr: not yet)
 };
 
 struct LevelBufs {
@@ -101,8 +102,12 @@ struct moka_state {
     int nlPhase = 0;                  // what run_stage launches for a nonlinear state: 0 preparation + stage, 1 preparation only, 2 stage only
     double *nlQv = nullptr, *nlQe = nullptr, *nlKe = nullptr;
     int feFast = -1;                            // moka_last_fe_path
-    double *nlZv = nullptr, *nlDiv = nullptr;   // Del2 mixing (moka_set_viscosity_del2)
+    double *nlZv = nullptr, *nlDiv = nullptr;   // Del2 mixing (moka_set_viscosity_del2); Del4 reads them too
     double viscDel2 = 0.0;
+    double *nlDiv4 = nullptr, *nlCurl4 = nullptr, *coef4 = nullptr;   // Del4 mixing (moka_set_viscosity_del4): div4, curl4, viscDel4 * scaling
+    double viscDel4 = 0.0;
+    int del4Path = 0;                 // moka_state_del4_path
+    int halos = 0;                    // live moka_halo objects on this state (Del4 refuses them)
     std::vector<void *> allocs;
     // objects that hold or have exported the addresses of this state's arrays (halos, tapes): while any exists the arrays stay
     // where they are (moka_state_optimize_placement refuses)
@@ -118,8 +123,9 @@ using namespace moka;
 int fail(moka_ctx *ctx, int code, const std::string &msg);
 // Halos and tapes count themselves in moka_state.attached while they hold the state's addresses.  Handles may be destroyed in
 // any order (garbage-collected callers: a state can go before its tape), so the count is only touched while the state is alive.
-void state_attach(moka_state *st);
-void state_detach(moka_state *st);
+// halo = true: the object is a moka_halo (counted in moka_state.halos too)
+void state_attach(moka_state *st, bool halo = false);
+void state_detach(moka_state *st, bool halo = false);
 
 #define HIPCHK(ctx, call)                                                                          \
     do {                                                                                           \

@@ -444,6 +444,15 @@ function set_viscosity_del2!(Prog::MProg, viscDel2::Float64)
     s === nothing && error("MokaHIP: the model is not on the device yet")
     check(ccall((:moka_set_viscosity_del2, lib), Cint, (Ptr{Cvoid}, Cdouble), s.handle, viscDel2), s.backend.ctx)
 end
+# Del4 (biharmonic) mixing, subtracted after everything else (include/moka_hip.h); meshScalingDel4: nothing or one factor >= 0
+# per edge, in the mesh's edge order; 0 = off
+function set_viscosity_del4!(Prog::MProg, viscDel4::Float64; meshScalingDel4::Union{Nothing,Vector{Float64}} = nothing)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    sc = meshScalingDel4 === nothing ? Ptr{Cdouble}(C_NULL) : pointer(meshScalingDel4)
+    GC.@preserve meshScalingDel4 check(ccall((:moka_set_viscosity_del4, lib), Cint, (Ptr{Cvoid}, Cdouble, Ptr{Cdouble}),
+                                             s.handle, viscDel4, sc), s.backend.ctx)
+end
 
 # The opt-in 13-stream form of the RK4 step (moka_set_tuning key 7; include/moka_hip.h): the same Runge-Kutta step with another
 # round-off than time_integration.jl:134-135's running sum (<= 1e-12 relative per step), 12 % fewer bytes.  Process-wide;

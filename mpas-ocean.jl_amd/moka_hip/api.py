@@ -572,14 +572,25 @@ def ocn_init_from_arrays(mesh_data, ssh, normalVelocity, layerThickness, resting
     return Setup, Diag, Tend, Prog
 
 
-def set_nonlinear(Prog: "PrognosticVars", on: bool = True, visc_del2: float = 0.0):
+def set_nonlinear(Prog: "PrognosticVars", on: bool = True, visc_del2: float = 0.0, visc_del4: float = 0.0,
+                  mesh_scaling_del4=None):
     """Switch the optional nonlinear terms (potential-vorticity Coriolis, kinetic-energy gradient) of this model's
     tendencies / RK4 steps on or off.  An extension: the reference has only the linear terms; default off.
-    `visc_del2` != 0 adds Del2 momentum mixing (the reference's uncalled sketch, horizontal_momentum_mixing.jl:53-80)."""
+    `visc_del2` != 0 adds Del2 momentum mixing (the reference's uncalled sketch, horizontal_momentum_mixing.jl:53-80).
+    `visc_del4` != 0 adds Del4 (biharmonic) mixing, subtracted last (moka_set_viscosity_del4); `mesh_scaling_del4`: None or one
+    factor >= 0 per edge, in the mesh's edge order."""
     L.check(L.lib().moka_set_nonlinear(Prog._state._h, 1 if on else 0), Prog._state.mesh.backend._h)
     Prog._state.nonlinear = bool(on)
     if on:
         L.check(L.lib().moka_set_viscosity_del2(Prog._state._h, float(visc_del2)), Prog._state.mesh.backend._h)
+        sc = None
+        if mesh_scaling_del4 is not None:
+            sc = np.ascontiguousarray(mesh_scaling_del4, dtype=np.float64).reshape(-1)
+            nE = Prog._state.mesh.HorzMesh.data.nEdges
+            if sc.size != nE:
+                raise ValueError(f"mesh_scaling_del4: {sc.size} values for {nE} edges")
+        L.check(L.lib().moka_set_viscosity_del4(Prog._state._h, float(visc_del4), None if sc is None else sc.ctypes.data),
+                Prog._state.mesh.backend._h)
 
 
 # ---------------------------------------------------------------------------------------------

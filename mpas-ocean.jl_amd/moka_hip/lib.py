@@ -92,7 +92,7 @@ EXPORTS = [
     "moka_tape_record_fe", "moka_tape_commit_fe", "moka_adjoint_fe_step_fields", "moka_adjoint_fe_step",
     "moka_halo_export", "moka_halo_connect", "moka_halo_push_begin", "moka_halo_push_signal", "moka_halo_push_wait",
     "moka_rk4_dist_stage_launch", "moka_rk4_dist_step", "moka_fe_dist_launch", "moka_fe_dist_end", "moka_fe_dist_step",
-    "moka_set_nonlinear", "moka_last_fe_path", "moka_set_viscosity_del2", "moka_tape_create", "moka_tape_destroy", "moka_step_fe_taped", "moka_step_rk4_taped", "moka_adjoint_seed_sum_sq_ssh", "moka_adjoint_sweep",
+    "moka_set_nonlinear", "moka_last_fe_path", "moka_set_viscosity_del2", "moka_set_viscosity_del4", "moka_state_del4_path", "moka_tape_create", "moka_tape_destroy", "moka_step_fe_taped", "moka_step_rk4_taped", "moka_adjoint_seed_sum_sq_ssh", "moka_adjoint_sweep",
     "moka_adjoint_download",
     "moka_mark", "moka_marks_reset", "moka_marks_read", "moka_bw_probe", "moka_bw_probe_streams", "moka_bw_probe_reread", "moka_bw_probe_gather_big", "moka_ctx_pci_bus_id", "moka_halo_set_acquire", "moka_set_tuning", "moka_get_tuning", "moka_rk4_dist_parts_available", "moka_adjoint_rk4_stage_part", "moka_adjoint_rk4_parts_available", "moka_adjoint_rk4_stage_out_fields",
     "moka_gradient_on_edge_vjp", "moka_gradient_on_edge_jvp", "moka_divergence_on_cell_vjp", "moka_divergence_on_cell_jvp",
@@ -233,6 +233,8 @@ def lib():
     L.moka_last_fe_path.argtypes = [vp]
     L.moka_fe_lazy_pending.argtypes = [vp]
     L.moka_set_viscosity_del2.argtypes = [vp, C.c_double]
+    L.moka_set_viscosity_del4.argtypes = [vp, C.c_double, vp]
+    L.moka_state_del4_path.argtypes = [vp]
     L.moka_tape_create.argtypes = [vp, C.c_int64, C.POINTER(vp)]
     L.moka_tape_destroy.argtypes = [vp]
     L.moka_tape_destroy.restype = None
