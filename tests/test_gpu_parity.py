@@ -1072,7 +1072,7 @@ def test_driver_in_the_reference_constructor_order(tmp_path):
 @pytest.mark.parametrize("meshname,K,flags,nsteps", [("igw200", 1, 7, 12), ("igw200", 1, 0, 12), ("ico16", 1, 7, 6), ("ico16", 3, 3, 5),
                                                        ("ico16", 60, 0, 3), ("ico12f", 5, 1, 4), ("ico16", 70, 3, 2),
                                                        ("ico16", 60, 3, 3), ("ico12f", 40, 3, 3), ("ico16", 34, 1, 3)])
-def test_fe_adjoint_bitwise(backend, meshname, K, flags, nsteps):
+def test_fe_adjoint_bitwise(backend, request, meshname, K, flags, nsteps):
     mesh = get_mesh(meshname)
     if meshname == "igw200":
         ssh, u, h, rest = mg.igw_initial_state(mesh)
@@ -1082,6 +1082,7 @@ def test_fe_adjoint_bitwise(backend, meshname, K, flags, nsteps):
         ssh, u, h, rest = random_state(mesh, K, 31 + K)
         dtv = 20.0
     Setup, Diag, Tend, Prog = mk.ocn_init_from_arrays(mesh, ssh, u, h, rest, CONFIG, backend, multilayer=True)
+    request.addfinalizer(lambda: (Prog._state.close(), Setup.mesh.close()))   # also when an assertion fails (the state takes its tapes along)
     tape = mk.AdjointTape(Prog, nsteps)
     om = orc.OracleMesh(mesh, K, resting_thickness_sum=rest.sum(1), max_level_edge_top=K)
     st = orc.OracleState(om, ssh, u, h)
@@ -1171,7 +1172,7 @@ def test_adjoint_refuses_what_it_does_not_cover(backend):
 
 @pytest.mark.parametrize("meshname,K,nsteps", [("igw200", 1, 6), ("ico16", 3, 4), ("ico16", 60, 2), ("ico12f", 5, 3), ("ico16", 70, 2),
                                                  ("ico12f", 34, 2), ("ico16", 64, 2)])
-def test_rk4_adjoint_bitwise(backend, meshname, K, nsteps):
+def test_rk4_adjoint_bitwise(backend, request, meshname, K, nsteps):
     mesh = get_mesh(meshname)
     if meshname == "igw200":
         ssh, u, h, rest = mg.igw_initial_state(mesh)
@@ -1181,6 +1182,7 @@ def test_rk4_adjoint_bitwise(backend, meshname, K, nsteps):
         ssh, u, h, rest = random_state(mesh, K, 41 + K)
         dtv = 20.0
     Setup, Diag, Tend, Prog = mk.ocn_init_from_arrays(mesh, ssh, u, h, rest, CONFIG, backend, multilayer=True)
+    request.addfinalizer(lambda: (Prog._state.close(), Setup.mesh.close()))   # also when an assertion fails (the state takes its tapes along)
     tape = mk.AdjointTape(Prog, nsteps)
     om = orc.OracleMesh(mesh, K, resting_thickness_sum=rest.sum(1), max_level_edge_top=K)
     st = orc.OracleState(om, ssh, u, h)

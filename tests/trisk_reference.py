@@ -39,7 +39,8 @@ rounding per +, -, *, /, including forming 1/dc, 1/A; the factors 0.5 / 0.25 and
 The reference's own error (2^-64 relative per operation, on the same magnitudes) is below 2^-7 of the bound.  Storage in fp32
 adds half an ulp of fp32 on top (see `within`).
 
-`rk4` is the reference's RK4 step with the running sum (time_integration.jl:61-148: Provis = Curr + a_s t, New += b_s t)."""
+`rk4` is the reference's RK4 step with the running sum (time_integration.jl:61-148: Provis = Curr + a_s t, New += b_s t),
+`forward_euler` its Forward-Euler step (time_integration.jl:160-190) on the state (u, h, ssh, layerThicknessEdge)."""
 from __future__ import annotations
 
 import numpy as np
@@ -288,6 +289,26 @@ def rk4(mesh, u, h, rest_sum, mlt, dt, nsteps=1, *, nonlinear, visc_del2=0.0, vi
             nu, nh = nu + b[s] * tu, nh + b[s] * th
         cu, ch = nu, nh
     return cu, ch, ch.sum(axis=1) - _ld(rest_sum, (g.nC,))
+
+
+def forward_euler(mesh, u, h, ssh, rest_sum, mlt, dt, nsteps=1, *, hE=None, stale=False):
+    """nsteps Forward-Euler steps of the linear form in long double (time_integration.jl:160-190): the pressure gradient reads the
+    carried ssh, the flux the carried layerThicknessEdge hE when `stale` (else interp(h)); u' = u + dt tendU, h' = h + dt tendH,
+    ssh' = sum_k h' - rest, hE' = interp(h).  Returns (u, h, ssh, hE)."""
+    g = geometry(mesh)
+    u, h = _ld(u, (g.nE, -1)), _ld(h, (g.nC, -1))
+    K = u.shape[1]
+    ssh, rest = _ld(ssh, (g.nC,)), _ld(rest_sum, (g.nC,))
+    hE = (h[g.c1] + h[g.c2]) / 2 if hE is None else _ld(hE, (g.nE, K))
+    act = active(g, mlt, K)
+    dt = LD(dt)
+    for _ in range(nsteps):
+        hI = (h[g.c1] + h[g.c2]) / 2
+        tU = terms(mesh, u, h, rest, mlt, nonlinear=False, abs=False, ssh=ssh)["U"][0]
+        tH = -divergence(g, np.where(act, u * (hE if stale else hI), 0))[0]
+        u, h, hE = u + dt * tU, h + dt * tH, hI
+        ssh = h.sum(axis=1) - rest
+    return u, h, ssh, hE
 
 
 # ---- the per-element check ------------------------------------------------------------------------------------------------------
