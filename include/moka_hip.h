@@ -432,7 +432,10 @@ int moka_set_kernel_variant(moka_ctx *ctx, int variant);
  * few units in the last place of the state per step; oracle twin oracle_step_rk4_s13, tests/test_oracle_igw.py holds the
  * tolerance against the reference form).  With the nonlinear terms on: the same where the stage launch is the default patch
  * kernel (even 34 <= nVertLevels <= 64; twin oracle_step_rk4_nonlinear_s13).  Distributed, taped and fp32-storage steps keep
- * the reference's form.  moka_state_rk4_streams tells which form the next moka_step_rk4 of a state takes. */
+ * the reference's form.  moka_state_rk4_streams tells which form the next moka_step_rk4 of a state takes.
+ * Accepted values (anything else, and a key outside 1-9, is MOKA_ERR_ARG and changes nothing): key 1 a mask of modes 0-6, 10 and
+ * 11; key 8 a mask of modes 0-3 and 7-9 plus bit 16 (test hook: small launches too); key 5 0-3; key 6 >= 0; keys 2, 3, 4, 7 and
+ * 9 0 or 1.  moka_get_tuning returns the value last set (or the default). */
 int moka_set_tuning(int key, int value);
 int moka_get_tuning(int key, int *value);
 /* 13 = the next moka_step_rk4 / moka_run of this state runs in the 13-stream form (key 7 set and the state qualifies), 16 = the

@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,11 +20,38 @@
 
 #include "state.hpp"
 
-namespace moka { void fill_mesh_info(const Plan &p, moka_mesh_info *info); }
+namespace moka {
+
+void fill_mesh_info(const Plan &p, moka_mesh_info *info);
+
+// Process-wide launch-shape switches (moka_set_tuning / moka_get_tuning; include/moka_hip.h lists the keys, kernels.hpp names them):
+// the default, and either a bit mask whose bits each name kernel instances (mask != 0) or the largest value accepted (from 0).
+struct TuningEntry {
+    int mask, max;
+    std::atomic<int> value;
+    TuningEntry(int def, int m, int x) : mask(m), max(x), value(def) {}
+    bool accepts(int v) const { return mask ? (v & ~mask) == 0 : v >= 0 && v <= max; }
+};
+static TuningEntry g_tuning[] = {
+    {0, 0, -1},                                              // (no key 0)
+    {1 << 0, 0x7f | 1 << 10 | 1 << 11, 0},                   // 1 TUNE_F32_WIDE: fp32 modes 0-6, lean 10 / 11 (launch_rec2c_f32)
+    {1, 0, 1},                                               // 2 TUNE_FE_PREV
+    {1, 0, 1},                                               // 3 TUNE_CURL_FUSED
+    {1, 0, 1},                                               // 4 TUNE_FE_LEAN
+    {0, 0, 3},                                               // 5 TUNE_NL_SHAPE: shapes 0-3 (nl_stage_kernel)
+    {0, 0, INT_MAX},                                         // 6 TUNE_NL_CAP: vertex rows, 0 = no limit
+    {0, 0, 1},                                               // 7 TUNE_RK13
+    {1 << 0 | 1 << 1 | 1 << 7, 0xf | 7 << 7 | 1 << 16, 0},   // 8 TUNE_PAIR: pair instances 0-3, 7-9; bit 16 test hook (launch_rec2c_pair)
+    {1, 0, 1},                                               // 9 TUNE_FE_LEAN_INST
+};
+constexpr int N_TUNING = sizeof(g_tuning) / sizeof(g_tuning[0]);
+
+int tuning(TuningKey key) { return g_tuning[key].value.load(); }
+
+}  // namespace moka
 
 namespace mk {
 
-static std::atomic<bool> g_rk13{false};      // moka_set_tuning key 7: RK4 steps in the 13-stream form where mk::rk13_usable
 static std::mutex g_liveMutex;
 static std::unordered_set<const moka_state *> g_liveStates;
 void state_attach(moka_state *st, bool halo)
@@ -250,7 +278,7 @@ hipError_t run_stage(moka_state *st, const StageArgs &g_in, int pBegin, int pCou
         // One extra, non-adjacent patch in the same launch: only the default kernels can carry it.  Anything else
         // (explicit variants, fallbacks for other K, the nonlinear path) gets a launch of its own for it.
         hipError_t e = hipErrorNotSupported;
-        if (pCount > 0 && !st->nonlinear && (st->f32 || ((st->ctx->variant == 0 || st->ctx->variant == 11) && m->lpc == 64 && m->colOk))) {
+        if (pCount > 0 && !st->nonlinear && (st->f32 || default_stage_kernels(st))) {
             const moka::Plan &p = m->plan;
             dev.patchBegin = pBegin; dev.nPatches = pCount; dev.tailPatch = tail;
             int mE = p.patchEdgeStart[tail + 1] - p.patchEdgeStart[tail], mC = p.patchCellStart[tail + 1] - p.patchCellStart[tail];
@@ -288,8 +316,7 @@ hipError_t run_stage(moka_state *st, const StageArgs &g_in, int pBegin, int pCou
         // (whole mesh: the stencil of the edge pass reaches two cells deep), then the generic stage kernel's nonlinear twin
         const bool del2 = st->viscDel2 != 0.0, del4 = st->viscDel4 != 0.0;
         NlArgs nl{st->nlQv, st->nlQe, st->nlKe, del2 ? st->nlZv : nullptr, del2 ? st->nlDiv : nullptr, st->viscDel2};
-        // kernel variants 4 / 3 select the plainer forms of the nonlinear kernels too (tests run every form against the oracle)
-        const int form = st->ctx->variant == 4 ? 1 : st->ctx->variant == 3 ? 3 : 0;
+        const int form = nl_form(st->ctx);          // tests run every form against the oracle
         // a patch range (partitioned meshes: moka_rk4_dist_stage) is served by the patch forms only
         if (pCount >= 0 && !nl_patch_forms(dev, m->lpc, form)) return hipErrorNotSupported;
         // Del4: whole-mesh stages only (its stencil reaches three cell rings; moka_halo_create refuses such states)
@@ -313,8 +340,8 @@ hipError_t run_stage(moka_state *st, const StageArgs &g_in, int pBegin, int pCou
     if (st->f32) {   // the one fp32-storage kernel (checked at state creation against the patches that are ever launched)
         if (pCount < 0 && m->plan.nPatchesLaunch < m->plan.nPatches) {
             // whole-mesh launch on a partitioned mesh: the halo-only patches are skipped (their rows arrive by exchange)
-            dev.nPatches = m->plan.nPatchesLaunch;
-            dev.maxOwnE = std::max(m->plan.maxOwnELaunch, 1); dev.maxOwnC = std::max(m->plan.maxOwnCLaunch, 1);
+            dev = launch_bounds(m);
+            dev.tailPatch = -1; dev.nPatches = m->plan.nPatchesLaunch;
         }
         return launch_stage_rec2c_f32(dev, g, s);
     }
@@ -323,7 +350,7 @@ hipError_t run_stage(moka_state *st, const StageArgs &g_in, int pBegin, int pCou
     // else the generic index kernel.  11 rec2c, 4 column, 3 generic.  (The other execution shapes measured in rounds 1-3 -- pipelined
     // and 16-byte-lane column kernels, LDS-tiled and LDS-DMA forms, persistent double-buffered tiles -- lost and are gone; their
     // numbers are in profiles/r01_variants.txt ... r03_variants.txt.)
-    if ((v == 0 || v == 11) && m->lpc == 64 && m->colOk) {   // default: 16-byte lanes + own-edge u rows cached in LDS
+    if (default_stage_kernels(st)) {                          // default: 16-byte lanes + own-edge u rows cached in LDS
         hipError_t e = launch_stage_rec2c(dev, g, s);
         if (e != hipErrorNotSupported) return e;
     }
@@ -338,17 +365,15 @@ bool fe_stage_path(const moka_state *st, int flags)
     const moka_mesh *mm = st->mesh;
     if (flags & MOKA_FE_LEVEL1_ONLY) return false;
     if (st->f32) return true;                                  // checked when the state was created
-    MeshDev dev = mm->dev;
-    dev.maxOwnE = std::max(mm->plan.maxOwnELaunch, 1); dev.maxOwnC = std::max(mm->plan.maxOwnCLaunch, 1);
-    return (st->ctx->variant == 0 || st->ctx->variant == 11) && mm->lpc == 64 && mm->colOk && rec2c_supported(dev);
+    return default_stage_kernels(st) && rec2c_supported(launch_bounds(mm));
 }
 
 // A LEAN step stores the new level and relativeVorticity only (moka_state.feLazy).  It needs the stage-kernel path, the spare
 // level set, and -- with the reference's stale flux thickness -- that thickness to be derivable from the previous level.
 bool fe_lean(const moka_state *st, int flags)
 {
-    return moka::fe_lean_enabled() && !st->feForceEager && fe_stage_path(st, flags) && st->spare.ssh &&
-           (!(flags & MOKA_FE_STALE_HEDGE) || (st->hEdgePrev && moka::fe_prev_mode()));
+    return tuning(TUNE_FE_LEAN) && !st->feForceEager && fe_stage_path(st, flags) && st->spare.ssh &&
+           (!(flags & MOKA_FE_STALE_HEDGE) || (st->hEdgePrev && tuning(TUNE_FE_PREV)));
 }
 
 // What a Forward-Euler step does about lazily pending arrays before its first launch.  A lean step reads none of them and
@@ -390,7 +415,7 @@ StageArgs fe_stage_args(moka_state *st, const FeArgs &a, int flags)
     s.pu_out = a.u_new; s.ph_out = a.h_new; s.ssh_out = a.ssh_new;
     s.a = a.dt;
     const bool stale = flags & MOKA_FE_STALE_HEDGE;
-    const bool prev = stale && st->hEdgePrev && st->spare.ssh && a.h_new != st->lev[0].h && moka::fe_prev_mode();
+    const bool prev = stale && st->hEdgePrev && st->spare.ssh && a.h_new != st->lev[0].h && tuning(TUNE_FE_PREV);
     s.hEdgeOld = stale && !prev ? a.hEdgeOld : nullptr;
     s.hPrev = prev ? st->lev[0].h : nullptr;
     s.feMode = prev ? 6 : stale ? 4 : 5;
@@ -400,11 +425,7 @@ StageArgs fe_stage_args(moka_state *st, const FeArgs &a, int flags)
         s.hEdgeNew = a.hEdgeNew; s.F = a.F; s.div = a.div;
     }
     // relativeVorticity by the same launch (the vertices of the launched patches) where the stage kernels can carry it
-    {
-        MeshDev dev = st->mesh->dev;
-        dev.maxOwnE = std::max(st->mesh->plan.maxOwnELaunch, 1); dev.maxOwnC = std::max(st->mesh->plan.maxOwnCLaunch, 1);
-        if (moka::stage_curl_fits(dev, st->f32)) { s.vort = a.vort; s.accumVort = (flags & MOKA_FE_ACCUM_VORT) ? 1 : 0; }
-    }
+    if (stage_curl_fits(launch_bounds(st->mesh), st->f32)) { s.vort = a.vort; s.accumVort = (flags & MOKA_FE_ACCUM_VORT) ? 1 : 0; }
     return s;
 }
 
@@ -421,13 +442,12 @@ static int materialize_fe(moka_state *st)
     g.tendU = st->tendU; g.tendH = st->tendH; g.F = st->F; g.div = st->div;
     g.hEdgeNew = st->hEdge[0];                                  // mode 6 reads no stored layerThicknessEdge: written in place
     g.areaCell = mm->dev.areaCell;
-    MeshDev dev = mm->dev;
+    MeshDev dev = launch_bounds(mm);
     dev.tailPatch = -1;
     dev.patchBegin = 0; dev.nPatches = mm->plan.nPatchesLaunch;
     if (st->feLazyCount >= 0) {                                 // a distributed step with a direct halo: the interior patches only
         dev.patchBegin = st->feLazyBegin; dev.nPatches = st->feLazyCount;
     }
-    dev.maxOwnE = std::max(mm->plan.maxOwnELaunch, 1); dev.maxOwnC = std::max(mm->plan.maxOwnCLaunch, 1);
     if (dev.nPatches > 0)
         HIPCHK(st->ctx, st->f32 ? launch_stage_rec2c_f32(dev, g, st->ctx->stream) : launch_stage_rec2c(dev, g, st->ctx->stream));
     st->feLazy = false;
@@ -746,51 +766,20 @@ int moka_bw_probe_gather_big(moka_ctx *ctx, int64_t bytes, int iters, double *gb
     return MOKA_OK;
 }
 
-// Process-wide launch-shape switches for A/B measurements (results are identical for every setting):
-//   key 1: bit mask of the modes of the fp32-storage stage kernel that run as 512-thread workgroups bounded to 128 registers
-//          (default: mode 0; see kernels.hip, g_f32WideModes)
-//   key 2: 0 = Forward-Euler steps always gather the stored layerThicknessEdge (stage-kernel mode 4), 1 (default) = they form
-//          it from the previous level's layerThickness whenever that is the same thing (mode 6)
-//   key 4: 0 = every Forward-Euler step stores all of its DiagnosticVars / TendencyVars; 1 (default) = lean steps where possible
-//          (new level and relativeVorticity stored, the rest produced on first read: moka_state.feLazy)
-//   key 5: launch shape of the nonlinear stage kernel's patch form (nonlinear.hip, g_nlShape): 0 (default) vertex rows in LDS, three
-//          512-thread workgroups per CU; 1 = round 2's edge rows in LDS, two workgroups; 2 / 3 = other shapes of the vertex-row form
-//   key 6: test hook, upper limit of the vertex rows that form keeps in LDS (0 = none)
-//   key 3: 0 = the relativeVorticity pass of a Forward-Euler step always gets a launch of its own, 1 (default) = it rides in the
-//          stage-kernel launches where they can carry it
-//   key 8: bit mask of the modes of the Float64 stage kernel whose large launches take TWO consecutive patches per 512-thread workgroup
-//          (default: 0, 1 and the 13-stream 7; kernels.hip, launch_stage_rec2c)
-//   key 9: 1 (default) = lean Forward-Euler launches run the kernels' lean instances (modes 10 / 11: optional outputs compiled out),
-//          0 = the general Forward-Euler instances (outputs tested at run time)
-//   key 7: NOT result-neutral, opt-in (default 0): moka_step_rk4 / moka_run of Float64 states on whole meshes in the 13-stream form
-//          (mk::rk13_usable; New formed in stage 4 from the provisional states instead of accumulated through the stages)
 int moka_set_tuning(int key, int value)
 {
-    if (key == 1) { moka::set_f32_wide_modes(value); return MOKA_OK; }
-    if (key == 2) { moka::set_fe_prev_mode(value); return MOKA_OK; }
-    if (key == 9) { moka::set_fe_lean_instances(value); return MOKA_OK; }
-    if (key == 3) { moka::set_curl_fused(value); return MOKA_OK; }
-    if (key == 4) { moka::set_fe_lean(value); return MOKA_OK; }
-    if (key == 5) { moka::set_nl_shape(value); return MOKA_OK; }
-    if (key == 6) { moka::set_nl_cap_limit(value); return MOKA_OK; }
-    if (key == 7) { g_rk13.store(value != 0); return MOKA_OK; }
-    if (key == 8) { moka::set_pair_modes(value); return MOKA_OK; }
-    return fail(nullptr, MOKA_ERR_ARG, "unknown tuning key");
+    if (key < 1 || key >= N_TUNING) return fail(nullptr, MOKA_ERR_ARG, "unknown tuning key");
+    if (!g_tuning[key].accepts(value)) return fail(nullptr, MOKA_ERR_ARG, "tuning key " + std::to_string(key) + ": value names no kernel instance");
+    g_tuning[key].value.store(value);
+    return MOKA_OK;
 }
 
 int moka_get_tuning(int key, int *value)
 {
     if (!value) return fail(nullptr, MOKA_ERR_ARG, "value is NULL");
-    if (key == 1) { *value = moka::f32_wide_modes(); return MOKA_OK; }
-    if (key == 2) { *value = moka::fe_prev_mode(); return MOKA_OK; }
-    if (key == 9) { *value = moka::fe_lean_instances(); return MOKA_OK; }
-    if (key == 3) { *value = moka::curl_fused(); return MOKA_OK; }
-    if (key == 4) { *value = moka::fe_lean_enabled(); return MOKA_OK; }
-    if (key == 5) { *value = moka::nl_shape(); return MOKA_OK; }
-    if (key == 6) { *value = moka::nl_cap_limit(); return MOKA_OK; }
-    if (key == 7) { *value = g_rk13.load() ? 1 : 0; return MOKA_OK; }
-    if (key == 8) { *value = moka::pair_modes(); return MOKA_OK; }
-    return fail(nullptr, MOKA_ERR_ARG, "unknown tuning key");
+    if (key < 1 || key >= N_TUNING) return fail(nullptr, MOKA_ERR_ARG, "unknown tuning key");
+    *value = g_tuning[key].value.load();
+    return MOKA_OK;
 }
 
 int moka_kernel_variant_available(int variant)
@@ -1092,8 +1081,7 @@ int moka_state_create(moka_ctx *ctx, moka_mesh *mesh, moka_state **out)
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t nEK = (size_t)p.K * p.nE, nCK = (size_t)p.K * p.nC, nVK = (size_t)p.K * p.nV;
     st->f32 = p.stateBytes == 4;
-    MeshDev launchDev = mesh->dev;        // what the stage launches will see: maxima over the patches that are ever computed
-    launchDev.maxOwnE = std::max(p.maxOwnELaunch, 1); launchDev.maxOwnC = std::max(p.maxOwnCLaunch, 1);
+    const MeshDev launchDev = launch_bounds(mesh);
     if (st->f32 && !stage_f32_supported(launchDev)) {
         delete st;
         return fail(ctx, MOKA_ERR_UNSUPPORTED,
@@ -1278,9 +1266,8 @@ int moka_step_fe(moka_state *st, double dt, int flags)
     bool fast = false, prevMode = false;
     if (stagePath) {
         StageArgs g = fe_stage_args(st, a, flags);
-        MeshDev dev = mm->dev;
+        MeshDev dev = launch_bounds(mm);
         dev.tailPatch = -1;
-        dev.maxOwnE = std::max(mm->plan.maxOwnELaunch, 1); dev.maxOwnC = std::max(mm->plan.maxOwnCLaunch, 1);
         auto launch = [&]() { return st->f32 ? launch_stage_rec2c_f32(dev, g, st->ctx->stream) : launch_stage_rec2c(dev, g, st->ctx->stream); };
         hipError_t e = launch();
         if (e == hipErrorNotSupported && g.vort) {             // vertex records do not fit beside the rows after all: own launch
@@ -1385,15 +1372,13 @@ void rk4_end(moka_state *st)
 // (with the nonlinear terms: through k_stage_nl5, twin oracle_step_rk4_nonlinear_s13).
 bool rk13_usable(const moka_state *st)
 {
-    if (!g_rk13.load() || st->f32) return false;
+    if (!tuning(TUNE_RK13) || st->f32) return false;
     if (st->nonlinear && st->viscDel4 != 0.0) return false;     // Del4: the reference's running sum (no 13-stream twin)
     const moka_mesh *mm = st->mesh;
     if (mm->plan.nPatchesLaunch != mm->plan.nPatches) return false;
     if (st->nonlinear)             // nonlinear terms: k_stage_nl5 carries the form (StageArgs.rkMode 9), the plainer kernels do not
-        return nl_stage_is_nl5(mm->dev, mm->lpc, st->ctx->variant == 4 ? 1 : st->ctx->variant == 3 ? 3 : 0);
-    MeshDev dev = mm->dev;
-    dev.maxOwnE = std::max(mm->plan.maxOwnELaunch, 1); dev.maxOwnC = std::max(mm->plan.maxOwnCLaunch, 1);
-    return (st->ctx->variant == 0 || st->ctx->variant == 11) && mm->lpc == 64 && mm->colOk && rec2c_supported(dev);
+        return nl_stage_is_nl5(mm->dev, mm->lpc, mm->plan.ldsOk, nl_form(st->ctx));
+    return default_stage_kernels(st) && rec2c_supported(launch_bounds(mm));
 }
 
 StageArgs rk13_stage_args(moka_state *st, int s, double dt, const double *ssh0)

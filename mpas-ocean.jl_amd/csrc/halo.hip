@@ -945,8 +945,7 @@ int moka_rk4_dist_parts_available(const moka_halo *h)
     if (!h) return 0;
     const moka_state *st = h->st;
     if (!st->nonlinear) return 1;
-    const int form = st->ctx->variant == 4 ? 1 : st->ctx->variant == 3 ? 3 : 0;
-    return nl_patch_forms(st->mesh->dev, st->mesh->lpc, form) ? 1 : 0;
+    return nl_patch_forms(st->mesh->dev, st->mesh->lpc, nl_form(st->ctx)) ? 1 : 0;
 }
 
 // direct transport, the device-queue half of a stage: boundary patches, push (comm stream), interior patches
@@ -1030,11 +1029,8 @@ int moka_rk4_dist_step(moka_halo *h, double dt, moka_transport_fn transport, voi
 static bool fe_vort_fused(const moka_halo *h)
 {
     const moka_state *st = h->st;
-    const moka_mesh *mm = st->mesh;
-    MeshDev dev = mm->dev;
-    dev.maxOwnE = std::max(mm->plan.maxOwnELaunch, 1); dev.maxOwnC = std::max(mm->plan.maxOwnCLaunch, 1);   // bounds both ranges
-    if (st->f32) return stage_curl_fits(dev, true);
-    return (st->ctx->variant == 0 || st->ctx->variant == 11) && mm->lpc == 64 && mm->colOk && stage_curl_fits(dev, false);
+    const MeshDev dev = launch_bounds(st->mesh);           // bounds both ranges
+    return (st->f32 || default_stage_kernels(st)) && stage_curl_fits(dev, st->f32);
 }
 
 static int fe_dist_args(moka_state *st, double dt, int flags, StageArgs *g, FeArgs *a)
@@ -1111,7 +1107,7 @@ int moka_fe_dist_launch(moka_halo *h, double dt, int flags, int part)
         h->feStageKernel = true;
         return MOKA_OK;
     }
-    if ((c->variant == 0 || c->variant == 11) && mm->lpc == 64 && mm->colOk) e = launch_stage_rec2c(dev, g, c->stream);
+    if (default_stage_kernels(st)) e = launch_stage_rec2c(dev, g, c->stream);
     h->feStageKernel = e == hipSuccess;
     if (e == hipErrorNotSupported) {
         if (vortFused) return hfail(h, MOKA_ERR_UNSUPPORTED, "internal: the stage kernel refused a launch whose vertex pass it was to carry");

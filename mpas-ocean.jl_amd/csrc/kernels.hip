@@ -1,7 +1,7 @@
 // kernels.hip -- hand-written gfx950 (CDNA4, wave64) kernels of libmoka_hip: the DEFAULT fused tendency / RK-stage
 // kernels (k_stage_rec2c for Float64 states, k_stage_rec2c_f32 for fp32-storage states), the one-launch Forward-Euler
 // step (k_fe), the stand-alone operators and the utility kernels (ssh, permutations, halo maps).
-// The other execution shapes of the stage kernel live in stage_variants.hip, the optional nonlinear terms in
+// The other execution shapes of the stage kernel live in stage_fallback.hip, the optional nonlinear terms in
 // nonlinear.hip, reverse mode in adjoint.hip; shared device helpers in kernels_common.hpp.
 //
 // Layout.  Fields are (nVertLevels, n) with the level index fastest, exactly the reference layout
@@ -15,6 +15,10 @@
 // Arithmetic.  Compiled with -ffp-contract=off and written in the reference's operand order
 // (each expression cites the reference line), so results are bit-identical to the CPU oracle.
 // Memory-bound indirect stencil: no MFMA by design.
+#include <mutex>
+#include <set>
+#include <utility>
+
 #include "kernels_common.hpp"
 
 namespace moka {
@@ -1521,36 +1525,42 @@ static bool launch_rec2c(const ColMesh &m, const StageArgs &a, int mode, dim3 g,
     return launch_rec2c_nt<ME, ME2, BLOCK>(m, a, mode, g, lds, mE, mC, s);
 }
 
-// measurement: 0 = lean launches run the general Forward-Euler instances (outputs tested at run time) instead of modes 10 / 11
-static std::atomic<int> g_feLeanInst{1};
-void set_fe_lean_instances(int on) { g_feLeanInst.store(on); }
-int fe_lean_instances() { return g_feLeanInst.load(); }
+hipError_t raise_dyn_lds(std::initializer_list<const void *> fns, int bytes)
+{
+    static std::mutex mu;
+    static std::set<std::pair<int, const void *>> done;     // (device, kernel) raised there
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+    std::lock_guard<std::mutex> lk(mu);
+    for (const void *fn : fns) {
+        if (done.count({dev, fn})) continue;
+        if (hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); e != hipSuccess) return e;
+        done.insert({dev, fn});
+    }
+    return hipSuccess;
+}
 
 // the pair form (launch_stage_rec2c): 512-thread workgroups over two patches, whose records and rows need more than the default
-// 64 KB of dynamic LDS.  Default: the tendency launch (mode 0) and RK stage 1 (mode 1; 7 in the 13-stream form) -- measured on the
-// product mesh (P = 16, three interleaved rounds): tendency 1.188 -> 1.170 ms, stage 1 1.513 -> 1.479, stage 4 (mode 3) 1.443 ->
-// 1.461: mode 3 does not gain, stages 2 / 3 lose (profiles/r04_variants.txt section 8)
-static std::atomic<int> g_pairModes{(1 << 0) | (1 << 1) | (1 << 7)};
-void set_pair_modes(int mask) { g_pairModes.store(mask); }
-int pair_modes() { return g_pairModes.load(); }
-
+// 64 KB of dynamic LDS (raised once per device and mode).  Default modes (tuning key 8): the tendency launch (mode 0) and RK
+// stage 1 (mode 1; 7 in the 13-stream form) -- measured on the product mesh (P = 16, three interleaved rounds): tendency 1.188 ->
+// 1.170 ms, stage 1 1.513 -> 1.479, stage 4 (mode 3) 1.443 -> 1.461: mode 3 does not gain, stages 2 / 3 lose
+// (profiles/r04_variants.txt section 8).  hipErrorNotSupported: no pair instance of this mode.
 template <int ME, int ME2>
-static bool launch_rec2c_pair(const ColMesh &m, const StageArgs &a, int mode, dim3 g, size_t lds, int mE, int mC, hipStream_t s)
+static hipError_t launch_rec2c_pair(const ColMesh &m, const StageArgs &a, int mode, dim3 g, size_t lds, int mE, int mC, hipStream_t s)
 {
     const dim3 b(512);
-    // (once per device and mode, and never inside a stream capture: moka_run steps eagerly before it captures)
-    const bool raise = lds > 64 * 1024 && lds_attr_needed(22 + mode);
-#define PAIR_CASE(M)                                                                                                                      \
-    case M:                                                                                                                               \
-        if (raise)                                                                                                                        \
-            (void)hipFuncSetAttribute((const void *)k_stage_rec2c<ME, ME2, M, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        hipLaunchKernelGGL((k_stage_rec2c<ME, ME2, M, 512>), g, b, lds, s, m, a, mE, mC);                                                  \
-        return true;
+#define PAIR_CASE(M)                                                                                                   \
+    case M:                                                                                                            \
+        if (lds > 64 * 1024)                                                                                           \
+            if (hipError_t e = raise_dyn_lds({(const void *)k_stage_rec2c<ME, ME2, M, 512>}, 160 * 1024); e != hipSuccess) \
+                return e;                                                                                              \
+        hipLaunchKernelGGL((k_stage_rec2c<ME, ME2, M, 512>), g, b, lds, s, m, a, mE, mC);                               \
+        return hipGetLastError();
     switch (mode) {
         PAIR_CASE(0) PAIR_CASE(1) PAIR_CASE(2) PAIR_CASE(3) PAIR_CASE(7) PAIR_CASE(8) PAIR_CASE(9)
     }
 #undef PAIR_CASE
-    return false;
+    return hipErrorNotSupported;
 }
 
 size_t rec2c_lds_bytes(const MeshDev &md)
@@ -1561,14 +1571,9 @@ size_t rec2c_lds_bytes(const MeshDev &md)
 // the vertex records a Forward-Euler launch with the vertex pass stages behind the row cache: 3 coefficients + 4 offsets per vertex
 static inline size_t vert_lds_bytes(const MeshDev &md) { return (size_t)md.maxOwnV * (3 * 8 + 4 * 4) + 16; }
 
-// measurement: 0 = the vertex pass always gets a launch of its own (k_curl3)
-static std::atomic<int> g_curlFused{1};
-void set_curl_fused(int on) { g_curlFused.store(on); }
-int curl_fused() { return g_curlFused.load(); }
-
 bool stage_curl_fused(const MeshDev &md)
 {
-    return g_curlFused.load() && md.vRec != nullptr && md.VD == 3 && md.patchVertStart != nullptr && md.maxOwnV > 0;
+    return tuning(TUNE_CURL_FUSED) && md.vRec != nullptr && md.VD == 3 && md.patchVertStart != nullptr && md.maxOwnV > 0;
 }
 
 // ... and do its vertex records fit beside the records and own rows of patches as large as md.maxOwnE / md.maxOwnC
@@ -1601,7 +1606,7 @@ hipError_t launch_stage_rec2c(const MeshDev &md, const StageArgs &a, hipStream_t
     const ColMesh m = col_mesh(md, nLaunch);
     int mode = colp_mode(a);
     if (a.vort && (mode < 4 || !stage_curl_fused(md))) return hipErrorNotSupported;
-    if (fe_lean_instances() && colp_lean(a, mode)) mode += 5;        // a lean Forward-Euler launch: modes 10 / 11
+    if (tuning(TUNE_FE_LEAN_INST) && colp_lean(a, mode)) mode += 5;        // a lean Forward-Euler launch: modes 10 / 11
     const size_t lds = rec2c_lds_bytes(md) + (a.vort ? vert_lds_bytes(md) : 0);
     if (mode < 0 || md.K > 64 || (md.K & 1) || lds > 64 * 1024 || md.maxOwnC < 1 || md.maxOwnE < 1) return hipErrorNotSupported;
     // Two consecutive patches per 512-thread workgroup for the LIGHT modes (round 4; moka_set_tuning key 8).  Consecutive patches of
@@ -1611,7 +1616,8 @@ hipError_t launch_stage_rec2c(const MeshDev &md, const StageArgs &a, hipStream_t
     // entity) lose: those keep one patch per 256-thread workgroup.  Same entities, same arithmetic, same bits.  Only launches large enough to fill the chip either way,
     // without a tail patch, and when two such workgroups fit a CU's LDS (two per CU = the 16 waves of four small workgroups).
     // (bit 16 of the mask is a test hook: small launches too)
-    if (((pair_modes() >> mode) & 1) && md.tailPatch < 0 && (md.nPatches >= 4096 || ((pair_modes() >> 16) & 1)) && md.nPatches >= 2 &&
+    const int pair = tuning(TUNE_PAIR);
+    if (((pair >> mode) & 1) && md.tailPatch < 0 && (md.nPatches >= 4096 || ((pair >> 16) & 1)) && md.nPatches >= 2 &&
         md.ME == 6 && md.ME2 == 10) {
         MeshDev two = md;
         two.maxOwnE = 2 * md.maxOwnE; two.maxOwnC = 2 * md.maxOwnC;
@@ -1620,7 +1626,8 @@ hipError_t launch_stage_rec2c(const MeshDev &md, const StageArgs &a, hipStream_t
             const int nPair = (md.nPatches + 1) / 2;
             ColMesh mp = col_mesh(md, nPair);
             mp.pairEnd = md.patchBegin + md.nPatches;
-            if (launch_rec2c_pair<6, 10>(mp, a, mode, dim3(8 * ((nPair + 7) / 8)), lds2, two.maxOwnE, two.maxOwnC, s)) return hipGetLastError();
+            const hipError_t e = launch_rec2c_pair<6, 10>(mp, a, mode, dim3(8 * ((nPair + 7) / 8)), lds2, two.maxOwnE, two.maxOwnC, s);
+            if (e != hipErrorNotSupported) return e;
         }
     }
     bool ok = false;
@@ -1630,59 +1637,46 @@ hipError_t launch_stage_rec2c(const MeshDev &md, const StageArgs &a, hipStream_t
     return ok ? hipGetLastError() : hipErrorNotSupported;
 }
 
-// Which modes of the fp32-storage kernel run as 512-thread workgroups bounded to 128 registers (two per CU = 4 waves per
-// SIMD instead of three 4-wave workgroups = 3): bit m = mode m.  Modes 0 and 1 (no Curr / New rows in flight) fit 128
-// registers without spills, the others do not (tools/kernel_regs.py).  Measured on config 5 (profiles/r03_variants.txt):
-// mode 0, the tendency launch, 3.81 -> 3.71 ms; mode 1, RK stage 1, 4.81 -> 5.07 ms (its two result streams per entity
-// queue up behind twice as many waves) -- so mode 0 only.  moka_set_tuning(1, mask) changes it for measurements.
-static std::atomic<int> g_f32WideModes{1 << 0};
-void set_f32_wide_modes(int mask) { g_f32WideModes.store(mask); }
-int f32_wide_modes() { return g_f32WideModes.load(); }
-// measurement: 0 = every Forward-Euler step stores all of its DiagnosticVars / TendencyVars (no lean steps)
-static std::atomic<int> g_feLean{1};
-void set_fe_lean(int on) { g_feLean.store(on); }
-int fe_lean_enabled() { return g_feLean.load(); }
-// measurement: 0 keeps Forward-Euler steps on the gathered layerThicknessEdge (mode 4) even when mode 6 applies
-static std::atomic<int> g_fePrevMode{1};
-void set_fe_prev_mode(int on) { g_fePrevMode.store(on); }
-int fe_prev_mode() { return g_fePrevMode.load(); }
-
 template <int ME, int ME2, int NT, int WPE>
-static bool launch_rec2c_f32_nt(const ColMesh &m, const StageArgs &a, int mode, dim3 g, size_t lds, int mE, int mC, hipStream_t s)
+static hipError_t launch_rec2c_f32_nt(const ColMesh &m, const StageArgs &a, int mode, dim3 g, size_t lds, int mE, int mC, hipStream_t s)
 {
     // a launch that carries a halo-straddling patch of a partitioned mesh (up to 6 own edges per cell) may need more than
-    // the default 64 KB of dynamic LDS; such launches are small (the boundary group), occupancy does not matter there
-    if (lds > 64 * 1024 && lds_attr_needed((ME == 6 ? (ME2 == 10 ? 0 : 1) : 2) * 2 + (NT == 512 ? 1 : 0))) {
-        (void)hipFuncSetAttribute((const void *)k_stage_rec2c_f32<ME, ME2, 0, NT, WPE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)k_stage_rec2c_f32<ME, ME2, 1, NT, WPE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)k_stage_rec2c_f32<ME, ME2, 2, NT, WPE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)k_stage_rec2c_f32<ME, ME2, 3, NT, WPE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)k_stage_rec2c_f32<ME, ME2, 4, NT, WPE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)k_stage_rec2c_f32<ME, ME2, 5, NT, WPE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)k_stage_rec2c_f32<ME, ME2, 6, NT, WPE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)k_stage_rec2c_f32<ME, ME2, 10, NT, WPE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)k_stage_rec2c_f32<ME, ME2, 11, NT, WPE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    // the default 64 KB of dynamic LDS; such launches are small (the boundary group), occupancy does not matter there.  The
+    // first such launch raises every mode of this (ME, ME2, NT) at once.
+    if (lds > 64 * 1024) {
+        const hipError_t e = raise_dyn_lds({(const void *)k_stage_rec2c_f32<ME, ME2, 0, NT, WPE>, (const void *)k_stage_rec2c_f32<ME, ME2, 1, NT, WPE>,
+                                            (const void *)k_stage_rec2c_f32<ME, ME2, 2, NT, WPE>, (const void *)k_stage_rec2c_f32<ME, ME2, 3, NT, WPE>,
+                                            (const void *)k_stage_rec2c_f32<ME, ME2, 4, NT, WPE>, (const void *)k_stage_rec2c_f32<ME, ME2, 5, NT, WPE>,
+                                            (const void *)k_stage_rec2c_f32<ME, ME2, 6, NT, WPE>, (const void *)k_stage_rec2c_f32<ME, ME2, 10, NT, WPE>,
+                                            (const void *)k_stage_rec2c_f32<ME, ME2, 11, NT, WPE>},
+                                           160 * 1024);
+        if (e != hipSuccess) return e;
     }
     const dim3 b(NT);
     switch (mode) {
-        case 0: hipLaunchKernelGGL((k_stage_rec2c_f32<ME, ME2, 0, NT, WPE>), g, b, lds, s, m, a, mE, mC); return true;
-        case 1: hipLaunchKernelGGL((k_stage_rec2c_f32<ME, ME2, 1, NT, WPE>), g, b, lds, s, m, a, mE, mC); return true;
-        case 2: hipLaunchKernelGGL((k_stage_rec2c_f32<ME, ME2, 2, NT, WPE>), g, b, lds, s, m, a, mE, mC); return true;
-        case 3: hipLaunchKernelGGL((k_stage_rec2c_f32<ME, ME2, 3, NT, WPE>), g, b, lds, s, m, a, mE, mC); return true;
-        case 4: hipLaunchKernelGGL((k_stage_rec2c_f32<ME, ME2, 4, NT, WPE>), g, b, lds, s, m, a, mE, mC); return true;
-        case 5: hipLaunchKernelGGL((k_stage_rec2c_f32<ME, ME2, 5, NT, WPE>), g, b, lds, s, m, a, mE, mC); return true;
-        case 6: hipLaunchKernelGGL((k_stage_rec2c_f32<ME, ME2, 6, NT, WPE>), g, b, lds, s, m, a, mE, mC); return true;
-        case 10: hipLaunchKernelGGL((k_stage_rec2c_f32<ME, ME2, 10, NT, WPE>), g, b, lds, s, m, a, mE, mC); return true;
-        case 11: hipLaunchKernelGGL((k_stage_rec2c_f32<ME, ME2, 11, NT, WPE>), g, b, lds, s, m, a, mE, mC); return true;
+        case 0: hipLaunchKernelGGL((k_stage_rec2c_f32<ME, ME2, 0, NT, WPE>), g, b, lds, s, m, a, mE, mC); return hipGetLastError();
+        case 1: hipLaunchKernelGGL((k_stage_rec2c_f32<ME, ME2, 1, NT, WPE>), g, b, lds, s, m, a, mE, mC); return hipGetLastError();
+        case 2: hipLaunchKernelGGL((k_stage_rec2c_f32<ME, ME2, 2, NT, WPE>), g, b, lds, s, m, a, mE, mC); return hipGetLastError();
+        case 3: hipLaunchKernelGGL((k_stage_rec2c_f32<ME, ME2, 3, NT, WPE>), g, b, lds, s, m, a, mE, mC); return hipGetLastError();
+        case 4: hipLaunchKernelGGL((k_stage_rec2c_f32<ME, ME2, 4, NT, WPE>), g, b, lds, s, m, a, mE, mC); return hipGetLastError();
+        case 5: hipLaunchKernelGGL((k_stage_rec2c_f32<ME, ME2, 5, NT, WPE>), g, b, lds, s, m, a, mE, mC); return hipGetLastError();
+        case 6: hipLaunchKernelGGL((k_stage_rec2c_f32<ME, ME2, 6, NT, WPE>), g, b, lds, s, m, a, mE, mC); return hipGetLastError();
+        case 10: hipLaunchKernelGGL((k_stage_rec2c_f32<ME, ME2, 10, NT, WPE>), g, b, lds, s, m, a, mE, mC); return hipGetLastError();
+        case 11: hipLaunchKernelGGL((k_stage_rec2c_f32<ME, ME2, 11, NT, WPE>), g, b, lds, s, m, a, mE, mC); return hipGetLastError();
     }
-    return false;
+    return hipErrorNotSupported;
 }
 
+// Which modes of the fp32-storage kernel run as 512-thread workgroups bounded to 128 registers (two per CU = 4 waves per
+// SIMD instead of three 4-wave workgroups = 3): bit m = mode m of tuning key 1.  Modes 0 and 1 (no Curr / New rows in flight)
+// fit 128 registers without spills, the others do not (tools/kernel_regs.py).  Measured on config 5 (profiles/r03_variants.txt):
+// mode 0, the tendency launch, 3.81 -> 3.71 ms; mode 1, RK stage 1, 4.81 -> 5.07 ms (its two result streams per entity
+// queue up behind twice as many waves) -- so mode 0 only by default.
 template <int ME, int ME2>
-static bool launch_rec2c_f32(const ColMesh &m, const StageArgs &a, int mode, dim3 g, dim3, size_t lds, int mE, int mC, hipStream_t s)
+static hipError_t launch_rec2c_f32(const ColMesh &m, const StageArgs &a, int mode, dim3 g, size_t lds, int mE, int mC, hipStream_t s)
 {
     // two 512-thread workgroups must fit a CU's 160 KB of LDS for the wide form to mean 4 waves per SIMD
-    if (((f32_wide_modes() >> mode) & 1) && 2 * lds <= 160 * 1024)
+    if (((tuning(TUNE_F32_WIDE) >> mode) & 1) && 2 * lds <= 160 * 1024)
         return launch_rec2c_f32_nt<ME, ME2, 512, 4>(m, a, mode, g, lds, mE, mC, s);
     return launch_rec2c_f32_nt<ME, ME2, BLOCK, 3>(m, a, mode, g, lds, mE, mC, s);
 }
@@ -1700,19 +1694,18 @@ bool stage_f32_supported(const MeshDev &md)
 hipError_t launch_stage_rec2c_f32(const MeshDev &md, const StageArgs &a, hipStream_t s)
 {
     const int nLaunch = md.nPatches + (md.tailPatch >= 0 ? 1 : 0);
-    const dim3 g(8 * ((nLaunch + 7) / 8)), b(BLOCK);
+    const dim3 g(8 * ((nLaunch + 7) / 8));
     const ColMesh m = col_mesh(md, nLaunch);
     int mode = colp_mode(a);
     if (mode < 0 || !stage_f32_supported(md)) return hipErrorNotSupported;
     if (a.vort && (mode < 4 || !stage_curl_fused(md))) return hipErrorNotSupported;
-    if (fe_lean_instances() && colp_lean(a, mode)) mode += 5;        // a lean Forward-Euler launch: modes 10 / 11
+    if (tuning(TUNE_FE_LEAN_INST) && colp_lean(a, mode)) mode += 5;        // a lean Forward-Euler launch: modes 10 / 11
     const size_t lds = ((rec_lds_bytes(md) + 15) & ~(size_t)15) + (size_t)md.maxOwnE * md.K * 4 + 16 + (a.vort ? vert_lds_bytes(md) + 16 : 0);
     if (lds > 160 * 1024) return hipErrorNotSupported;
-    bool ok = false;
-    if (md.ME == 6 && md.ME2 == 10) ok = launch_rec2c_f32<6, 10>(m, a, mode, g, b, lds, md.maxOwnE, md.maxOwnC, s);
-    else if (md.ME == 8 && md.ME2 == 14) ok = launch_rec2c_f32<8, 14>(m, a, mode, g, b, lds, md.maxOwnE, md.maxOwnC, s);
-    else if (md.ME <= 6 && md.ME2 <= 14) ok = launch_rec2c_f32<6, 14>(m, a, mode, g, b, lds, md.maxOwnE, md.maxOwnC, s);
-    return ok ? hipGetLastError() : hipErrorNotSupported;
+    if (md.ME == 6 && md.ME2 == 10) return launch_rec2c_f32<6, 10>(m, a, mode, g, lds, md.maxOwnE, md.maxOwnC, s);
+    if (md.ME == 8 && md.ME2 == 14) return launch_rec2c_f32<8, 14>(m, a, mode, g, lds, md.maxOwnE, md.maxOwnC, s);
+    if (md.ME <= 6 && md.ME2 <= 14) return launch_rec2c_f32<6, 14>(m, a, mode, g, lds, md.maxOwnE, md.maxOwnC, s);
+    return hipErrorNotSupported;
 }
 
 // valid for even K <= 64 on meshes whose rows stay below 4 GiB (the caller checks: the tuned Forward-Euler path)

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
+
 #include "moka_internal.hpp"
 
 namespace moka {
@@ -99,18 +101,26 @@ bool stage_curl_fits(const MeshDev &m, bool f32);      // ... with patches of m.
 // fp32-state form (state pointers of StageArgs are float arrays); stage_f32_supported: can this mesh carry one
 bool stage_f32_supported(const MeshDev &m);
 hipError_t launch_stage_rec2c_f32(const MeshDev &m, const StageArgs &a, hipStream_t s);
-void set_f32_wide_modes(int mask);      // measurement: which modes of the fp32-storage kernel run as (512 threads, 4 waves per SIMD)
-int f32_wide_modes();
-void set_curl_fused(int on);            // measurement: 0 = the Forward-Euler vertex pass always gets a launch of its own
-int curl_fused();
-void set_fe_lean(int on);               // measurement: 0 = Forward-Euler steps always store every array (no lean steps)
-int fe_lean_enabled();
-void set_fe_prev_mode(int on);          // measurement: 0 = never form the stale layerThicknessEdge from the previous level (mode 6)
-int fe_prev_mode();
-void set_fe_lean_instances(int on);    // measurement: 0 = lean Forward-Euler launches through the general instances (modes 5 / 6) instead of 10 / 11
-int fe_lean_instances();
-void set_pair_modes(int mask);          // measurement: which modes of the Float64 stage kernel take two patches per 512-thread workgroup
-int pair_modes();
+
+// Process-wide launch-shape switches: the keys of moka_set_tuning / moka_get_tuning (include/moka_hip.h).  One table in api.hip
+// holds each key's default and accepted values; launchers read the current value through tuning().
+enum TuningKey : int {
+    TUNE_F32_WIDE = 1,       // bit mask: modes of the fp32-storage kernel run as 512-thread workgroups (4 waves per SIMD)
+    TUNE_FE_PREV = 2,        // 0 = never form the stale layerThicknessEdge from the previous level (mode 6)
+    TUNE_CURL_FUSED = 3,     // 0 = the Forward-Euler vertex pass always gets a launch of its own
+    TUNE_FE_LEAN = 4,        // 0 = Forward-Euler steps always store every array (no lean steps)
+    TUNE_NL_SHAPE = 5,       // launch shape of the nonlinear stage kernel's patch form (nonlinear.hip, nl_stage_kernel)
+    TUNE_NL_CAP = 6,         // test hook: upper limit of the vertex rows k_stage_nl5 keeps resident (0 = none)
+    TUNE_RK13 = 7,           // 1 = RK4 steps in the 13-stream form where mk::rk13_usable (NOT result-neutral)
+    TUNE_PAIR = 8,           // bit mask: modes of the Float64 stage kernel that take two patches per 512-thread workgroup
+    TUNE_FE_LEAN_INST = 9,   // 0 = lean Forward-Euler launches through the general instances (modes 5 / 6) instead of 10 / 11
+};
+int tuning(TuningKey key);
+
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) of each kernel in `fns` to `bytes`, once per device and kernel (the attribute is
+// a per-device property of a kernel; a process may drive several devices, e.g. LocalCluster over a device list).  Called by the
+// launchers ahead of their first large launch, never inside a stream capture: moka_run steps eagerly before it captures.
+hipError_t raise_dyn_lds(std::initializer_list<const void *> fns, int bytes);
 hipError_t launch_update_ssh_f32(const MeshDev &m, const float *h, float *ssh, int nlev, int lpc, hipStream_t s);
 hipError_t launch_permute_rows_f32(void *dst, const void *src, const int32_t *n2o, int64_t n, int K, int to_device,
                                    hipStream_t s);
@@ -153,12 +163,8 @@ struct NlArgs {
 };
 // form: 0 = best available, 1 = patch kernels without the LDS q_e rows, 2 = 16-byte-lane entity kernels, 3 = generic lane-group kernels
 // (prepare and stage must be called with the same form: forms 0 / 1 keep F alone in NlArgs.fq, forms 2 / 3 {F, q_e} pairs)
-void set_nl_shape(int v);
-int nl_shape();
-bool nl_stage_is_nl5(const MeshDev &m, int lpc, int form);  // the nonlinear stage launch of this mesh is k_stage_nl5 (knows StageArgs.rkMode 9)
+bool nl_stage_is_nl5(const MeshDev &m, int lpc, bool rowsOk, int form);  // the nonlinear stage launch of this mesh is k_stage_nl5 (knows StageArgs.rkMode 9)
 bool nl_patch_forms(const MeshDev &m, int lpc, int form);   // do the nonlinear launches of this mesh go through the per-patch kernels (which serve patch ranges)
-void set_nl_cap_limit(int v);
-int nl_cap_limit();
 hipError_t launch_nl_prepare(const MeshDev &m, const double *u, const double *h, const NlArgs &nl, int lpc, int form, hipStream_t s);
 // rowsOk: the plan built the patch row lists (rowStart / rowEdge / leoe; Plan.ldsOk)
 hipError_t launch_stage_nl(const MeshDev &m, const StageArgs &a, const NlArgs &nl, int lpc, bool rowsOk, int form, hipStream_t s);

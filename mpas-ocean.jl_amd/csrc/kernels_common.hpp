@@ -269,18 +269,6 @@ inline bool colp_lean(const StageArgs &a, int mode)
     return (mode == 5 || mode == 6) && a.pu_out && a.ph_out && a.ssh_out && !a.tendU && !a.tendH && !a.F && !a.div && !a.hEdgeNew;
 }
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device property of a kernel: remember per device (a process may
-// drive several, e.g. LocalCluster over a device list) whether `slot` (one bit per kernel family) has been raised there
-inline bool lds_attr_needed(int slot)
-{
-    static std::atomic<uint32_t> done[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64) return true;
-    const uint32_t bit = 1u << slot;
-    return !(done[dev].fetch_or(bit) & bit);
-}
-
 inline size_t rec_lds_bytes(const MeshDev &md)
 {
     return (size_t)md.maxOwnE * (2 * md.ME2 + 1) * 8 + (size_t)md.maxOwnC * (md.ME + 2) * 8 +

@@ -329,17 +329,6 @@ __global__ __launch_bounds__(BLOCK) void k_stage_nl2(const MeshDev m, const Stag
 // block -> patch by patch_of_block (kernels_common.hpp): an XCD walks one contiguous eighth of the patch list, so the patches in
 // flight on an XCD are neighbours and their halo rows meet in that XCD's L2 (config 4, PMC: k_stage_nl4 fetches 8.7 GB per
 // launch instead of 13.3, k_nl_prep4 3.1 instead of 5.4 -- at unchanged times: both kernels are bound by latency, not bytes)
-// launch shape of the patch form of the nonlinear stage kernel (moka_set_tuning key 5; identical results):
-//   0 (default) k_stage_nl5 (vertex rows + own F rows in LDS), 512 threads; 1 k_stage_nl4 (q_e rows in LDS);
-//   2 k_stage_nl5 with 256 threads; 3 k_stage_nl5 without the own F rows
-static std::atomic<int> g_nlShape{0}, g_nlCapLimit{0};
-void set_nl_shape(int v) { g_nlShape.store(v); }
-int nl_shape() { return g_nlShape.load(); }
-// key 6: upper limit of the vertex rows k_stage_nl5 keeps resident (0 = what the LDS budget holds): lets a test drive small meshes
-// through the path of patches that list more vertices than fit
-void set_nl_cap_limit(int v) { g_nlCapLimit.store(v); }
-int nl_cap_limit() { return g_nlCapLimit.load(); }
-
 static inline unsigned nl_grid(int nPatches) { return 8u * (unsigned)((nPatches + 7) / 8); }
 
 constexpr int NL4_VCH = 64, NL4_CCH = 16, NL4_ECH = 96;   // vertices / cells / edges staged per chunk
@@ -1232,7 +1221,7 @@ static inline int nl5_cap(const MeshDev &m, bool cf)
     const size_t budget = 80 * 1024, rec = nl5_lds_bytes(m, 0, cf);
     if (rec >= budget) return 0;
     int cap = (int)std::min<size_t>((size_t)m.maxPV, (budget - rec) / ((size_t)m.K * 8));
-    if (const int lim = g_nlCapLimit.load(); lim > 0) cap = std::min(cap, lim);
+    if (const int lim = tuning(TUNE_NL_CAP); lim > 0) cap = std::min(cap, lim);
     return cap;
 }
 
@@ -1247,7 +1236,60 @@ static inline bool nl3_ok(const MeshDev &m) { return m.K <= 64 && !(m.K & 1) && 
 
 bool nl_patch_forms(const MeshDev &m, int lpc, int form) { return lpc == 64 && nl3_ok(m) && form <= 1; }
 
+// every field's rows below 4 GiB: the 32-bit byte offsets of the LDS forms
+static inline bool rows_below_4gib(const MeshDev &m) { return (uint64_t)std::max(m.nE, std::max(m.nV, m.nC)) * m.K * 8 < (1ull << 32); }
+
+// 16-byte-lane entity kernels (even 34 <= K <= 64)
+static inline bool nl_lanes_ok(const MeshDev &m, int lpc, int form) { return lpc == 64 && m.K <= 64 && !(m.K & 1) && form <= 2; }
+
 static inline dim3 grid2(int n) { return dim3((unsigned)std::min(std::max((n + 7) / 8, 1), 65536)); }
+
+// The kernels that serve a nonlinear launch, chosen in one place for the launchers and for the questions asked ahead of a launch
+// (nl_stage_is_nl5; nl_patch_forms, which del4_path and the partitioned paths ask, is the patch kernels' branch of both choices).
+// The patch forms come first, then the 16-byte-lane entity kernels, then the generic lane-group kernels.
+enum class NlPrep { P5, P4, Lanes, Lpc };
+
+static NlPrep nl_prepare_kernel(const MeshDev &m, int lpc, int form)
+{
+    if (lpc == 64 && nl3_ok(m) && form == 0 && tuning(TUNE_NL_SHAPE) != 1 && m.maxOwnV > 0 && np5_lds_bytes(m) <= 64 * 1024 &&
+        rows_below_4gib(m))
+        return NlPrep::P5;
+    if (nl_patch_forms(m, lpc, form)) return NlPrep::P4;
+    if (nl_lanes_ok(m, lpc, form)) return NlPrep::Lanes;
+    return NlPrep::Lpc;
+}
+
+// Launch shape of the patch form of the stage kernel (tuning key 5; identical results): 0 (default) k_stage_nl5 (vertex rows +
+// own F rows in LDS), 512 threads; 1 k_stage_nl4 (q_e rows in LDS); 2 k_stage_nl5 with 256 threads; 3 k_stage_nl5 without the
+// own F rows.  Key 6 limits the vertex rows k_stage_nl5 keeps resident (nl5_cap): lets a test drive small meshes through the path
+// of patches that list more vertices than fit.
+struct NlStage {
+    enum Kind { Nl5, Nl4, Nl3, Lanes, Lpc } kind;
+    bool narrow = false;      // Nl5: 256 threads (shape 2) instead of 512
+    bool cf = false;          // Nl5: the own F rows resident too
+    int pvCap = 0;            // Nl5: vertex rows resident (MeshDev.pvCap)
+    size_t lds = 0;           // Nl5 / Nl4: dynamic LDS bytes
+};
+
+static NlStage nl_stage_kernel(const MeshDev &m, int lpc, bool rowsOk, int form)
+{
+    const int shape = tuning(TUNE_NL_SHAPE);
+    if (lpc == 64 && nl3_ok(m) && form == 0 && shape != 1 && m.pvStart && m.maxPV > 0 && rows_below_4gib(m)) {
+        // own F rows resident too where that leaves room for most of a patch's vertex rows (launches that carry the halo-straddling
+        // patches of a partitioned mesh, with up to 6 own edges per cell, go without)
+        const bool cf = shape != 3 && nl5_cap(m, true) >= std::min(m.maxPV, 64);
+        const int cap = nl5_cap(m, cf);
+        if (cap >= 16) return {NlStage::Nl5, shape == 2, cf, cap, nl5_lds_bytes(m, cap, cf)};
+    }
+    if (lpc == 64 && nl3_ok(m) && rowsOk && form == 0 && nl4_lds_bytes(m) <= 80 * 1024)      // two 512-thread workgroups per CU
+        return {NlStage::Nl4, false, false, 0, nl4_lds_bytes(m)};
+    if (nl_patch_forms(m, lpc, form)) return {NlStage::Nl3};
+    if (nl_lanes_ok(m, lpc, form)) return {NlStage::Lanes};
+    return {NlStage::Lpc};
+}
+
+// the stage launch goes through k_stage_nl5 (the only nonlinear stage kernel that knows the 13-stream form: StageArgs.rkMode 9)
+bool nl_stage_is_nl5(const MeshDev &m, int lpc, bool rowsOk, int form) { return nl_stage_kernel(m, lpc, rowsOk, form).kind == NlStage::Nl5; }
 
 template <int LPC>
 static hipError_t launch_nl_prepare_lpc(const MeshDev &m, const double *u, const double *h, const NlArgs &nl, hipStream_t s)
@@ -1271,83 +1313,57 @@ static hipError_t launch_stage_nl_lpc(const MeshDev &m, const StageArgs &a, cons
 
 hipError_t launch_nl_prepare(const MeshDev &m, const double *u, const double *h, const NlArgs &nl, int lpc, int form, hipStream_t s)
 {
-    if (lpc == 64 && nl3_ok(m) && form == 0 && g_nlShape.load() != 1 && m.maxOwnV > 0 && np5_lds_bytes(m) <= 64 * 1024 &&
-        (uint64_t)std::max(m.nE, std::max(m.nV, m.nC)) * m.K * 8 < (1ull << 32)) {
-        hipLaunchKernelGGL((k_nl_prep5<6, 3>), dim3(nl_grid(m.nPatches)), dim3(BLOCK), np5_lds_bytes(m), s, m, u, h, nl);
-        return hipGetLastError();
-    }
-    if (lpc == 64 && nl3_ok(m) && form <= 1) {
-        hipLaunchKernelGGL((k_nl_prep4<6, 3>), dim3(nl_grid(m.nPatches)), dim3(BLOCK), 0, s, m, u, h, nl);
-        return hipGetLastError();
-    }
-    if (lpc == 64 && m.K <= 64 && !(m.K & 1) && form <= 2) {     // even 34 <= K <= 64: 16-byte lanes
-        hipLaunchKernelGGL(k_nl_vertex2, grid2(m.nV), dim3(BLOCK), 0, s, m, u, h, nl.qv, nl.zv);
-        hipLaunchKernelGGL(k_nl_cell2, grid2(m.nC), dim3(BLOCK), 0, s, m, u, nl.ke, nl.divc);
-        hipLaunchKernelGGL(k_nl_edge2, grid2(m.nE), dim3(BLOCK), 0, s, m, u, h, nl);   // after k_nl_vertex2 (same stream)
-        return hipGetLastError();
+    switch (nl_prepare_kernel(m, lpc, form)) {
+        case NlPrep::P5:
+            hipLaunchKernelGGL((k_nl_prep5<6, 3>), dim3(nl_grid(m.nPatches)), dim3(BLOCK), np5_lds_bytes(m), s, m, u, h, nl);
+            return hipGetLastError();
+        case NlPrep::P4:
+            hipLaunchKernelGGL((k_nl_prep4<6, 3>), dim3(nl_grid(m.nPatches)), dim3(BLOCK), 0, s, m, u, h, nl);
+            return hipGetLastError();
+        case NlPrep::Lanes:
+            hipLaunchKernelGGL(k_nl_vertex2, grid2(m.nV), dim3(BLOCK), 0, s, m, u, h, nl.qv, nl.zv);
+            hipLaunchKernelGGL(k_nl_cell2, grid2(m.nC), dim3(BLOCK), 0, s, m, u, nl.ke, nl.divc);
+            hipLaunchKernelGGL(k_nl_edge2, grid2(m.nE), dim3(BLOCK), 0, s, m, u, h, nl);   // after k_nl_vertex2 (same stream)
+            return hipGetLastError();
+        case NlPrep::Lpc: break;
     }
 #define CALL(L) launch_nl_prepare_lpc<L>(m, u, h, nl, s)
     DISPATCH_LPC(lpc, CALL)
 #undef CALL
 }
 
-// the stage launch goes through k_stage_nl5 (the only nonlinear stage kernel that knows the 13-stream form: StageArgs.rkMode 9)
-bool nl_stage_is_nl5(const MeshDev &m, int lpc, int form)
+template <int NT, int W, bool CF, bool D4>
+static hipError_t launch_nl5(const MeshDev &m, const StageArgs &a, const NlArgs &nl, const NlStage &k, hipStream_t s)
 {
-    const int shape = g_nlShape.load();
-    if (!(lpc == 64 && nl3_ok(m) && form == 0 && shape != 1 && m.pvStart && m.maxPV > 0 &&
-          (uint64_t)std::max(m.nE, std::max(m.nV, m.nC)) * m.K * 8 < (1ull << 32)))
-        return false;
-    const bool cf = shape != 3 && nl5_cap(m, true) >= std::min(m.maxPV, 64);
-    return nl5_cap(m, cf) >= 16;
+    if (k.lds > 64 * 1024)
+        if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_stage_nl5<6, 10, NT, W, CF, D4>)}, 80 * 1024); e != hipSuccess) return e;
+    MeshDev mc = m;
+    mc.pvCap = k.pvCap;
+    hipLaunchKernelGGL((k_stage_nl5<6, 10, NT, W, CF, D4>), dim3(nl_grid(m.nPatches)), dim3(NT), k.lds, s, mc, a, nl);
+    return hipGetLastError();
 }
 
-// D4: the instances with Del4 mixing (NlArgs.coef4 != nullptr); their LDS attribute slots are 8 .. 12
+// D4: the instances with Del4 mixing (NlArgs.coef4 != nullptr)
 template <bool D4>
-static hipError_t launch_stage_nl_t(const MeshDev &m, const StageArgs &a, const NlArgs &nl, int lpc, bool rowsOk, int form, hipStream_t s)
+static hipError_t launch_stage_nl_t(const MeshDev &m, const StageArgs &a, const NlArgs &nl, int lpc, const NlStage &k, hipStream_t s)
 {
-    const int shape = g_nlShape.load();
-    if (lpc == 64 && nl3_ok(m) && form == 0 && shape != 1 && m.pvStart && m.maxPV > 0 &&
-        (uint64_t)std::max(m.nE, std::max(m.nV, m.nC)) * m.K * 8 < (1ull << 32)) {
-        // own F rows resident too where that leaves room for most of a patch's vertex rows (launches that carry the halo-straddling
-        // patches of a partitioned mesh, with up to 6 own edges per cell, go without)
-        const bool cf = shape != 3 && nl5_cap(m, true) >= std::min(m.maxPV, 64);
-        MeshDev mc = m;
-        mc.pvCap = nl5_cap(m, cf);
-        if (mc.pvCap >= 16) {
-            const size_t lds = nl5_lds_bytes(mc, mc.pvCap, cf);
-            const int slot = (D4 ? 9 : 17) + (shape == 2 ? 2 : 0) + (cf ? 1 : 0);
-            const void *fn = shape == 2 ? (cf ? reinterpret_cast<const void *>(k_stage_nl5<6, 10, 256, 3, true, D4>) : reinterpret_cast<const void *>(k_stage_nl5<6, 10, 256, 3, false, D4>))
-                                        : (cf ? reinterpret_cast<const void *>(k_stage_nl5<6, 10, 512, 4, true, D4>) : reinterpret_cast<const void *>(k_stage_nl5<6, 10, 512, 4, false, D4>));
-            if (lds > 64 * 1024 && lds_attr_needed(slot)) {
-                hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-                if (e != hipSuccess) return e;
-            }
-            const dim3 g(nl_grid(m.nPatches));
-            if (shape == 2 && cf) hipLaunchKernelGGL((k_stage_nl5<6, 10, 256, 3, true, D4>), g, dim3(256), lds, s, mc, a, nl);
-            else if (shape == 2) hipLaunchKernelGGL((k_stage_nl5<6, 10, 256, 3, false, D4>), g, dim3(256), lds, s, mc, a, nl);
-            else if (cf) hipLaunchKernelGGL((k_stage_nl5<6, 10, 512, 4, true, D4>), g, dim3(512), lds, s, mc, a, nl);
-            else hipLaunchKernelGGL((k_stage_nl5<6, 10, 512, 4, false, D4>), g, dim3(512), lds, s, mc, a, nl);
+    // the 13-stream form's last stage exists in k_stage_nl5 only (mk::rk13_usable asks nl_stage_is_nl5 first)
+    if (a.rkMode == 9 && k.kind != NlStage::Nl5) return hipErrorNotSupported;
+    switch (k.kind) {
+        case NlStage::Nl5:
+            if (k.narrow) return k.cf ? launch_nl5<256, 3, true, D4>(m, a, nl, k, s) : launch_nl5<256, 3, false, D4>(m, a, nl, k, s);
+            return k.cf ? launch_nl5<512, 4, true, D4>(m, a, nl, k, s) : launch_nl5<512, 4, false, D4>(m, a, nl, k, s);
+        case NlStage::Nl4:
+            if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_stage_nl4<6, 10, 512, D4>)}, 80 * 1024); e != hipSuccess) return e;
+            hipLaunchKernelGGL((k_stage_nl4<6, 10, 512, D4>), dim3(nl_grid(m.nPatches)), dim3(512), k.lds, s, m, a, nl);
             return hipGetLastError();
-        }
-    }
-    if (a.rkMode == 9) return hipErrorNotSupported;      // the 13-stream form's last stage exists in k_stage_nl5 only (mk::rk13_usable asks nl_stage_is_nl5 first)
-    if (lpc == 64 && nl3_ok(m) && rowsOk && form == 0 && nl4_lds_bytes(m) <= 80 * 1024) {     // two 512-thread workgroups per CU
-        const size_t lds = nl4_lds_bytes(m);
-        if (lds_attr_needed(D4 ? 8 : 16)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_stage_nl4<6, 10, 512, D4>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL((k_stage_nl4<6, 10, 512, D4>), dim3(nl_grid(m.nPatches)), dim3(512), lds, s, m, a, nl);
-        return hipGetLastError();
-    }
-    if (lpc == 64 && nl3_ok(m) && form <= 1) {
-        hipLaunchKernelGGL((k_stage_nl3<6, 10, D4>), dim3(nl_grid(m.nPatches)), dim3(BLOCK), 0, s, m, a, nl);
-        return hipGetLastError();
-    }
-    if (lpc == 64 && m.K <= 64 && !(m.K & 1) && form <= 2) {
-        hipLaunchKernelGGL(k_stage_nl2<D4>, grid2(std::max(m.nE, m.nC)), dim3(BLOCK), 0, s, m, a, nl);
-        return hipGetLastError();
+        case NlStage::Nl3:
+            hipLaunchKernelGGL((k_stage_nl3<6, 10, D4>), dim3(nl_grid(m.nPatches)), dim3(BLOCK), 0, s, m, a, nl);
+            return hipGetLastError();
+        case NlStage::Lanes:
+            hipLaunchKernelGGL(k_stage_nl2<D4>, grid2(std::max(m.nE, m.nC)), dim3(BLOCK), 0, s, m, a, nl);
+            return hipGetLastError();
+        case NlStage::Lpc: break;
     }
 #define CALL(L) launch_stage_nl_lpc<L, D4>(m, a, nl, s)
     DISPATCH_LPC(lpc, CALL)
@@ -1356,7 +1372,8 @@ static hipError_t launch_stage_nl_t(const MeshDev &m, const StageArgs &a, const 
 
 hipError_t launch_stage_nl(const MeshDev &m, const StageArgs &a, const NlArgs &nl, int lpc, bool rowsOk, int form, hipStream_t s)
 {
-    return nl.coef4 ? launch_stage_nl_t<true>(m, a, nl, lpc, rowsOk, form, s) : launch_stage_nl_t<false>(m, a, nl, lpc, rowsOk, form, s);
+    const NlStage k = nl_stage_kernel(m, lpc, rowsOk, form);
+    return nl.coef4 ? launch_stage_nl_t<true>(m, a, nl, lpc, k, s) : launch_stage_nl_t<false>(m, a, nl, lpc, k, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1481,10 +1498,7 @@ __global__ __launch_bounds__(D4_NT, 2) void k_d4_patch(const MeshDev m, const D4
 
 int del4_path(const MeshDev &m, const D4Rows &r, int lpc, int form)
 {
-    if (nl_patch_forms(m, lpc, form) && r.start && (size_t)r.maxRows * m.K * 8 <= 80 * 1024 &&
-        (uint64_t)std::max(m.nE, std::max(m.nV, m.nC)) * m.K * 8 < (1ull << 32))
-        return 1;
-    return 2;
+    return nl_patch_forms(m, lpc, form) && r.start && (size_t)r.maxRows * m.K * 8 <= 80 * 1024 && rows_below_4gib(m) ? 1 : 2;
 }
 
 hipError_t launch_del4(const MeshDev &m, const D4Rows &r, const double *divc, const double *zv, double *div4, double *curl4, int path,
@@ -1492,10 +1506,8 @@ hipError_t launch_del4(const MeshDev &m, const D4Rows &r, const double *divc, co
 {
     if (path == 1) {
         const size_t lds = (size_t)r.maxRows * m.K * 8;
-        if (lds > 64 * 1024 && lds_attr_needed(13)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_d4_patch<6, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-            if (e != hipSuccess) return e;
-        }
+        if (lds > 64 * 1024)
+            if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_d4_patch<6, 3>)}, 80 * 1024); e != hipSuccess) return e;
         hipLaunchKernelGGL((k_d4_patch<6, 3>), dim3(nl_grid(m.nPatches)), dim3(D4_NT), lds, s, m, r, divc, zv, div4, curl4);
         return hipGetLastError();
     }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <map>
 #include <string>
 #include <utility>
@@ -133,6 +134,24 @@ void state_detach(moka_state *st, bool halo = false);
         if (_e != hipSuccess)                                                                      \
             return mk::fail(ctx, MOKA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_e)); \
     } while (0)
+
+// The kernel choice of the linear stage launches.  The default stage kernels (launch_stage_rec2c*) may serve a Float64 state's
+// launches: kernel variant 0 (auto) or 11, 64 lanes per column, byte-offset records.  Whether they do depends on the patches too
+// (rec2c_supported / stage_curl_fits of launch_bounds); run_stage falls back to the column or the generic kernel.
+inline bool default_stage_kernels(const moka_state *st)
+{
+    const int v = st->ctx->variant;
+    return (v == 0 || v == 11) && st->mesh->lpc == 64 && st->mesh->colOk;
+}
+// the mesh as every whole-mesh stage launch sees it: maxima over the patches that are ever computed (at least 1)
+inline MeshDev launch_bounds(const moka_mesh *mm)
+{
+    MeshDev dev = mm->dev;
+    dev.maxOwnE = std::max(mm->plan.maxOwnELaunch, 1); dev.maxOwnC = std::max(mm->plan.maxOwnCLaunch, 1);
+    return dev;
+}
+// `form` of the nonlinear launchers: kernel variants 4 / 3 select the plainer forms of the nonlinear kernels too
+inline int nl_form(const moka_ctx *ctx) { return ctx->variant == 4 ? 1 : ctx->variant == 3 ? 3 : 0; }
 
 // every host->device copy of the library: on the context's stream, then synchronised (see api.hip)
 int h2d(moka_ctx *ctx, void *dst, const void *src, size_t bytes);

@@ -37,6 +37,45 @@ def test_ctx_create_fails_loudly_without_gpu():
     assert b"no CPU fallback" in L.lib().moka_last_error(None)
 
 
+
+# moka_set_tuning keys 1-9 (include/moka_hip.h): default, values that name kernel instances, values that name none
+TUNING = {
+    1: (0b1, [0, 0b11, 0x7f, (1 << 10) | (1 << 11), 0x7f | (1 << 10) | (1 << 11)], [1 << 7, 1 << 8, 1 << 9, 1 << 12, 1 << 16, -1]),
+    2: (1, [0, 1], [2, -1]),
+    3: (1, [0, 1], [2, -1]),
+    4: (1, [0, 1], [2, -1]),
+    5: (0, [0, 1, 2, 3], [4, -1]),
+    6: (0, [0, 16, 40, 1 << 20], [-1]),
+    7: (0, [0, 1], [2, -1]),
+    8: (0b10000011, [0, 0b1111, (1 << 16) | 0b1110001111, 1 << 16],
+        [1 << 4, 1 << 5, 1 << 6, 1 << 10, 1 << 11, (1 << 16) | (1 << 10), 1 << 17, -1]),
+    9: (1, [0, 1], [2, -1]),
+}
+
+
+def test_tuning_table_through_the_c_abi():
+    """One table holds keys 1-9: get returns the defaults, every accepted value round-trips, a value or mask bit that names no
+    kernel instance (key 8 bits 10 / 11: the lean modes have no pair instance) and an unknown key are MOKA_ERR_ARG and change
+    nothing."""
+    lib = L.lib()
+    v = C.c_int()
+    for key, (default, good, bad) in TUNING.items():
+        assert lib.moka_get_tuning(key, C.byref(v)) == 0 and v.value == default, key
+        try:
+            for x in good:
+                assert lib.moka_set_tuning(key, x) == 0, (key, x)
+                assert lib.moka_get_tuning(key, C.byref(v)) == 0 and v.value == x, (key, x)
+            assert lib.moka_set_tuning(key, default) == 0
+            for x in bad:
+                assert lib.moka_set_tuning(key, x) == L.ERR_ARG, (key, x)
+                assert lib.moka_get_tuning(key, C.byref(v)) == 0 and v.value == default, (key, x)
+        finally:
+            lib.moka_set_tuning(key, default)
+    for key in (-1, 0, 10, 11, 1 << 20):
+        assert lib.moka_set_tuning(key, 0) == L.ERR_ARG, key
+        assert lib.moka_get_tuning(key, C.byref(v)) == L.ERR_ARG, key
+    assert lib.moka_get_tuning(1, None) == L.ERR_ARG
+
 MESHES = {
     "planar": lambda: mg.planar_hex_mesh(12, 10, 1000.0, f0=1e-4),
     "sphere": lambda: mg.icosahedral_mesh(6),
