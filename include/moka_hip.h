@@ -516,6 +516,39 @@ int  moka_set_viscosity_del4(moka_state *st, double viscDel4, const double *mesh
  * the default and variant-4 forms), 2 the entity kernels, 0 no Del4 stage yet */
 int  moka_state_del4_path(const moka_state *st);
 
+/* ---- passive tracers (extension; the reference has none, parity unpinned, default off) ---------------------------
+ * nTracers >= 0 cell-centred tracers phi_j[k,c] ride with the RK4 step in the conservative flux form
+ *   d(h phi)/dt = -div(F phi_e),  F = u * h_e the thickness flux of the thickness equation,  phi_e = (phi_c + phi_c') / 2.
+ * For a provisional state (pu, ph, pphi), cell c and level k the tendency T accumulates from 0.0 over the slots i of edgesOnCell in
+ * slot order, skipping empty slots and slots with k >= maxLevelEdgeTop[e] (levels counted from 0; c' = the cell across slot i):
+ *   hE = 0.5 * (ph[k,c] + ph[k,c']);  F = pu[k,e] * hE;  pE = 0.5 * (pphi[k,c] + pphi[k,c']);
+ *   T += ((F * pE) * (dvEdge[e] * edgeSignOnCell[i,c])) * (1/areaCell[c])
+ * -- the thickness tendency with F * pE for F: a tracer that is 1 everywhere reproduces tendLayerThickness and stays exactly 1.0.
+ * One RK4 step, per tracer, with a = (dt/2, dt/2, dt), b = (dt/6, dt/3, dt/3, dt/6) and (pu_s, ph_s), ph_{s+1}, h_new the step's own
+ * provisional and new states, whatever terms are switched on (linear, nonlinear, Del2, Del4):
+ *   Qc = phi_cur * h_cur;  Qn = Qc;  pphi = phi_cur
+ *   s = 0..3:  t = T(pu_s, ph_s, pphi);  s < 3: pphi = (Qc + a[s] * t) / ph_{s+1};  Qn = Qn + b[s] * t
+ *   phi_new = Qn / h_new
+ * The library stores phi per time level (upload then download is exact; re-uploading layerThickness between steps leaves nothing
+ * stale: the contents Q exist inside a step only); layerThickness must be nonzero.  The tracers' time levels rotate with the state's
+ * (moka_step_rk4, moka_run(MOKA_RUNGE_KUTTA_4), moka_advance_time_levels).  Tracers never feed back: the dycore's fields are, bit for bit,
+ * those of a state without tracers, and moka_tendencies is unchanged.
+ * moka_set_tracers allocates the arrays (zeros; any earlier tracers are dropped); 0 frees them and restores the behaviour of a state
+ * that never had any.  MOKA_ERR_ARG for a negative count; MOKA_ERR_UNSUPPORTED for fp32-storage states, partitioned meshes and states
+ * that have a halo or a tape.  While nTracers > 0, moka_step_fe, moka_run(MOKA_FORWARD_EULER), moka_tape_create, moka_halo_create and
+ * the moka_rk4_dist_* calls return MOKA_ERR_UNSUPPORTED, and moka_set_tuning key 7 leaves the state on the running sum
+ * (moka_state_rk4_streams: 16).  moka_state_optimize_placement neither times nor moves the tracer arrays.
+ * Out of scope: upwind, FCT and higher-order edge values, tracer diffusion, Forward Euler, fp32 storage, partitioned meshes, reverse
+ * mode, the 13-stream form, YAML keys and NetCDF I/O of tracers, and fusing the tracer sum into the dycore's stage kernels. */
+int  moka_set_tracers(moka_state *st, int32_t nTracers);
+/* tracer j (0-based) at time_level 0 (previous) / 1 (current): (nVertLevels, nCells) doubles in the caller's cell numbering, like
+ * layerThickness */
+int  moka_tracer_upload(moka_state *st, int32_t j, int time_level, const double *host);
+int  moka_tracer_download(moka_state *st, int32_t j, int time_level, double *host);
+/* which kernel served the last tracer stage of this state: 1 the patch form (even 34 <= nVertLevels <= 64, hexagon-width byte-offset
+ * records, the default kernel choice), 2 the generic form (everything else, and kernel variant 3), 0 no tracer stage yet */
+int  moka_state_tracer_path(const moka_state *st);
+
 /* ---- reverse mode of the Forward-Euler loop ----------------------------------------------------------------
  * The reference gets d sum(ssh^2) / d (initial normalVelocity, layerThickness) from Enzyme over ocn_run_loop
  * (ext/MPASEnzymeExt.jl, test/enzyme/test_Enzyme_end2end.jl:62-96; on CUDA it yields NaNs there, :183-186).

@@ -1173,6 +1173,7 @@ int moka_advance_time_levels(moka_state *st, int flags)
     HIPCHK(st->ctx, launch_copy(st->lev[0].ssh, st->lev[1].ssh, p.nC, s));
     HIPCHK(st->ctx, launch_copy(st->lev[0].u, st->lev[1].u, (int64_t)p.K * p.nE, s));
     HIPCHK(st->ctx, launch_copy(st->lev[0].h, st->lev[1].h, (int64_t)p.K * p.nC, s));
+    if (st->nTracers > 0) HIPCHK(st->ctx, launch_copy(st->trPhi[0], st->trPhi[1], (int64_t)st->nTracers * p.K * p.nC, s));
     return MOKA_OK;
 }
 
@@ -1247,6 +1248,7 @@ int moka_step_fe(moka_state *st, double dt, int flags)
 {
     if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
     if (st->nonlinear) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "nonlinear terms: moka_tendencies / RK4 only");
+    if (st->nTracers > 0) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "tracers: transported by RK4 steps only (no Forward Euler)");
     HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
     const moka_mesh *mm = st->mesh;
     const bool whole = mm->plan.nPatchesLaunch == mm->plan.nPatches;
@@ -1354,6 +1356,7 @@ int rk4_begin(moka_state *st, const double **ssh0)
 void rk4_end(moka_state *st)
 {
     std::swap(st->lev[0], st->lev[1]);
+    std::swap(st->trPhi[0], st->trPhi[1]);       // the tracers' time levels rotate with the state's
     st->sshConsistent = true;
     st->diagDirty = true;
     st->tendDirty = true;
@@ -1373,6 +1376,7 @@ void rk4_end(moka_state *st)
 bool rk13_usable(const moka_state *st)
 {
     if (!tuning(TUNE_RK13) || st->f32) return false;
+    if (st->nTracers > 0) return false;                          // tracers: the running sum (their stage launch follows its buffers)
     if (st->nonlinear && st->viscDel4 != 0.0) return false;     // Del4: the reference's running sum (no 13-stream twin)
     const moka_mesh *mm = st->mesh;
     if (mm->plan.nPatchesLaunch != mm->plan.nPatches) return false;
@@ -1415,6 +1419,28 @@ void rk13_end(moka_state *st)
     st->lazyPu = st->lazyPh = nullptr; st->lazyOwner = nullptr;
 }
 }  // namespace mk
+// The tracer launch of RK4 stage s, behind the dycore's launch g on the compute stream (it reads the thickness that launch wrote:
+// the next provisional one, the new level's at stage 4; the stage's own provisional state is never written by its launch).  Buffers
+// follow rk4_stage_args: provisional tracers current level -> trProv[0] -> trProv[1] -> trProv[0]; the running content sum Qn lives in
+// the previous level's array, as New does, and stage 4 leaves the new tracers there (rk4_end swaps the levels).  Qc = phi * h of the
+// current level is formed on the fly by every stage that needs it (the same product, the same bits as a stored one).
+static hipError_t tracer_stage(moka_state *st, int s, const StageArgs &g)
+{
+    const moka_mesh *mm = st->mesh;
+    const Plan &p = mm->plan;
+    TracerArgs t{};
+    t.nT = st->nTracers; t.stage = s; t.stride = (int64_t)p.K * p.nC;
+    t.pu = g.pu; t.ph = g.ph; t.hcur = st->lev[1].h; t.hnext = s < 4 ? g.ph_out : g.nh_out;
+    t.pphi = s == 1 ? st->trPhi[1] : st->trProv[s == 3 ? 1 : 0];
+    t.pphi_out = s == 4 ? nullptr : st->trProv[s == 2 ? 1 : 0];
+    t.cphi = st->trPhi[1]; t.qn = st->trPhi[0];
+    t.a = g.a; t.b = g.b;
+    const MeshDev dev = launch_bounds(mm);
+    const bool generic = st->ctx->variant == 3;
+    st->tracerPath = tracer_kernel(dev, mm->lpc, t.nT, generic).form;
+    return launch_tracers(dev, t, mm->lpc, generic, st->ctx->stream);
+}
+
 extern "C" {
 
 int moka_state_rk4_streams(const moka_state *st) { return !st ? 0 : rk13_usable(st) ? 13 : 16; }
@@ -1441,7 +1467,9 @@ int moka_step_rk4(moka_state *st, double dt)
     const bool s13 = rk13_usable(st);
     for (int s = 1; s <= 4; ++s) {
         if (timed) HIPCHK(c, stamp());
-        HIPCHK(c, run_stage(st, s13 ? rk13_stage_args(st, s, dt, ssh0) : rk4_stage_args(st, s, dt, ssh0)));
+        const StageArgs g = s13 ? rk13_stage_args(st, s, dt, ssh0) : rk4_stage_args(st, s, dt, ssh0);
+        HIPCHK(c, run_stage(st, g));
+        if (st->nTracers > 0) HIPCHK(c, tracer_stage(st, s, g));
     }
     if (timed) HIPCHK(c, stamp());
     if (s13) rk13_end(st);
@@ -1681,6 +1709,70 @@ int moka_set_viscosity_del4(moka_state *st, double viscDel4, const double *meshS
 
 int moka_state_del4_path(const moka_state *st) { return st ? st->del4Path : 0; }
 
+int moka_set_tracers(moka_state *st, int32_t nTracers)
+{
+    if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
+    if (nTracers < 0) return fail(st->ctx, MOKA_ERR_ARG, "nTracers must be >= 0");
+    const Plan &p = st->mesh->plan;
+    if (nTracers > 0) {
+        if (st->f32) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "tracers: Float64 states only");
+        if (st->attached > 0 || st->halos > 0)
+            return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "tracers: not on a state with a halo or a tape");
+        if (p.nPatchesLaunch != p.nPatches) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "tracers: whole (unpartitioned) meshes only");
+    }
+    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));
+    double **arr[4] = {&st->trPhi[0], &st->trPhi[1], &st->trProv[0], &st->trProv[1]};
+    auto release = [&]() {
+        for (double **q : arr) {
+            if (!*q) continue;
+            st->allocs.erase(std::remove(st->allocs.begin(), st->allocs.end(), (void *)*q), st->allocs.end());
+            (void)hipFree(*q);
+            *q = nullptr;
+        }
+        st->nTracers = 0;
+        st->tracerPath = 0;
+    };
+    release();
+    if (nTracers == 0) return MOKA_OK;
+    for (double **q : arr)
+        if (int rc = alloc_field(st, q, (size_t)nTracers * p.K * p.nC)) {
+            (void)hipStreamSynchronize(st->ctx->stream);
+            release();
+            return rc;
+        }
+    HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));
+    st->nTracers = nTracers;
+    return MOKA_OK;
+}
+
+static int tracer_ref(moka_state *st, int32_t j, int time_level, const void *host, double **out)
+{
+    if (!st || !host) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    if (j < 0 || j >= st->nTracers) return fail(st->ctx, MOKA_ERR_ARG, "tracer index out of range (moka_set_tracers)");
+    if (time_level != 0 && time_level != 1) return fail(st->ctx, MOKA_ERR_ARG, "time_level must be 0 (previous) or 1 (current)");
+    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    const Plan &p = st->mesh->plan;
+    *out = st->trPhi[time_level] + (size_t)j * p.K * p.nC;
+    return MOKA_OK;
+}
+
+int moka_tracer_upload(moka_state *st, int32_t j, int time_level, const double *host)
+{
+    double *d = nullptr;
+    if (int rc = tracer_ref(st, j, time_level, host, &d)) return rc;
+    return put_rows(st->mesh, d, host, MOKA_CELL, st->mesh->plan.nC, st->mesh->plan.K);
+}
+
+int moka_tracer_download(moka_state *st, int32_t j, int time_level, double *host)
+{
+    double *d = nullptr;
+    if (int rc = tracer_ref(st, j, time_level, host, &d)) return rc;
+    return get_rows(st->mesh, host, d, MOKA_CELL, st->mesh->plan.nC, st->mesh->plan.K);
+}
+
+int moka_state_tracer_path(const moka_state *st) { return st ? st->tracerPath : 0; }
+
 // ---------------------------------------------------------------------------------------------
 // reverse mode of the Forward-Euler loop.  The reference differentiates
 // ocn_run_loop with Enzyme (ext/MPASEnzymeExt.jl; test/enzyme/test_Enzyme_end2end.jl: d sum(ssh^2) / d initial
@@ -1741,6 +1833,7 @@ int moka_tape_create(moka_state *st, int64_t capacity_steps, moka_tape **out)
     *out = nullptr;
     if (st->f32) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "reverse mode: Float64 states only");
     if (st->nonlinear) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "reverse mode covers the reference's linear terms only");
+    if (st->nTracers > 0) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "tracers: no reverse mode (moka_set_tracers(st, 0) first)");
     const Plan &p = st->mesh->plan;
     HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
     // transposed Coriolis stencil, sources sorted by (caller's edge id, slot): the oracle's summation order

@@ -183,6 +183,32 @@ int del4_path(const MeshDev &m, const D4Rows &r, int lpc, int form);
 hipError_t launch_del4(const MeshDev &m, const D4Rows &r, const double *divc, const double *zv, double *div4, double *curl4, int path,
                        hipStream_t s);
 
+// ---- passive tracers (moka_set_tracers; tracers.hip): one launch per RK4 stage behind the dycore's stage launch, all tracers ----
+// Arrays of nT tracers lie `stride` doubles apart.  With T the flux-form tendency of include/moka_hip.h, per tracer and element:
+//   Qc = cphi * hcur;  stage < 4: pphi_out = (Qc + a * T) / hnext;  Qn = (stage 1 ? Qc : qn) + b * T;  qn = stage 4 ? Qn / hnext : Qn
+struct TracerArgs {
+    int nT, stage;                // stage 1..4
+    int64_t stride;               // K * nC
+    const double *pu, *ph;        // the stage's provisional normalVelocity / layerThickness (gathered)
+    const double *hcur;           // the current level's layerThickness (stage 1: == ph)
+    const double *hnext;          // the next provisional layerThickness (stages 1-3) / the new level's (stage 4)
+    const double *pphi;           // the stage's provisional tracers (stage 1: the current level's; gathered)
+    const double *cphi;           // the current level's tracers
+    double *pphi_out;             // the next provisional tracers (stage 4: unused)
+    double *qn;                   // the running content sum: written by stage 1, read + written by 2 and 3; stage 4 leaves the new level's tracers there
+    double a, b;
+};
+// The kernel that serves a tracer launch, chosen in one place for the launcher and for moka_state_tracer_path.  form 1: k_tracer_patch
+// (even 34 <= K <= 64, hexagon-width byte-offset records, which exist only where every field's rows stay below 4 GiB; `chunk` tracers'
+// rows resident in `lds` bytes of dynamic LDS per pass), form 2: k_tracer_cell.  generic: the caller asks for form 2 (kernel variant 3).
+struct TracerKernel {
+    int form;
+    size_t lds;
+    int chunk;
+};
+TracerKernel tracer_kernel(const MeshDev &m, int lpc, int nT, bool generic);
+hipError_t launch_tracers(const MeshDev &m, const TracerArgs &a, int lpc, bool generic, hipStream_t s);
+
 // ---- reverse mode of one Forward-Euler step: gather form, the oracle's summation order ----
 struct AdjMesh {
     int32_t nC, nE, K, ME, W;          // W = width of the transposed Coriolis lists

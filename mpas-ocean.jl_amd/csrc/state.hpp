@@ -109,6 +109,12 @@ struct moka_state {
     double viscDel4 = 0.0;
     int del4Path = 0;                 // moka_state_del4_path
     int halos = 0;                    // live moka_halo objects on this state (Del4 refuses them)
+    // passive tracers (moka_set_tracers): nTracers arrays of (K, nC) doubles, K * nC apart, per buffer.  trPhi[] are the two time
+    // levels and swap with lev[] (during an RK4 step trPhi[0] carries the running content sum Qn, as lev[0] carries New); trProv[] are
+    // the provisional tracers beside rk[].  nullptr without tracers.
+    int nTracers = 0;
+    double *trPhi[2] = {nullptr, nullptr}, *trProv[2] = {nullptr, nullptr};
+    int tracerPath = 0;               // moka_state_tracer_path
     std::vector<void *> allocs;
     // objects that hold or have exported the addresses of this state's arrays (halos, tapes): while any exists the arrays stay
     // where they are (moka_state_optimize_placement refuses)

@@ -1,0 +1,274 @@
+// tracers.hip -- passive tracer transport beside the RK4 stages of libmoka_hip (gfx950; moka_set_tracers, NOT in the reference).
+#include "kernels_common.hpp"
+
+namespace moka {
+
+// ------------------------------------------------------------------------------------------------
+// Conservative flux form d(h phi)/dt = -div(F phi_e) with the thickness flux F = u * h_e of the thickness equation and the centred
+// edge value phi_e = (phi_c + phi_c') / 2.  Per cell c and level k the tendency accumulates from 0.0 over the slots of edgesOnCell
+// in slot order (empty slots and slots with k >= maxLevelEdgeTop of the edge skipped):
+//     hE = 0.5 * (ph[k,c] + ph[k,c']);  F = pu[k,e] * hE;  pE = 0.5 * (pphi[k,c] + pphi[k,c']);  T += ((F * pE) * sdv[c,i]) * invArea[c]
+// -- the thickness tendency of k_stage_nl with F * pE for F, so that a tracer that is 1 everywhere reproduces tendLayerThickness,
+// and then the provisional and the new thickness, bit for bit: it stays exactly 1.0.  One launch serves every tracer of the state:
+// F of a slot is formed once and reused by the tracer loop.  What a stage does with T: TracerArgs (kernels.hpp).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void tracer_update(const TracerArgs &a, double t, double cphi, double hcur, double hnext, double qnIn,
+                                              double &pOut, double &qOut)
+{
+    const double qc = cphi * hcur;
+    pOut = (qc + a.a * t) / hnext;
+    const double qn = (a.stage == 1 ? qc : qnIn) + a.b * t;
+    qOut = a.stage == 4 ? qn / hnext : qn;
+}
+
+constexpr int TR_TJ = 4;      // tracers whose sums a lane of k_tracer_cell carries at once (F is formed once per TR_TJ tracers)
+
+// Generic form: LPC lanes span a column, one cell per lane group, index records; any K, any maxEdges (the shape of k_nl_cell).
+template <int LPC>
+__global__ __launch_bounds__(BLOCK) void k_tracer_cell(const MeshDev m, const TracerArgs a)
+{
+    constexpr int NG = BLOCK / LPC;
+    const int grp = uniform_if_wave<LPC>(threadIdx.x / LPC), l = threadIdx.x % LPC;
+    const int K = m.K, ME = m.ME;
+    const bool s1 = a.stage == 1, s4 = a.stage == 4;
+    for (int c = blockIdx.x * NG + grp; c < m.nC; c += gridDim.x * NG) {
+        const double invA = cptr(m.invArea)[c];
+        for (int k = l; k < K; k += LPC) {
+            const size_t off = (size_t)c * K + k;
+            const double hc = a.ph[off], hnext = a.hnext[off], hcur = s4 ? 0.0 : a.hcur[off];
+            for (int j0 = 0; j0 < a.nT; j0 += TR_TJ) {
+                const int nj = min(TR_TJ, a.nT - j0);
+                double t[TR_TJ], pc[TR_TJ];
+#pragma unroll
+                for (int jj = 0; jj < TR_TJ; ++jj) {
+                    t[jj] = 0.0;
+                    pc[jj] = jj < nj ? a.pphi[(size_t)(j0 + jj) * a.stride + off] : 0.0;
+                }
+                for (int i = 0; i < ME; ++i) {
+                    const int e = cptr(m.eoc)[(size_t)c * ME + i];
+                    if (e < 0 || k >= cptr(m.mltc)[(size_t)c * ME + i]) continue;
+                    const size_t noff = (size_t)cptr(m.coc)[(size_t)c * ME + i] * K + k;
+                    const double hE = 0.5 * (hc + a.ph[noff]);
+                    const double F = a.pu[(size_t)e * K + k] * hE;
+                    const double sd = cptr(m.sdv)[(size_t)c * ME + i];
+#pragma unroll
+                    for (int jj = 0; jj < TR_TJ; ++jj)
+                        if (jj < nj) {
+                            const double pE = 0.5 * (pc[jj] + a.pphi[(size_t)(j0 + jj) * a.stride + noff]);
+                            t[jj] += ((F * pE) * sd) * invA;
+                        }
+                }
+#pragma unroll
+                for (int jj = 0; jj < TR_TJ; ++jj)
+                    if (jj < nj) {
+                        const size_t joff = (size_t)(j0 + jj) * a.stride + off;
+                        const double cphi = s1 ? pc[jj] : s4 ? 0.0 : a.cphi[joff];
+                        double pOut, qOut;
+                        tracer_update(a, t[jj], cphi, hcur, hnext, s1 ? 0.0 : a.qn[joff], pOut, qOut);
+                        if (!s4) a.pphi_out[joff] = pOut;
+                        a.qn[joff] = qOut;
+                    }
+            }
+        }
+    }
+}
+
+// Patch form (even 34 <= K <= 64, hexagon-width byte-offset records): one workgroup per patch, half a wave per cell, a lane owns levels
+// 2l and 2l + 1 (16 bytes).  The patch's cRec records, sdv, invArea and maxLevelEdgeTop entries and the ph and pphi rows of its own cells
+// are staged in LDS in one phase; a cell then reads its neighbours' cached rows in one burst of ds_read_b128 and overwrites the lanes
+// of foreign rows with exec-masked global loads by 32-bit byte offset (k_nl_prep5's row cache).  `chunk` tracers' rows are resident
+// at a time: a state with more takes further passes over the patch (the pphi rows re-staged, F re-formed once per pass).
+constexpr int TR_NT = 256;
+
+template <int ME_>
+__global__ __launch_bounds__(TR_NT, 2) void k_tracer_patch(const MeshDev m, const TracerArgs a, const int chunk)
+{
+    constexpr int NG = TR_NT / 32;
+    static_assert(ME_ == 6, "burst width");
+    extern __shared__ __align__(16) unsigned char tr_smem[];
+    const int tid = threadIdx.x, grp = tid >> 5, l = tid & 31, K = m.K, CI = m.CI, mC = m.maxOwnC;
+    const bool act = 2 * l < K;
+    const unsigned rowB = (unsigned)K * 8u, lo = (unsigned)l * 16u;
+    double *sRows = reinterpret_cast<double *>(tr_smem);                    // [1 + chunk][maxOwnC][K]  ph rows, then pphi rows per tracer
+    double *sSd = sRows + (size_t)(1 + chunk) * mC * K;                     // [maxOwnC][ME]  sdv
+    double *sIa = sSd + (size_t)mC * ME_;                                   // [maxOwnC]      invArea
+    uint32_t *sRec = reinterpret_cast<uint32_t *>(sIa + mC);                // [maxOwnC][CI]  cRec
+    int *sMl = reinterpret_cast<int *>(sRec + (size_t)mC * CI);             // [maxOwnC][ME]  maxLevelEdgeTop of the slot's edge
+    const int pl_ = patch_of_block(m.nPatches);
+    if (pl_ >= m.nPatches) return;
+    const int p = pl_ + m.patchBegin;
+    const int c0 = m.patchCellStart[p], nc = m.patchCellStart[p + 1] - c0;
+    const bool s1 = a.stage == 1, s4 = a.stage == 4;
+    const unsigned ownB = (unsigned)c0 * rowB, ownN = (unsigned)nc * rowB;
+    const glb_bytes_t uG = (glb_bytes_t)a.pu, hG = (glb_bytes_t)a.ph;
+    const uint32_t ldsH = (uint32_t)(size_t)sRows + lo;
+
+    // rows [rb * nc, (1 + cj) * nc) of the cache from global memory: row type 0 = ph, 1 + jj = tracer j0 + jj; eight in flight per half-wave
+    auto stage_rows = [&](int rb, int j0, int cj) {
+        if (!act) return;
+        const int nrows = (1 + cj) * nc;
+        for (int q0 = rb * nc + grp; q0 < nrows; q0 += 8 * NG) {
+            double2 v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int q = q0 + j * NG;
+                v[j] = make_double2(0.0, 0.0);
+                if (q < nrows) {
+                    const int ty = q / nc, ci = q - ty * nc;
+                    const double *src = ty == 0 ? a.ph : a.pphi + (size_t)(j0 + ty - 1) * a.stride;
+                    v[j] = *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(src) + (ownB + (unsigned)ci * rowB + lo));
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int q = q0 + j * NG;
+                if (q < nrows) {
+                    const int ty = q / nc, ci = q - ty * nc;
+                    reinterpret_cast<double2 *>(sRows + ((size_t)ty * mC + ci) * K)[l] = v[j];
+                }
+            }
+        }
+    };
+
+    {   // records: the first TR_NT entries of each list go through registers, so that every global load of the phase (rows included)
+        // is issued before the first LDS write; lists longer than that (large patch_cells) finish in plain loops
+        const int nRec = nc * CI, nSd = nc * ME_;
+        const uint32_t r0 = tid < nRec ? m.cRec[(size_t)c0 * CI + tid] : 0u;
+        const double sd0 = tid < nSd ? m.sdv[(size_t)c0 * ME_ + tid] : 0.0;
+        const int ml0 = tid < nSd ? m.mltc[(size_t)c0 * ME_ + tid] : 0;
+        const double ia0 = tid < nc ? m.invArea[c0 + tid] : 0.0;
+        stage_rows(0, 0, min(chunk, a.nT));
+        if (tid < nRec) sRec[tid] = r0;
+        if (tid < nSd) { sSd[tid] = sd0; sMl[tid] = ml0; }
+        if (tid < nc) sIa[tid] = ia0;
+        for (int i = tid + TR_NT; i < nRec; i += TR_NT) sRec[i] = m.cRec[(size_t)c0 * CI + i];
+        for (int i = tid + TR_NT; i < nSd; i += TR_NT) { sSd[i] = m.sdv[(size_t)c0 * ME_ + i]; sMl[i] = m.mltc[(size_t)c0 * ME_ + i]; }
+        for (int i = tid + TR_NT; i < nc; i += TR_NT) sIa[i] = m.invArea[c0 + i];
+    }
+    for (int j0 = 0; j0 < a.nT; j0 += chunk) {
+        const int cj = min(chunk, a.nT - j0);
+        if (j0 > 0) {
+            __syncthreads();                      // the previous pass has read its rows
+            stage_rows(1, j0, cj);
+        }
+        __syncthreads();
+        if (!act) continue;
+        for (int ci = grp; ci < nc; ci += NG) {
+            const uint32_t *rec = sRec + (size_t)ci * CI;
+            const unsigned mask = rec[2 * ME_];
+            double2 F[ME_];
+            bool ch[ME_], okx[ME_], oky[ME_];
+            uint32_t aoff[ME_], gh[ME_];
+            {
+                double2 uu[ME_];
+                uint32_t ah[ME_];
+                v4u_t rh[ME_];
+#pragma unroll
+                for (int i = 0; i < ME_; ++i) uu[i] = glb_row2(uG + (rec[i] + lo));
+#pragma unroll
+                for (int i = 0; i < ME_; ++i) {        // cached row or row 0 of the cache (then overwritten by the masked global load)
+                    const unsigned ho = rec[ME_ + i], loc = ho - ownB;
+                    ch[i] = loc < ownN;
+                    aoff[i] = ch[i] ? loc : 0u;
+                    gh[i] = ho + lo;
+                    asm("" : "+v"(gh[i]));             // the offset stays in a VGPR (see k_nl_prep5)
+                    ah[i] = ldsH + aoff[i];
+                }
+                lds_burst<ME_>(rh, ah);
+                const double2 hc = reinterpret_cast<const double2 *>(sRows + (size_t)ci * K)[l];
+#pragma unroll
+                for (int i = 0; i < ME_; ++i) {
+                    double2 hh = __builtin_bit_cast(double2, rh[i]);
+                    if (!ch[i]) hh = glb_row2(hG + gh[i]);
+                    F[i] = make_double2(uu[i].x * (0.5 * (hc.x + hh.x)), uu[i].y * (0.5 * (hc.y + hh.y)));   // Operators.jl:217, DiagnosticVars.jl:165
+                    const int ml = sMl[ci * ME_ + i];
+                    const bool valid = (mask >> i) & 1u;
+                    okx[i] = valid && 2 * l < ml;
+                    oky[i] = valid && 2 * l + 1 < ml;
+                }
+            }
+            const double *sd = sSd + ci * ME_;
+            const double invA = sIa[ci];
+            const unsigned orow = ownB + (unsigned)ci * rowB + lo;       // the cell's own row in every (K, nC) array
+            const double2 hcO = reinterpret_cast<const double2 *>(sRows + (size_t)ci * K)[l];
+            const double2 hnext = gload2(a.hnext, orow);
+            const double2 hcur = s1 ? hcO : s4 ? make_double2(0.0, 0.0) : gload2(a.hcur, orow);
+            for (int jj = 0; jj < cj; ++jj) {
+                const size_t jo = (size_t)(j0 + jj) * a.stride;
+                const glb_bytes_t pG = (glb_bytes_t)(a.pphi + jo);
+                const uint32_t ldsP = ldsH + (uint32_t)(1 + jj) * (uint32_t)mC * rowB;
+                uint32_t ap[ME_];
+                v4u_t rp[ME_];
+#pragma unroll
+                for (int i = 0; i < ME_; ++i) ap[i] = ldsP + aoff[i];
+                lds_burst<ME_>(rp, ap);
+                const double2 pc = reinterpret_cast<const double2 *>(sRows + ((size_t)(1 + jj) * mC + ci) * K)[l];
+                double2 t = make_double2(0.0, 0.0);
+                double2 pp[ME_];
+#pragma unroll
+                for (int i = 0; i < ME_; ++i) {
+                    pp[i] = __builtin_bit_cast(double2, rp[i]);
+                    if (!ch[i]) pp[i] = glb_row2(pG + gh[i]);
+                }
+#pragma unroll
+                for (int i = 0; i < ME_; ++i) {
+                    const double ex = 0.5 * (pc.x + pp[i].x), ey = 0.5 * (pc.y + pp[i].y);
+                    const double tx = t.x + ((F[i].x * ex) * sd[i]) * invA, ty = t.y + ((F[i].y * ey) * sd[i]) * invA;
+                    t.x = okx[i] ? tx : t.x;
+                    t.y = oky[i] ? ty : t.y;
+                }
+                const double2 cphi = s1 ? pc : s4 ? make_double2(0.0, 0.0) : gload2(a.cphi + jo, orow);
+                const double2 qnIn = s1 ? make_double2(0.0, 0.0) : gload2(a.qn + jo, orow);
+                double2 pOut, qOut;
+                tracer_update(a, t.x, cphi.x, hcur.x, hnext.x, qnIn.x, pOut.x, qOut.x);
+                tracer_update(a, t.y, cphi.y, hcur.y, hnext.y, qnIn.y, pOut.y, qOut.y);
+                if (!s4) gstore2(a.pphi_out + jo, orow, pOut);
+                gstore2(a.qn + jo, orow, qOut);
+            }
+        }
+    }
+}
+
+static inline size_t tracer_patch_lds(const MeshDev &m, int chunk)
+{
+    return (size_t)(1 + chunk) * m.maxOwnC * m.K * 8 + (size_t)m.maxOwnC * (m.ME + 1) * 8 + (size_t)m.maxOwnC * (m.CI + m.ME) * 4;
+}
+
+TracerKernel tracer_kernel(const MeshDev &m, int lpc, int nT, bool generic)
+{
+    if (!generic && lpc == 64 && m.K >= 34 && m.K <= 64 && !(m.K & 1) && m.ME == 6 && m.cRec && m.maxOwnC > 0) {
+        // as many tracers' rows resident as 80 KB hold (two workgroups per CU), at least one
+        const size_t budget = 80 * 1024, fixed = tracer_patch_lds(m, 0), perT = (size_t)m.maxOwnC * m.K * 8;
+        if (fixed + perT <= budget) {
+            const int chunk = (int)std::min<size_t>((size_t)std::max(nT, 1), (budget - fixed) / perT);
+            return {1, tracer_patch_lds(m, chunk), chunk};
+        }
+    }
+    return {2, 0, 0};
+}
+
+template <int LPC>
+static hipError_t launch_tracer_cell(const MeshDev &m, const TracerArgs &a, hipStream_t s)
+{
+    const int ng = BLOCK / LPC;
+    const int grid = std::min(std::max((m.nC + ng - 1) / ng, 1), 65536);
+    hipLaunchKernelGGL((k_tracer_cell<LPC>), dim3(grid), dim3(BLOCK), 0, s, m, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_tracers(const MeshDev &m, const TracerArgs &a, int lpc, bool generic, hipStream_t s)
+{
+    if (a.nT <= 0) return hipSuccess;
+    const TracerKernel k = tracer_kernel(m, lpc, a.nT, generic);
+    if (k.form == 1) {
+        if (k.lds > 64 * 1024)
+            if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_tracer_patch<6>)}, 80 * 1024); e != hipSuccess) return e;
+        hipLaunchKernelGGL((k_tracer_patch<6>), dim3(patch_grid(m)), dim3(TR_NT), k.lds, s, m, a, k.chunk);
+        return hipGetLastError();
+    }
+#define CALL(L) launch_tracer_cell<L>(m, a, s)
+    DISPATCH_LPC(lpc, CALL)
+#undef CALL
+}
+
+}  // namespace moka

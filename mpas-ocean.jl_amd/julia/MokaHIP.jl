@@ -454,6 +454,30 @@ function set_viscosity_del4!(Prog::MProg, viscDel4::Float64; meshScalingDel4::Un
                                              s.handle, viscDel4, sc), s.backend.ctx)
 end
 
+# Passive tracers (include/moka_hip.h states the algebra): centred flux-form transport by the thickness flux inside RK4 steps.
+# fields: (nVertLevels, nCells) matrices, uploaded into both time levels; an empty vector removes the tracers again.
+function set_tracers!(Prog::MProg, fields::Vector{Matrix{Float64}})
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    check(ccall((:moka_set_tracers, lib), Cint, (Ptr{Cvoid}, Int32), s.handle, length(fields)), s.backend.ctx)
+    for (j, a) in enumerate(fields), level in (0, 1)
+        check(ccall((:moka_tracer_upload, lib), Cint, (Ptr{Cvoid}, Int32, Cint, Ptr{Float64}), s.handle, j - 1, level, a), s.backend.ctx)
+    end
+end
+# tracer j (1-based) of the current (level = 1) or previous (level = 0) time level into `out`
+function tracer!(out::Matrix{Float64}, Prog::MProg, j::Integer; level::Integer = 1)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    check(ccall((:moka_tracer_download, lib), Cint, (Ptr{Cvoid}, Int32, Cint, Ptr{Float64}), s.handle, j - 1, level, out), s.backend.ctx)
+    out
+end
+# 1 the patch form, 2 the generic form of the tracer kernel served the last RK4 stage, 0 none yet
+function tracer_path(Prog::MProg)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    Int(ccall((:moka_state_tracer_path, lib), Cint, (Ptr{Cvoid},), s.handle))
+end
+
 # The opt-in 13-stream form of the RK4 step (moka_set_tuning key 7; include/moka_hip.h): the same Runge-Kutta step with another
 # round-off than time_integration.jl:134-135's running sum (<= 1e-12 relative per step), 12 % fewer bytes.  Process-wide;
 # rk4_streams tells which form the next step of a bound model takes (13, or 16 = the reference's).

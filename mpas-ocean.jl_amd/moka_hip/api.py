@@ -30,6 +30,7 @@ __all__ = [
     "Clock", "OneTimeAlarm", "PeriodicAlarm", "Alarm", "advance", "isRinging", "reset", "stop", "changeTimeStep",
     "attachAlarm", "setCurrentTime", "ocn_setup_clock", "ocn_setup_mesh", "ocn_init", "write_netcdf",
     "ConfigRead", "ConfigGet", "GlobalConfig", "AdjointTape", "set_nonlinear", "REFERENCE_COMPAT", "prognostic_vars_best_placement",
+    "set_tracers", "Tracers",
 ]
 
 MokaError = L.MokaError
@@ -591,6 +592,43 @@ def set_nonlinear(Prog: "PrognosticVars", on: bool = True, visc_del2: float = 0.
                 raise ValueError(f"mesh_scaling_del4: {sc.size} values for {nE} edges")
         L.check(L.lib().moka_set_viscosity_del4(Prog._state._h, float(visc_del4), None if sc is None else sc.ctypes.data),
                 Prog._state.mesh.backend._h)
+
+
+class Tracers:
+    """The passive tracers of a model (set_tracers): cell-centred (nCells, K) fields carried by every RK4 step."""
+
+    def __init__(self, state: "_State", n: int, shape):
+        self._s, self.n, self.shape = state, int(n), tuple(shape)
+
+    def get(self, j: int, level: int = -1) -> np.ndarray:
+        """Tracer j at time level `level` (0 = previous, -1 / 1 = current)."""
+        out = np.empty(self.shape, dtype=np.float64)
+        L.check(L.lib().moka_tracer_download(self._s._h, int(j), level % 2, L.f64(out)), self._s.mesh.backend._h)
+        return out
+
+    def set(self, j: int, a, level: int = -1):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape != self.shape:
+            a = a.reshape(self.shape)
+        L.check(L.lib().moka_tracer_upload(self._s._h, int(j), level % 2, L.f64(a)), self._s.mesh.backend._h)
+
+    def path(self) -> int:
+        """moka_state_tracer_path: 1 the patch form, 2 the generic form of the tracer kernel, 0 before the first RK4 step."""
+        return int(L.lib().moka_state_tracer_path(self._s._h))
+
+
+def set_tracers(Prog: "PrognosticVars", arrays) -> Tracers:
+    """Give this model passive tracers (moka_set_tracers): `arrays` is a list of (nCells, K) fields, uploaded into both time levels;
+    an empty list removes the tracers again.  An extension (the reference has none): centred flux-form transport by the thickness
+    flux inside RK4 steps (include/moka_hip.h states the algebra); Forward Euler, tapes and halos refuse a state with tracers."""
+    s = Prog._state
+    arrays = list(arrays)
+    L.check(L.lib().moka_set_tracers(s._h, len(arrays)), s.mesh.backend._h)
+    tr = Tracers(s, len(arrays), Prog.layerThickness[-1].shape)
+    for j, a in enumerate(arrays):
+        tr.set(j, a, 0)
+        tr.set(j, a, 1)
+    return tr
 
 
 # ---------------------------------------------------------------------------------------------
