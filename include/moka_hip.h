@@ -524,6 +524,16 @@ int  moka_state_del4_path(const moka_state *st);
  *   hE = 0.5 * (ph[k,c] + ph[k,c']);  F = pu[k,e] * hE;  pE = 0.5 * (pphi[k,c] + pphi[k,c']);
  *   T += ((F * pE) * (dvEdge[e] * edgeSignOnCell[i,c])) * (1/areaCell[c])
  * -- the thickness tendency with F * pE for F: a tracer that is 1 everywhere reproduces tendLayerThickness and stays exactly 1.0.
+ * Harmonic diffusion (moka_set_tracer_diffusion; default off).  With a diffusivity kappa_j >= 0 (m^2/s) per tracer the scheme is
+ *   d(h phi)/dt = -div(F phi_e) + div(kappa_j h_e grad phi).
+ * Per cell, level and slot the skip rules are those above, for both terms; after the advective addition of a slot a second,
+ * separate addition follows, with the slot's hE and one rounding per operation (no contraction):
+ *   G = pphi[k,c'] - pphi[k,c];  T += ((((kappa_j * hE) * G) * dvdc[c,i]) * (1/areaCell[c])),  dvdc[c,i] = dvEdge[e] / dcEdge[e]
+ * (dvdc: one double division when the mesh is created; unsigned, so both cells of an edge see the same value).  The RK4 recipe below
+ * is untouched: only T gains the term.  Hence: a constant tracer has G == 0 exactly and the unit tracer stays exactly 1.0 for any
+ * kappa; (kappa * hE) * G * dvdc is exactly antisymmetric between the two cells of an edge, so the content sum_c A_c sum_k phi h is
+ * conserved to round-off as by the advective flux; and adding +-0.0 never changes the bits of T (it starts at +0.0 and cannot become
+ * -0.0 under round-to-nearest), so a tracer with kappa_j == 0 beside diffused ones equals the undiffused result bit for bit.
  * One RK4 step, per tracer, with a = (dt/2, dt/2, dt), b = (dt/6, dt/3, dt/3, dt/6) and (pu_s, ph_s), ph_{s+1}, h_new the step's own
  * provisional and new states, whatever terms are switched on (linear, nonlinear, Del2, Del4):
  *   Qc = phi_cur * h_cur;  Qn = Qc;  pphi = phi_cur
@@ -538,8 +548,9 @@ int  moka_state_del4_path(const moka_state *st);
  * that have a halo or a tape.  While nTracers > 0, moka_step_fe, moka_run(MOKA_FORWARD_EULER), moka_tape_create, moka_halo_create and
  * the moka_rk4_dist_* calls return MOKA_ERR_UNSUPPORTED, and moka_set_tuning key 7 leaves the state on the running sum
  * (moka_state_rk4_streams: 16).  moka_state_optimize_placement neither times nor moves the tracer arrays.
- * Out of scope: upwind, FCT and higher-order edge values, tracer diffusion, Forward Euler, fp32 storage, partitioned meshes, reverse
- * mode, the 13-stream form, YAML keys and NetCDF I/O of tracers, and fusing the tracer sum into the dycore's stage kernels. */
+ * Out of scope: upwind, FCT and higher-order edge values, biharmonic, anisotropic or spatially varying tracer diffusion, Forward Euler,
+ * fp32 storage, partitioned meshes, reverse mode, the 13-stream form, YAML keys and NetCDF I/O of tracers, and fusing the tracer sum
+ * into the dycore's stage kernels. */
 int  moka_set_tracers(moka_state *st, int32_t nTracers);
 /* tracer j (0-based) at time_level 0 (previous) / 1 (current): (nVertLevels, nCells) doubles in the caller's cell numbering, like
  * layerThickness */
@@ -548,6 +559,15 @@ int  moka_tracer_download(moka_state *st, int32_t j, int time_level, double *hos
 /* which kernel served the last tracer stage of this state: 1 the patch form (even 34 <= nVertLevels <= 64, hexagon-width byte-offset
  * records, the default kernel choice), 2 the generic form (everything else, and kernel variant 3), 0 no tracer stage yet */
 int  moka_state_tracer_path(const moka_state *st);
+/* Harmonic tracer diffusion (algebra above).  kappa: nTracers diffusivities in m^2/s, NULL = all zero; the values take effect with
+ * the next RK4 step or moka_run.  MOKA_ERR_ARG, with nothing changed, for a negative, NaN or infinite value and for a non-NULL kappa
+ * on a state without tracers.  While every value is zero the tracer launches are those of a state that never set a diffusivity.
+ * moka_set_tracers (any count, 0 included) resets every diffusivity to zero.  The explicit stability limit is not checked (as for
+ * visc_del2).  Rule of thumb: RK4 is stable on the negative real axis down to about -2.78 and the largest eigenvalue of the hexagon
+ * Laplacian is about 8 / dcEdge^2, so kappa dt / dcEdge_min^2 <~ 0.35.  Tracers still never feed back. */
+int  moka_set_tracer_diffusion(moka_state *st, const double *kappa);
+/* the diffusivity of tracer j (0-based) into *out; MOKA_ERR_ARG for j out of range */
+int  moka_tracer_diffusion(const moka_state *st, int32_t j, double *out);
 
 /* ---- reverse mode of the Forward-Euler loop ----------------------------------------------------------------
  * The reference gets d sum(ssh^2) / d (initial normalVelocity, layerThickness) from Enzyme over ocn_run_loop

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <atomic>
 #include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1435,9 +1436,10 @@ static hipError_t tracer_stage(moka_state *st, int s, const StageArgs &g)
     t.pphi_out = s == 4 ? nullptr : st->trProv[s == 2 ? 1 : 0];
     t.cphi = st->trPhi[1]; t.qn = st->trPhi[0];
     t.a = g.a; t.b = g.b;
+    t.kappa = st->trKappaDev; t.dvdc = st->trKappaDev ? mm->dvdc : nullptr;
     const MeshDev dev = launch_bounds(mm);
     const bool generic = st->ctx->variant == 3;
-    st->tracerPath = tracer_kernel(dev, mm->lpc, t.nT, generic).form;
+    st->tracerPath = tracer_kernel(dev, mm->lpc, t.nT, generic, t.kappa != nullptr).form;
     return launch_tracers(dev, t, mm->lpc, generic, st->ctx->stream);
 }
 
@@ -1722,7 +1724,7 @@ int moka_set_tracers(moka_state *st, int32_t nTracers)
     }
     HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
     HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));
-    double **arr[4] = {&st->trPhi[0], &st->trPhi[1], &st->trProv[0], &st->trProv[1]};
+    double **arr[5] = {&st->trPhi[0], &st->trPhi[1], &st->trProv[0], &st->trProv[1], &st->trKappaDev};
     auto release = [&]() {
         for (double **q : arr) {
             if (!*q) continue;
@@ -1732,11 +1734,13 @@ int moka_set_tracers(moka_state *st, int32_t nTracers)
         }
         st->nTracers = 0;
         st->tracerPath = 0;
+        st->trKappa.clear();             // every diffusivity back to zero
     };
     release();
     if (nTracers == 0) return MOKA_OK;
     for (double **q : arr)
-        if (int rc = alloc_field(st, q, (size_t)nTracers * p.K * p.nC)) {
+        if (q == &st->trKappaDev) continue;      // allocated by moka_set_tracer_diffusion
+        else if (int rc = alloc_field(st, q, (size_t)nTracers * p.K * p.nC)) {
             (void)hipStreamSynchronize(st->ctx->stream);
             release();
             return rc;
@@ -1772,6 +1776,46 @@ int moka_tracer_download(moka_state *st, int32_t j, int time_level, double *host
 }
 
 int moka_state_tracer_path(const moka_state *st) { return st ? st->tracerPath : 0; }
+
+int moka_set_tracer_diffusion(moka_state *st, const double *kappa)
+{
+    if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
+    const int nT = st->nTracers;
+    if (kappa && nT == 0) return fail(st->ctx, MOKA_ERR_ARG, "tracer diffusion: the state has no tracers (moka_set_tracers)");
+    bool any = false;
+    for (int j = 0; kappa && j < nT; ++j) {
+        if (!(kappa[j] >= 0.0) || !std::isfinite(kappa[j]))
+            return fail(st->ctx, MOKA_ERR_ARG, "tracer diffusion: every diffusivity must be finite and >= 0");
+        any = any || kappa[j] != 0.0;
+    }
+    moka_mesh *mm = st->mesh;
+    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));      // no launch is reading the old values
+    if (!any) {
+        if (st->trKappaDev) {
+            st->allocs.erase(std::remove(st->allocs.begin(), st->allocs.end(), (void *)st->trKappaDev), st->allocs.end());
+            (void)hipFree(st->trKappaDev);
+            st->trKappaDev = nullptr;
+        }
+        st->trKappa.clear();
+        return MOKA_OK;
+    }
+    if (!mm->dvdc)
+        if (int rc = upload_vec(mm, mm->plan.dvdc, &mm->dvdc)) return rc;
+    if (!st->trKappaDev)
+        if (int rc = alloc_field(st, &st->trKappaDev, (size_t)nT)) return rc;
+    if (int rc = h2d(st->ctx, st->trKappaDev, kappa, (size_t)nT * sizeof(double))) return rc;
+    st->trKappa.assign(kappa, kappa + nT);
+    return MOKA_OK;
+}
+
+int moka_tracer_diffusion(const moka_state *st, int32_t j, double *out)
+{
+    if (!st || !out) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    if (j < 0 || j >= st->nTracers) return fail(st->ctx, MOKA_ERR_ARG, "tracer index out of range (moka_set_tracers)");
+    *out = st->trKappa.empty() ? 0.0 : st->trKappa[j];
+    return MOKA_OK;
+}
 
 // ---------------------------------------------------------------------------------------------
 // reverse mode of the Forward-Euler loop.  The reference differentiates

@@ -197,16 +197,20 @@ struct TracerArgs {
     double *pphi_out;             // the next provisional tracers (stage 4: unused)
     double *qn;                   // the running content sum: written by stage 1, read + written by 2 and 3; stage 4 leaves the new level's tracers there
     double a, b;
+    // harmonic diffusion (moka_set_tracer_diffusion): nT diffusivities and the plan's (nC, ME) dvEdge / dcEdge per slot; both nullptr
+    // while every diffusivity of the state is zero (the launch is then the one of a state that never set any)
+    const double *kappa, *dvdc;
 };
 // The kernel that serves a tracer launch, chosen in one place for the launcher and for moka_state_tracer_path.  form 1: k_tracer_patch
 // (even 34 <= K <= 64, hexagon-width byte-offset records, which exist only where every field's rows stay below 4 GiB; `chunk` tracers'
 // rows resident in `lds` bytes of dynamic LDS per pass), form 2: k_tracer_cell.  generic: the caller asks for form 2 (kernel variant 3).
+// diff: the DIFF instantiations (the patch form then stages dvdc too: more LDS, possibly a smaller chunk).
 struct TracerKernel {
     int form;
     size_t lds;
     int chunk;
 };
-TracerKernel tracer_kernel(const MeshDev &m, int lpc, int nT, bool generic);
+TracerKernel tracer_kernel(const MeshDev &m, int lpc, int nT, bool generic, bool diff);
 hipError_t launch_tracers(const MeshDev &m, const TracerArgs &a, int lpc, bool generic, hipStream_t s);
 
 // ---- reverse mode of one Forward-Euler step: gather form, the oracle's summation order ----

@@ -402,6 +402,7 @@ int build_plan(const moka_mesh_desc *d, Plan &p)
     p.coc.assign((size_t)nC * ME, -1);
     p.mltc.assign((size_t)nC * ME, 0);
     p.sdv.assign((size_t)nC * ME, 0.0);
+    p.dvdc.assign((size_t)nC * ME, 0.0);
     p.invArea.resize(nC); p.areaCell.resize(nC); p.rsum.resize(nC);
     p.cellBandwidth = 0;
     for (int cn = 0; cn < nC; ++cn) {
@@ -416,6 +417,7 @@ int build_plan(const moka_mesh_desc *d, Plan &p)
             p.coc[IX(i, cn, ME)] = p.cellO2N[other];
             p.mltc[IX(i, cn, ME)] = d->maxLevelEdgeTop ? d->maxLevelEdgeTop[eo] : 1;
             p.sdv[IX(i, cn, ME)] = d->dvEdge[eo] * (double)d->edgeSignOnCell[IX(i, co, d->maxEdges)];
+            p.dvdc[IX(i, cn, ME)] = d->dvEdge[eo] / d->dcEdge[eo];
             p.cellBandwidth = std::max<int64_t>(p.cellBandwidth, std::abs((int64_t)p.cellO2N[other] - cn));
         }
         p.invArea[cn] = 1. / d->areaCell[co];

@@ -49,6 +49,7 @@ struct moka_mesh {
     // (maxOwnE, maxOwnC) of a launched patch sub-range: a partition's halo-only patches own up to 6 edges per cell
     // and are never launched, so the LDS carve of a boundary / interior launch is sized by the patches it covers
     std::map<std::pair<int, int>, std::pair<int, int>> rangeMax;
+    const double *dvdc = nullptr;         // plan.dvdc on the device, uploaded by the first moka_set_tracer_diffusion with a nonzero value
     moka::D4Rows d4{};        // Del4 mixing: per-patch edge rows of k_d4_patch, built at the first moka_set_viscosity_del4 (start == nullptr: not yet)
 };
 
@@ -115,6 +116,10 @@ struct moka_state {
     int nTracers = 0;
     double *trPhi[2] = {nullptr, nullptr}, *trProv[2] = {nullptr, nullptr};
     int tracerPath = 0;               // moka_state_tracer_path
+    // harmonic tracer diffusion (moka_set_tracer_diffusion): the host copy (nTracers values, empty = all zero) and the device array the
+    // tracer launches read -- nullptr while every value is zero: the launches are then those of a state that never set any
+    std::vector<double> trKappa;
+    double *trKappaDev = nullptr;
     std::vector<void *> allocs;
     // objects that hold or have exported the addresses of this state's arrays (halos, tapes): while any exists the arrays stay
     // where they are (moka_state_optimize_placement refuses)

@@ -11,6 +11,11 @@ namespace moka {
 // -- the thickness tendency of k_stage_nl with F * pE for F, so that a tracer that is 1 everywhere reproduces tendLayerThickness,
 // and then the provisional and the new thickness, bit for bit: it stays exactly 1.0.  One launch serves every tracer of the state:
 // F of a slot is formed once and reused by the tracer loop.  What a stage does with T: TracerArgs (kernels.hpp).
+// DIFF (moka_set_tracer_diffusion: some kappa_j != 0) adds the harmonic term div(kappa_j h_e grad phi): after the advective addition
+// of a slot, a second, separate one,
+//     G = pphi[k,c'] - pphi[k,c];  T += ((((kappa[j] * hE) * G) * dvdc[c,i]) * invArea[c]),   dvdc = dvEdge[e] / dcEdge[e] (plan.cpp)
+// -- G == 0 for a constant tracer, the product antisymmetric between the two cells of an edge, and +-0.0 for kappa[j] == 0, which
+// leaves the bits of T alone.  DIFF == false is the code of a state that never set a diffusivity.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void tracer_update(const TracerArgs &a, double t, double cphi, double hcur, double hnext, double qnIn,
                                               double &pOut, double &qOut)
@@ -24,7 +29,7 @@ __device__ __forceinline__ void tracer_update(const TracerArgs &a, double t, dou
 constexpr int TR_TJ = 4;      // tracers whose sums a lane of k_tracer_cell carries at once (F is formed once per TR_TJ tracers)
 
 // Generic form: LPC lanes span a column, one cell per lane group, index records; any K, any maxEdges (the shape of k_nl_cell).
-template <int LPC>
+template <int LPC, bool DIFF>
 __global__ __launch_bounds__(BLOCK) void k_tracer_cell(const MeshDev m, const TracerArgs a)
 {
     constexpr int NG = BLOCK / LPC;
@@ -38,11 +43,12 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_cell(const MeshDev m, const Tr
             const double hc = a.ph[off], hnext = a.hnext[off], hcur = s4 ? 0.0 : a.hcur[off];
             for (int j0 = 0; j0 < a.nT; j0 += TR_TJ) {
                 const int nj = min(TR_TJ, a.nT - j0);
-                double t[TR_TJ], pc[TR_TJ];
+                double t[TR_TJ], pc[TR_TJ], kap[TR_TJ];
 #pragma unroll
                 for (int jj = 0; jj < TR_TJ; ++jj) {
                     t[jj] = 0.0;
                     pc[jj] = jj < nj ? a.pphi[(size_t)(j0 + jj) * a.stride + off] : 0.0;
+                    kap[jj] = DIFF && jj < nj ? cptr(a.kappa)[j0 + jj] : 0.0;
                 }
                 for (int i = 0; i < ME; ++i) {
                     const int e = cptr(m.eoc)[(size_t)c * ME + i];
@@ -51,11 +57,14 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_cell(const MeshDev m, const Tr
                     const double hE = 0.5 * (hc + a.ph[noff]);
                     const double F = a.pu[(size_t)e * K + k] * hE;
                     const double sd = cptr(m.sdv)[(size_t)c * ME + i];
+                    const double dd = DIFF ? cptr(a.dvdc)[(size_t)c * ME + i] : 0.0;
 #pragma unroll
                     for (int jj = 0; jj < TR_TJ; ++jj)
                         if (jj < nj) {
-                            const double pE = 0.5 * (pc[jj] + a.pphi[(size_t)(j0 + jj) * a.stride + noff]);
+                            const double pn = a.pphi[(size_t)(j0 + jj) * a.stride + noff];
+                            const double pE = 0.5 * (pc[jj] + pn);
                             t[jj] += ((F * pE) * sd) * invA;
+                            if (DIFF) t[jj] += (((kap[jj] * hE) * (pn - pc[jj])) * dd) * invA;
                         }
                 }
 #pragma unroll
@@ -78,9 +87,10 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_cell(const MeshDev m, const Tr
 // are staged in LDS in one phase; a cell then reads its neighbours' cached rows in one burst of ds_read_b128 and overwrites the lanes
 // of foreign rows with exec-masked global loads by 32-bit byte offset (k_nl_prep5's row cache).  `chunk` tracers' rows are resident
 // at a time: a state with more takes further passes over the patch (the pphi rows re-staged, F re-formed once per pass).
+// DIFF: the patch's dvdc entries are staged beside sdv, and a cell keeps hE of its slots beside F.
 constexpr int TR_NT = 256;
 
-template <int ME_>
+template <int ME_, bool DIFF>
 __global__ __launch_bounds__(TR_NT, 2) void k_tracer_patch(const MeshDev m, const TracerArgs a, const int chunk)
 {
     constexpr int NG = TR_NT / 32;
@@ -91,7 +101,8 @@ __global__ __launch_bounds__(TR_NT, 2) void k_tracer_patch(const MeshDev m, cons
     const unsigned rowB = (unsigned)K * 8u, lo = (unsigned)l * 16u;
     double *sRows = reinterpret_cast<double *>(tr_smem);                    // [1 + chunk][maxOwnC][K]  ph rows, then pphi rows per tracer
     double *sSd = sRows + (size_t)(1 + chunk) * mC * K;                     // [maxOwnC][ME]  sdv
-    double *sIa = sSd + (size_t)mC * ME_;                                   // [maxOwnC]      invArea
+    double *sDd = sSd + (size_t)mC * ME_;                                   // [maxOwnC][ME]  dvdc (DIFF only)
+    double *sIa = sDd + (DIFF ? (size_t)mC * ME_ : 0);                      // [maxOwnC]      invArea
     uint32_t *sRec = reinterpret_cast<uint32_t *>(sIa + mC);                // [maxOwnC][CI]  cRec
     int *sMl = reinterpret_cast<int *>(sRec + (size_t)mC * CI);             // [maxOwnC][ME]  maxLevelEdgeTop of the slot's edge
     const int pl_ = patch_of_block(m.nPatches);
@@ -135,14 +146,18 @@ __global__ __launch_bounds__(TR_NT, 2) void k_tracer_patch(const MeshDev m, cons
         const int nRec = nc * CI, nSd = nc * ME_;
         const uint32_t r0 = tid < nRec ? m.cRec[(size_t)c0 * CI + tid] : 0u;
         const double sd0 = tid < nSd ? m.sdv[(size_t)c0 * ME_ + tid] : 0.0;
+        const double dd0 = DIFF && tid < nSd ? a.dvdc[(size_t)c0 * ME_ + tid] : 0.0;
         const int ml0 = tid < nSd ? m.mltc[(size_t)c0 * ME_ + tid] : 0;
         const double ia0 = tid < nc ? m.invArea[c0 + tid] : 0.0;
         stage_rows(0, 0, min(chunk, a.nT));
         if (tid < nRec) sRec[tid] = r0;
         if (tid < nSd) { sSd[tid] = sd0; sMl[tid] = ml0; }
+        if (DIFF && tid < nSd) sDd[tid] = dd0;
         if (tid < nc) sIa[tid] = ia0;
         for (int i = tid + TR_NT; i < nRec; i += TR_NT) sRec[i] = m.cRec[(size_t)c0 * CI + i];
         for (int i = tid + TR_NT; i < nSd; i += TR_NT) { sSd[i] = m.sdv[(size_t)c0 * ME_ + i]; sMl[i] = m.mltc[(size_t)c0 * ME_ + i]; }
+        if (DIFF)
+            for (int i = tid + TR_NT; i < nSd; i += TR_NT) sDd[i] = a.dvdc[(size_t)c0 * ME_ + i];
         for (int i = tid + TR_NT; i < nc; i += TR_NT) sIa[i] = m.invArea[c0 + i];
     }
     for (int j0 = 0; j0 < a.nT; j0 += chunk) {
@@ -156,7 +171,7 @@ __global__ __launch_bounds__(TR_NT, 2) void k_tracer_patch(const MeshDev m, cons
         for (int ci = grp; ci < nc; ci += NG) {
             const uint32_t *rec = sRec + (size_t)ci * CI;
             const unsigned mask = rec[2 * ME_];
-            double2 F[ME_];
+            double2 F[ME_], hE[DIFF ? ME_ : 1];
             bool ch[ME_], okx[ME_], oky[ME_];
             uint32_t aoff[ME_], gh[ME_];
             {
@@ -180,14 +195,16 @@ __global__ __launch_bounds__(TR_NT, 2) void k_tracer_patch(const MeshDev m, cons
                 for (int i = 0; i < ME_; ++i) {
                     double2 hh = __builtin_bit_cast(double2, rh[i]);
                     if (!ch[i]) hh = glb_row2(hG + gh[i]);
-                    F[i] = make_double2(uu[i].x * (0.5 * (hc.x + hh.x)), uu[i].y * (0.5 * (hc.y + hh.y)));   // Operators.jl:217, DiagnosticVars.jl:165
+                    const double2 he = make_double2(0.5 * (hc.x + hh.x), 0.5 * (hc.y + hh.y));
+                    F[i] = make_double2(uu[i].x * he.x, uu[i].y * he.y);   // Operators.jl:217, DiagnosticVars.jl:165
+                    if (DIFF) hE[i] = he;
                     const int ml = sMl[ci * ME_ + i];
                     const bool valid = (mask >> i) & 1u;
                     okx[i] = valid && 2 * l < ml;
                     oky[i] = valid && 2 * l + 1 < ml;
                 }
             }
-            const double *sd = sSd + ci * ME_;
+            const double *sd = sSd + ci * ME_, *dd = sDd + ci * ME_;
             const double invA = sIa[ci];
             const unsigned orow = ownB + (unsigned)ci * rowB + lo;       // the cell's own row in every (K, nC) array
             const double2 hcO = reinterpret_cast<const double2 *>(sRows + (size_t)ci * K)[l];
@@ -195,6 +212,7 @@ __global__ __launch_bounds__(TR_NT, 2) void k_tracer_patch(const MeshDev m, cons
             const double2 hcur = s1 ? hcO : s4 ? make_double2(0.0, 0.0) : gload2(a.hcur, orow);
             for (int jj = 0; jj < cj; ++jj) {
                 const size_t jo = (size_t)(j0 + jj) * a.stride;
+                const double kap = DIFF ? a.kappa[j0 + jj] : 0.0;
                 const glb_bytes_t pG = (glb_bytes_t)(a.pphi + jo);
                 const uint32_t ldsP = ldsH + (uint32_t)(1 + jj) * (uint32_t)mC * rowB;
                 uint32_t ap[ME_];
@@ -213,7 +231,11 @@ __global__ __launch_bounds__(TR_NT, 2) void k_tracer_patch(const MeshDev m, cons
 #pragma unroll
                 for (int i = 0; i < ME_; ++i) {
                     const double ex = 0.5 * (pc.x + pp[i].x), ey = 0.5 * (pc.y + pp[i].y);
-                    const double tx = t.x + ((F[i].x * ex) * sd[i]) * invA, ty = t.y + ((F[i].y * ey) * sd[i]) * invA;
+                    double tx = t.x + ((F[i].x * ex) * sd[i]) * invA, ty = t.y + ((F[i].y * ey) * sd[i]) * invA;
+                    if (DIFF) {
+                        tx += (((kap * hE[i].x) * (pp[i].x - pc.x)) * dd[i]) * invA;
+                        ty += (((kap * hE[i].y) * (pp[i].y - pc.y)) * dd[i]) * invA;
+                    }
                     t.x = okx[i] ? tx : t.x;
                     t.y = oky[i] ? ty : t.y;
                 }
@@ -229,46 +251,58 @@ __global__ __launch_bounds__(TR_NT, 2) void k_tracer_patch(const MeshDev m, cons
     }
 }
 
-static inline size_t tracer_patch_lds(const MeshDev &m, int chunk)
+static inline size_t tracer_patch_lds(const MeshDev &m, int chunk, bool diff)
 {
-    return (size_t)(1 + chunk) * m.maxOwnC * m.K * 8 + (size_t)m.maxOwnC * (m.ME + 1) * 8 + (size_t)m.maxOwnC * (m.CI + m.ME) * 4;
+    return (size_t)(1 + chunk) * m.maxOwnC * m.K * 8 + (size_t)m.maxOwnC * (m.ME + 1) * 8 + (size_t)m.maxOwnC * (m.CI + m.ME) * 4 +
+           (diff ? (size_t)m.maxOwnC * m.ME * 8 : 0);
 }
 
-TracerKernel tracer_kernel(const MeshDev &m, int lpc, int nT, bool generic)
+TracerKernel tracer_kernel(const MeshDev &m, int lpc, int nT, bool generic, bool diff)
 {
     if (!generic && lpc == 64 && m.K >= 34 && m.K <= 64 && !(m.K & 1) && m.ME == 6 && m.cRec && m.maxOwnC > 0) {
         // as many tracers' rows resident as 80 KB hold (two workgroups per CU), at least one
-        const size_t budget = 80 * 1024, fixed = tracer_patch_lds(m, 0), perT = (size_t)m.maxOwnC * m.K * 8;
+        const size_t budget = 80 * 1024, fixed = tracer_patch_lds(m, 0, diff), perT = (size_t)m.maxOwnC * m.K * 8;
         if (fixed + perT <= budget) {
             const int chunk = (int)std::min<size_t>((size_t)std::max(nT, 1), (budget - fixed) / perT);
-            return {1, tracer_patch_lds(m, chunk), chunk};
+            return {1, tracer_patch_lds(m, chunk, diff), chunk};
         }
     }
     return {2, 0, 0};
 }
 
-template <int LPC>
+template <int LPC, bool DIFF>
 static hipError_t launch_tracer_cell(const MeshDev &m, const TracerArgs &a, hipStream_t s)
 {
     const int ng = BLOCK / LPC;
     const int grid = std::min(std::max((m.nC + ng - 1) / ng, 1), 65536);
-    hipLaunchKernelGGL((k_tracer_cell<LPC>), dim3(grid), dim3(BLOCK), 0, s, m, a);
+    hipLaunchKernelGGL((k_tracer_cell<LPC, DIFF>), dim3(grid), dim3(BLOCK), 0, s, m, a);
     return hipGetLastError();
+}
+
+template <bool DIFF>
+static hipError_t launch_tracer_patch(const MeshDev &m, const TracerArgs &a, const TracerKernel &k, hipStream_t s)
+{
+    if (k.lds > 64 * 1024)
+        if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_tracer_patch<6, DIFF>)}, 80 * 1024); e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_tracer_patch<6, DIFF>), dim3(patch_grid(m)), dim3(TR_NT), k.lds, s, m, a, k.chunk);
+    return hipGetLastError();
+}
+
+template <bool DIFF>
+static hipError_t launch_tracer_generic(const MeshDev &m, const TracerArgs &a, int lpc, hipStream_t s)
+{
+#define CALL(L) launch_tracer_cell<L, DIFF>(m, a, s)
+    DISPATCH_LPC(lpc, CALL)
+#undef CALL
 }
 
 hipError_t launch_tracers(const MeshDev &m, const TracerArgs &a, int lpc, bool generic, hipStream_t s)
 {
     if (a.nT <= 0) return hipSuccess;
-    const TracerKernel k = tracer_kernel(m, lpc, a.nT, generic);
-    if (k.form == 1) {
-        if (k.lds > 64 * 1024)
-            if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_tracer_patch<6>)}, 80 * 1024); e != hipSuccess) return e;
-        hipLaunchKernelGGL((k_tracer_patch<6>), dim3(patch_grid(m)), dim3(TR_NT), k.lds, s, m, a, k.chunk);
-        return hipGetLastError();
-    }
-#define CALL(L) launch_tracer_cell<L>(m, a, s)
-    DISPATCH_LPC(lpc, CALL)
-#undef CALL
+    const bool diff = a.kappa != nullptr;       // (then a.dvdc is set too: tracer_stage)
+    const TracerKernel k = tracer_kernel(m, lpc, a.nT, generic, diff);
+    if (k.form == 1) return diff ? launch_tracer_patch<true>(m, a, k, s) : launch_tracer_patch<false>(m, a, k, s);
+    return diff ? launch_tracer_generic<true>(m, a, lpc, s) : launch_tracer_generic<false>(m, a, lpc, s);
 }
 
 }  // namespace moka

@@ -456,13 +456,28 @@ end
 
 # Passive tracers (include/moka_hip.h states the algebra): centred flux-form transport by the thickness flux inside RK4 steps.
 # fields: (nVertLevels, nCells) matrices, uploaded into both time levels; an empty vector removes the tracers again.
-function set_tracers!(Prog::MProg, fields::Vector{Matrix{Float64}})
+# diffusivity: harmonic diffusion div(kappa h_e grad phi) beside the transport -- one value (m^2/s, >= 0) for all tracers or one per
+# tracer; nothing leaves them undiffused.  The explicit stability limit (kappa dt / dcEdge_min^2 <~ 0.35) is not checked.
+function set_tracers!(Prog::MProg, fields::Vector{Matrix{Float64}}; diffusivity = nothing)
     s = Prog.ssh[end].state
     s === nothing && error("MokaHIP: the model is not on the device yet")
     check(ccall((:moka_set_tracers, lib), Cint, (Ptr{Cvoid}, Int32), s.handle, length(fields)), s.backend.ctx)
     for (j, a) in enumerate(fields), level in (0, 1)
         check(ccall((:moka_tracer_upload, lib), Cint, (Ptr{Cvoid}, Int32, Cint, Ptr{Float64}), s.handle, j - 1, level, a), s.backend.ctx)
     end
+    if diffusivity !== nothing
+        kappa = diffusivity isa Number ? fill(Float64(diffusivity), length(fields)) : Vector{Float64}(diffusivity)
+        length(kappa) == length(fields) || error("MokaHIP: $(length(kappa)) diffusivities for $(length(fields)) tracers")
+        check(ccall((:moka_set_tracer_diffusion, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), s.handle, kappa), s.backend.ctx)
+    end
+end
+# the diffusivity of tracer j (1-based), 0.0 unless set_tracers! was given one
+function tracer_diffusivity(Prog::MProg, j::Integer)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    out = Ref{Float64}(0.0)
+    check(ccall((:moka_tracer_diffusion, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), s.handle, j - 1, out), s.backend.ctx)
+    out[]
 end
 # tracer j (1-based) of the current (level = 1) or previous (level = 0) time level into `out`
 function tracer!(out::Matrix{Float64}, Prog::MProg, j::Integer; level::Integer = 1)

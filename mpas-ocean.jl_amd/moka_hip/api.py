@@ -616,11 +616,35 @@ class Tracers:
         """moka_state_tracer_path: 1 the patch form, 2 the generic form of the tracer kernel, 0 before the first RK4 step."""
         return int(L.lib().moka_state_tracer_path(self._s._h))
 
+    def set_diffusivity(self, values):
+        """moka_set_tracer_diffusion: harmonic diffusion div(kappa h_e grad phi) beside the transport.  `values`: one diffusivity
+        (m^2/s, finite, >= 0) for every tracer or one per tracer; None or 0 switches diffusion off.  Takes effect with the next RK4
+        step or run.  The explicit stability limit (kappa dt / dcEdge_min^2 <~ 0.35) is not checked."""
+        k = None
+        if values is not None:
+            k = np.asarray(values, dtype=np.float64)
+            k = np.full(self.n, float(k)) if k.ndim == 0 else np.ascontiguousarray(k.ravel())
+            if k.size != self.n:
+                raise ValueError(f"diffusivity: {k.size} values for {self.n} tracers")
+        if k is not None and self.n == 0 and not k.size:
+            k = None
+        L.check(L.lib().moka_set_tracer_diffusion(self._s._h, None if k is None else k.ctypes.data), self._s.mesh.backend._h)
 
-def set_tracers(Prog: "PrognosticVars", arrays) -> Tracers:
+    def diffusivity(self) -> np.ndarray:
+        """moka_tracer_diffusion: the diffusivity of every tracer (zeros unless set_diffusivity was called)."""
+        out = np.zeros(self.n, dtype=np.float64)
+        v = C.c_double()
+        for j in range(self.n):
+            L.check(L.lib().moka_tracer_diffusion(self._s._h, j, C.byref(v)), self._s.mesh.backend._h)
+            out[j] = v.value
+        return out
+
+
+def set_tracers(Prog: "PrognosticVars", arrays, diffusivity=None) -> Tracers:
     """Give this model passive tracers (moka_set_tracers): `arrays` is a list of (nCells, K) fields, uploaded into both time levels;
     an empty list removes the tracers again.  An extension (the reference has none): centred flux-form transport by the thickness
-    flux inside RK4 steps (include/moka_hip.h states the algebra); Forward Euler, tapes and halos refuse a state with tracers."""
+    flux inside RK4 steps (include/moka_hip.h states the algebra); Forward Euler, tapes and halos refuse a state with tracers.
+    diffusivity: a scalar or one value per tracer (Tracers.set_diffusivity); None leaves the tracers undiffused."""
     s = Prog._state
     arrays = list(arrays)
     L.check(L.lib().moka_set_tracers(s._h, len(arrays)), s.mesh.backend._h)
@@ -628,6 +652,8 @@ def set_tracers(Prog: "PrognosticVars", arrays) -> Tracers:
     for j, a in enumerate(arrays):
         tr.set(j, a, 0)
         tr.set(j, a, 1)
+    if diffusivity is not None:
+        tr.set_diffusivity(diffusivity)
     return tr
 
 

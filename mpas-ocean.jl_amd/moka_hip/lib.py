@@ -101,6 +101,7 @@ EXPORTS = [
     "moka_halo_stats_enable", "moka_halo_stats_read", "moka_halo_set_stream_flags", "moka_state_array_address", "moka_state_placement_launches",
     "moka_state_rk4_streams",
     "moka_set_tracers", "moka_tracer_upload", "moka_tracer_download", "moka_state_tracer_path",
+    "moka_set_tracer_diffusion", "moka_tracer_diffusion",
 ]
 
 
@@ -240,6 +241,8 @@ def lib():
     L.moka_tracer_upload.argtypes = [vp, C.c_int32, C.c_int, vp]
     L.moka_tracer_download.argtypes = [vp, C.c_int32, C.c_int, vp]
     L.moka_state_tracer_path.argtypes = [vp]
+    L.moka_set_tracer_diffusion.argtypes = [vp, vp]
+    L.moka_tracer_diffusion.argtypes = [vp, C.c_int32, C.POINTER(C.c_double)]
     L.moka_tape_create.argtypes = [vp, C.c_int64, C.POINTER(vp)]
     L.moka_tape_destroy.argtypes = [vp]
     L.moka_tape_destroy.restype = None

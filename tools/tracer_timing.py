@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
-"""GPU box helper: ms per linear RK4 step with 0, 1 and 3 passive tracers (moka_set_tracers) in one process, the three settings
-alternated round by round and each step timed between two moka_mark events (medians) -- first with the default kernel choice (the
-tracer launch in its patch form), then with kernel variant 3 (generic dycore kernels, the tracer launch in its generic form).  The
-tracer launch alone is the difference to the same run's tracer-free step, over the four launches of a step.  Config 4 (icosahedral
+"""GPU box helper: ms per linear RK4 step with 0, 1 and 3 passive tracers (moka_set_tracers), each tracer count with harmonic
+diffusion off and on (moka_set_tracer_diffusion, kappa = 0.02 dcEdge_min^2 / dt), in one process, the settings alternated round by
+round and each step timed between two moka_mark events (median, min, max) -- first with the default kernel choice (the tracer launch
+in its patch form), then with kernel variant 3 (generic dycore kernels, the tracer launch in its generic form).  The tracer launch
+alone is the difference to the same run's tracer-free step, over the four launches of a step; the diffusion-off legs run the
+instantiations of a state that never set a diffusivity, so they are the baseline of the diffusion-on legs.  Shader clock and package
+power are sampled from sysfs while the 3-tracer steps run back to back, diffusion off and on (bench.py's under_load).  Config 4 (icosahedral
 m = 320, 1 024 002 cells x 60 levels); --small: config 3 (m = 64).  Prints one JSON line and, with --out FILE, writes the summary
 table there.
 
@@ -21,10 +24,12 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "mpas-ocean.jl_amd"))
+sys.path.insert(0, ROOT)
 import numpy as np                         # noqa: E402
 import moka_hip as mk                      # noqa: E402
 from moka_hip import lib as L              # noqa: E402
 from moka_hip import meshgen as mg         # noqa: E402
+import bench                               # noqa: E402  (under_load)
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--small", action="store_true")
@@ -44,16 +49,21 @@ lib = L.lib()
 rng = np.random.default_rng(1)
 phi = rng.uniform(0.5, 1.5, (mesh.nCells, K))
 counts = (0, 1, 3)
-result = {"cells": mesh.nCells, "edges": mesh.nEdges, "K": K, "rounds": args.rounds, "steps_per_round": args.steps, "forms": {}}
+kappa = 0.02 * float(mesh.dcEdge.min()) ** 2 / dts
+settings = [(0, False)] + [(n, d) for n in counts if n for d in (False, True)]
+key = lambda n, d: f"{n}{'+diff' if d else ''}"      # noqa: E731
+result = {"cells": mesh.nCells, "edges": mesh.nEdges, "K": K, "rounds": args.rounds, "steps_per_round": args.steps, "kappa": kappa,
+          "forms": {}}
 for variant, form in ((0, "patch"), (3, "generic")):
     b.set_kernel_variant(variant)
     Setup, Diag, Tend, Prog = mk.ocn_init_from_arrays(mesh, ssh, u, h, rest, cfg, b, multilayer=True)
     sh = Prog._state._h
     steps = {n: [] for n in counts}
+    dsteps = {key(n, d): [] for n, d in settings}
     path = 0
     for _ in range(args.rounds):
-        for n in counts:
-            tr = mk.set_tracers(Prog, [phi] * n)
+        for n, diff in settings:
+            tr = mk.set_tracers(Prog, [phi] * n, diffusivity=kappa if diff else None)
             for _ in range(args.warmup):                                     # lazy allocations, LDS attributes, clocks
                 L.check(lib.moka_step_rk4(sh, C.c_double(dts)), b._h)
             b.synchronize()
@@ -63,9 +73,15 @@ for variant, form in ((0, "patch"), (3, "generic")):
                 L.check(lib.moka_step_rk4(sh, C.c_double(dts)), b._h)
                 b.mark()
             b.synchronize()
-            steps[n] += list(b.marks_read())
+            dsteps[key(n, diff)] += list(b.marks_read())
+            if not diff:
+                steps[n] = dsteps[key(n, False)]
             if n:
                 path = tr.path()
+    load = {}
+    for diff in (False, True):                                               # clock and power while the 3-tracer steps run
+        mk.set_tracers(Prog, [phi] * 3, diffusivity=kappa if diff else None)
+        load[key(3, diff)] = bench.under_load(b, lambda: L.check(lib.moka_step_rk4(sh, C.c_double(dts)), b._h), seconds=1.5, batch=5)
     mk.set_tracers(Prog, [])
     med = {n: statistics.median(v) for n, v in steps.items()}
     contract = {n: 8 * K * (4 * mesh.nEdges + 10 * mesh.nCells + 16 * n * mesh.nCells) for n in counts if n}
@@ -74,7 +90,12 @@ for variant, form in ((0, "patch"), (3, "generic")):
         "increment_ms_per_step": {n: med[n] - med[0] for n in counts if n},
         "tracer_launch_ms": {n: (med[n] - med[0]) / 4 for n in counts if n},
         "contract_bytes_per_step": contract,
-        "contract_TBps": {n: contract[n] / ((med[n] - med[0]) * 1e-3) / 1e12 for n in contract}}
+        "contract_TBps": {n: contract[n] / ((med[n] - med[0]) * 1e-3) / 1e12 for n in contract},
+        "diffusion": {k: {"median": statistics.median(v), "min": min(v), "max": max(v),
+                          "p25": statistics.quantiles(v, n=4)[0], "p75": statistics.quantiles(v, n=4)[2]} for k, v in dsteps.items()},
+        "diffusion_launch_delta_ms": {n: (statistics.median(dsteps[key(n, True)]) - statistics.median(dsteps[key(n, False)])) / 4
+                                      for n in counts if n},
+        "under_load": load}
     Prog._state.close(); Setup.mesh.close()
 b.set_kernel_variant(0)
 bw = b.bw_probe()
@@ -100,4 +121,14 @@ if args.out:
                              f"{f['contract_bytes_per_step'][n] / 1e9:<23.2f} {f['contract_TBps'][n]:<8.2f} "
                              f"{f['contract_fraction_of_copy_rate'][n]:.2f}")
                 fh.write(line.rstrip() + "\n")
+            fh.write("\n   harmonic diffusion (kappa = 0.02 dcEdge_min^2 / dt on every tracer) off / on, ms / RK4 step\n"
+                     "   setting   median    min       p25       p75       max       on - off per tracer launch\n")
+            for k, d in f["diffusion"].items():
+                line = f"   {k:<9s} {d['median']:<9.3f} {d['min']:<9.3f} {d['p25']:<9.3f} {d['p75']:<9.3f} {d['max']:<9.3f}"
+                if k.endswith("+diff"):
+                    line += f" {f['diffusion_launch_delta_ms'][int(k.split('+')[0])]:+.3f}"
+                fh.write(line.rstrip() + "\n")
+            for k, u in f["under_load"].items():
+                fh.write(f"   under load, {k}: sclk {u['sclk_mhz_mean']} MHz (min {u['sclk_mhz_min']}), power {u['power_w_mean']} W "
+                         f"(max {u['power_w_max']}), {u['ms_per_call_sustained']:.3f} ms / step sustained\n")
             fh.write("\n")
