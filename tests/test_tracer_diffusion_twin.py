@@ -9,6 +9,7 @@ import pytest
 
 import oracle as orc
 import tracer_diffusion_twin as td
+import tracer_cases as tc
 import tracer_twin as tt
 import trisk_reference as tr
 from del4_twin import TwinState
@@ -241,3 +242,40 @@ def test_diffusion_entry_points_exist():
     assert hasattr(mk.Tracers, "set_diffusivity") and hasattr(mk.Tracers, "diffusivity")
     for doc in ("README.md", "DESIGN.md", "INTEGRATION.md", os.path.join("include", "moka_hip.h")):
         assert ", tracer diffusion," not in open(os.path.join(ROOT, doc)).read(), doc
+
+
+@pytest.mark.parametrize("nx,ny,K", tc.TINY)
+def test_twin_tendency_on_tiny_periodic_meshes(nx, ny, K):
+    """The smallest doubly periodic meshes, where a cell meets the same neighbour through several slots: per element
+    |T - T_ld| <= C_TD 2^-53 M as on the large meshes, and a constant tracer's diffusive part vanishes exactly.  The GPU test on
+    these meshes (test_gpu_tracer_shapes.py) rests on a twin known to handle them."""
+    name = f"tiny-{nx}-{ny}"
+    mesh = tc.get_mesh(name)
+    _, u, h, rest = tc.state_of(name, K)
+    mlt = np.full(mesh.nEdges, K, dtype=np.int32)
+    om = orc.OracleMesh(mesh, K, resting_thickness_sum=rest.sum(1), max_level_edge_top=mlt)
+    kappa = tc.kappas(name, 3)[0]
+    twin = td.TracerDiffusionTwin(om, om, [kappa])
+    for phi in tc.distinct_fields(mesh, K, 2):
+        ref, M = td.tendency_ld(mesh, u, h, phi, mlt, kappa)
+        ok = tr.within(twin.tendency(u, h, phi, kappa), ref, M, td.C_TD)
+        assert ok.all(), int((~ok).sum())
+        assert not tr.within(twin.tendency(u, h, phi, 0.0), ref, M, td.C_TD).all()         # the diffusive term is there
+    one = np.ones_like(h)
+    assert np.array_equal(twin.tendency(u, h, one, kappa), om.tendencies_clean(u, h)[1])
+
+
+def test_advection_and_diffusion_are_integrated_by_rk4_on_an_exact_eigenmode():
+    """The plane wave of test_kappa_means_what_it_says_on_an_exact_eigenmode in a uniform flow U = (70, 40) (tracer_cases.py derives
+    the mode): 10 steps must give 1 + 0.5 Re(R(z)^10 exp(i k . x)) with z = (mu + kappa lam) dt off both axes, within that test's
+    10 * 32 * 2^-53 * max|phi0| = 5.3e-14.  Measured on the CPU: z = -0.010762 - 0.11201i, |R|^10 = 0.89797, deviation 1.1e-15; the
+    same bound refuses a third-order stage loop by 3.0e-5 and the exact exponential by 6.8e-7; the dycore drift is exactly 0."""
+    mesh, (ssh, u, h, rest), phi0 = tc.eigenmode_state(4)
+    om = orc.OracleMesh(mesh, 4, resting_thickness_sum=rest.sum(1), max_level_edge_top=4)
+    twin = td.TracerDiffusionTwin(om, om, [tc.EIG_KAPPA])
+    st = TwinState(ssh, u, h)
+    phis = [[phi0.copy()], [phi0.copy()]]
+    for _ in range(tc.EIG_STEPS):
+        twin.step_rk4(st, phis, tc.EIG_DT)
+    assert np.array_equal(st.u[1], u) and np.array_equal(st.h[1], h)          # the uniform flow is steady, exactly
+    tc.eigenmode_check(phis[1][0], mesh, 4, tc.EIG_KAPPA, phi0, "TracerDiffusionTwin, kappa = 0.02 dc^2 / dt")

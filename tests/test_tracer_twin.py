@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import oracle as orc
+import tracer_cases as tc
 import tracer_twin as tt
 import trisk_reference as tr
 from del4_twin import Del4Twin, TwinState
@@ -233,3 +234,43 @@ def test_tracer_entry_points_exist():
     assert callable(mk.set_tracers) and hasattr(mk.Tracers, "get") and hasattr(mk.Tracers, "set") and hasattr(mk.Tracers, "path")
     mk_src = open(os.path.join(ROOT, "mpas-ocean.jl_amd", "Makefile")).read()
     assert "tracers.o" in mk_src
+
+
+# ---- repeated neighbours, and the stage weights ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("nx,ny,K", tc.TINY)
+def test_twin_tendency_on_tiny_periodic_meshes(nx, ny, K):
+    """The smallest doubly periodic meshes, where a cell meets the same neighbour through several slots (2 x 4, 4 x 2: through both
+    boundaries): per element |T - T_ref| <= C_T 2^-53 M as on the large meshes, and the unit tracer's T is tendLayerThickness.  The
+    GPU test on these meshes (test_gpu_tracer_shapes.py) rests on a twin known to handle them."""
+    mesh = tc.get_mesh(f"tiny-{nx}-{ny}")
+    _, u, h, rest = tc.state_of(f"tiny-{nx}-{ny}", K)
+    mlt = np.full(mesh.nEdges, K, dtype=np.int32)
+    om = orc.OracleMesh(mesh, K, resting_thickness_sum=rest.sum(1), max_level_edge_top=mlt)
+    twin = tt.TracerTwin(om, om)
+    for phi in tc.distinct_fields(mesh, K, 2):
+        ok = check_T(twin, mesh, u, h, phi, mlt)
+        assert ok.all(), int((~ok).sum())
+    assert np.array_equal(twin.tendency(u, h, np.ones_like(h)), om.tendencies_clean(u, h)[1])
+
+
+def _eigenmode_run(twin_cls):
+    mesh, (ssh, u, h, rest), phi0 = tc.eigenmode_state(4)
+    om = orc.OracleMesh(mesh, 4, resting_thickness_sum=rest.sum(1), max_level_edge_top=4)
+    twin = twin_cls(om, om)
+    st = TwinState(ssh, u, h)
+    phis = [[phi0.copy()], [phi0.copy()]]
+    for _ in range(tc.EIG_STEPS):
+        twin.step_rk4(st, phis, tc.EIG_DT)
+    assert np.array_equal(st.u[1], u) and np.array_equal(st.h[1], h)          # the uniform flow is steady, exactly
+    return mesh, phis[1][0], phi0
+
+
+def test_advection_is_integrated_by_rk4_on_an_exact_eigenmode():
+    """A plane wave in a uniform flow U = (70, 40) over regular hexagons (tracer_cases.py derives the mode): 10 steps of
+    phi0 = 1 + 0.5 cos(k . x) must give 1 + 0.5 Re(R(z)^10 exp(i k . x)), z = mu dt, R the RK4 stability polynomial, within
+    10 steps * 32 * 2^-53 * max|phi0| = 5.3e-14 (the diffusion eigenmode test's tolerance).  z is imaginary here, so this pins the
+    stage weights a, b and the Qc / Qn recipe where the unit-tracer and the content identities, which hold for any weights, cannot.
+    Measured on the CPU: z = -0.11201i, |R|^10 = 1.00000, deviation 1.3e-15; the same bound refuses a third-order loop by 3.3e-5
+    and the exact exponential by 7.3e-7; the dycore drift is exactly 0."""
+    mesh, phi, phi0 = _eigenmode_run(tt.TracerTwin)
+    tc.eigenmode_check(phi, mesh, 4, 0.0, phi0, "TracerTwin, kappa = 0")
