@@ -549,8 +549,9 @@ int  moka_state_del4_path(const moka_state *st);
  * the moka_rk4_dist_* calls return MOKA_ERR_UNSUPPORTED, and moka_set_tuning key 7 leaves the state on the running sum
  * (moka_state_rk4_streams: 16).  moka_state_optimize_placement neither times nor moves the tracer arrays.
  * Out of scope: upwind, FCT and higher-order edge values, biharmonic, anisotropic or spatially varying tracer diffusion, Forward Euler,
- * fp32 storage, partitioned meshes, reverse mode, the 13-stream form, YAML keys and NetCDF I/O of tracers, and fusing the tracer sum
- * into the dycore's stage kernels. */
+ * fp32 storage, partitioned meshes, reverse mode with respect to the flow or the diffusivities (with respect to the tracers themselves:
+ * moka_tracer_tape_* below), the 13-stream form, YAML keys and NetCDF I/O of tracers, and fusing the tracer sum into the dycore's stage
+ * kernels. */
 int  moka_set_tracers(moka_state *st, int32_t nTracers);
 /* tracer j (0-based) at time_level 0 (previous) / 1 (current): (nVertLevels, nCells) doubles in the caller's cell numbering, like
  * layerThickness */
@@ -568,6 +569,55 @@ int  moka_state_tracer_path(const moka_state *st);
 int  moka_set_tracer_diffusion(moka_state *st, const double *kappa);
 /* the diffusivity of tracer j (0-based) into *out; MOKA_ERR_ARG for j out of range */
 int  moka_tracer_diffusion(const moka_state *st, int32_t j, double *out);
+
+/* ---- reverse mode of passive tracer transport over a frozen flow (extension) ---------------------------------------
+ * Once the flow is given the tracer step above is linear in phi, so d J(phi_N) / d phi_0 is the exact transpose of a linear map.  It
+ * needs no adjoint of the dycore, only the provisional states the step forms anyway, and therefore works over the linear, nonlinear,
+ * Del2 and Del4 dycores alike.  A handle of its own, separate from moka_tape: moka_tape_create still refuses a state with tracers, and
+ * moka_set_tracers a state with a tape of either kind.
+ * Notation as above: a = (dt/2, dt/2, dt), b = (dt/6, dt/3, dt/3, dt/6); P_s = (pu_s, ph_s), s = 0..3, the provisional states the four
+ * stage launches read (ph_0 = h_cur); hn the new level's thickness; kappa_j the diffusivities in force during the step; sdv, dvdc,
+ * invArea and the skip rules (empty slots, slots with k >= maxLevelEdgeTop[e]) those of the forward scheme; c' the cell across slot i.
+ * The transposed tendency r = R(P, y) at (k, c) of a field y accumulates from 0.0 over the slots i of edgesOnCell in slot order, one
+ * rounding per operation, no contraction:
+ *   hE = 0.5 * (ph[k,c] + ph[k,c']);  F = pu[k,e] * hE                  (the forward bits)
+ *   r += ((0.5 * F) * sdv[c,i]) * (y[k,c] - y[k,c'])
+ *   with diffusion, a second, separate addition:   r += ((kappa_j * hE) * dvdc[c,i]) * (y[k,c'] - y[k,c])
+ * -- sdv of the edge seen from c' is -sdv[c,i] and the mask belongs to the edge, so the transposed scatter folds into the difference
+ * y[c] - y[c'] with y = w * invArea; the diffusion operator is self-adjoint under the area weight.  A gather over the forward stencil:
+ * the forward launch's traffic, no atomics.
+ * One step backwards, per tracer j and element (k, c); X the adjoint of phi_new, S a scratch field, invA = invArea[c]:
+ *   g = X / hn
+ *   y = (b[3] * g) * invA
+ *   s = 3, 2, 1:   r = R(P_s, y);  v = r / ph_s;  S = (s == 3 ? v : S + v);  y = (b[s-1] * g + a[s-1] * v) * invA
+ *   r = R(P_0, y);  X_prev = ph_0 * (g + S) + r
+ * X_prev is the adjoint of phi_cur.  The recipe never reads phi.  Hence: a zero seed stays exactly zero; a tracer with kappa_j == 0
+ * beside diffused tracers has the bits of the undiffused sweep (adding +-0.0 never changes r, by the forward argument); and a sweep
+ * whose recorded steps all have every kappa == 0 launches the instances without diffusion.
+ * The result is the gradient with respect to the tracer fields at the start of the first recorded step, the flow held as it ran.
+ * Usage: tracer_tape_create -> n x step_rk4_tracer_taped -> seed (per tracer) -> sweep -> download (per tracer).
+ * Out of scope: sensitivities of the tracers to the flow (d phi_N / d (u, h)) and to kappa, coupling to moka_tape, Forward Euler,
+ * partitioned meshes, fp32 storage. */
+typedef struct moka_tracer_tape moka_tracer_tape;
+/* MOKA_ERR_UNSUPPORTED on a state without tracers, MOKA_ERR_ARG for NULL arguments or a negative capacity.  The tape remembers the
+ * state's tracer count and counts as a tape of the state: while it lives, moka_state_optimize_placement and moka_set_tracers(st, n > 0)
+ * refuse.  K * (4 nEdges + 5 nCells) doubles per step of capacity (the four P_s and hn), nTracers more for the diffusivities, and five
+ * work arrays of nTracers * K * nCells doubles.  State and tape may be destroyed in either order. */
+int  moka_tracer_tape_create(moka_state *st, int64_t capacity_steps, moka_tracer_tape **out);
+void moka_tracer_tape_destroy(moka_tracer_tape *t);
+/* exactly moka_step_rk4 on the tape's state -- state and tracers end up bit for bit as after the untaped call -- with P_0..P_3, hn and
+ * the diffusivities recorded by copies behind the stage launches.  MOKA_ERR_ARG when the tape is full or the state's tracer count is no
+ * longer the tape's.  A recorded step un-seeds the tape. */
+int  moka_step_rk4_tracer_taped(moka_tracer_tape *t, double dt);
+int  moka_tracer_tape_steps(const moka_tracer_tape *t, int64_t *n);                /* recorded and not yet reversed */
+/* X_j := host, (nVertLevels, nCells) doubles in the caller's numbering like moka_tracer_upload; NULL = zeros.  The first seed after a
+ * recorded step zeroes the other tracers' X.  MOKA_ERR_ARG for j out of range. */
+int  moka_tracer_adjoint_seed(moka_tracer_tape *t, int32_t j, const double *host);
+/* reverse over (and pop) every recorded step; the tape is then empty and reusable.  MOKA_ERR_ARG when unseeded. */
+int  moka_tracer_adjoint_sweep(moka_tracer_tape *t);
+int  moka_tracer_adjoint_download(moka_tracer_tape *t, int32_t j, double *host);    /* X_j as it stands */
+/* which kernel served the last reverse stage: 1 the patch form, 2 the generic form (the conditions of moka_state_tracer_path), 0 none yet */
+int  moka_tracer_adjoint_path(const moka_tracer_tape *t);
 
 /* ---- reverse mode of the Forward-Euler loop ----------------------------------------------------------------
  * The reference gets d sum(ssh^2) / d (initial normalVelocity, layerThickness) from Enzyme over ocn_run_loop

@@ -1443,13 +1443,28 @@ static hipError_t tracer_stage(moka_state *st, int s, const StageArgs &g)
     return launch_tracers(dev, t, mm->lpc, generic, st->ctx->stream);
 }
 
-extern "C" {
+// Tape of the tracer reverse mode (moka_tracer_tape_*, further down).  Per recorded step: the four provisional states the stage launches
+// read, the new level's thickness and the diffusivities in force -- K * (4 nEdges + 5 nCells) doubles and nTracers more.
+struct moka_tracer_tape {
+    moka_state *st = nullptr;
+    moka_ctx *ctx = nullptr;
+    int nT = 0;
+    int64_t capacity = 0, n = 0;
+    double *pu = nullptr, *ph = nullptr;             // capacity x 4 x (K, nE) / (K, nC): pu_s, ph_s of stage s = 0..3
+    double *hn = nullptr;                            // capacity x (K, nC): layerThickness of the new level
+    double *kap = nullptr;                           // capacity x nT: the diffusivities on the device
+    std::vector<double> kappa, dts;                  // ... and on the host (n * nT values); dt of each step
+    double *X = nullptr, *g = nullptr, *S = nullptr, *y[2] = {nullptr, nullptr};   // nT x (K, nC) each: the adjoint state and the sweep's work arrays
+    bool seeded = false;
+    int path = 0;                                    // moka_tracer_adjoint_path
+    std::vector<void *> allocs;
+    bool counted = false;                            // st->attached includes this tape
+};
 
-int moka_state_rk4_streams(const moka_state *st) { return !st ? 0 : rk13_usable(st) ? 13 : 16; }
-
-int moka_step_rk4(moka_state *st, double dt)
+// moka_step_rk4, and the same step recorded on `rec`: each stage's provisional state is copied behind that stage's launches, before a
+// later stage overwrites the ping-pong buffer; the new thickness behind stage 4.  Copies only: the step's launches are untouched.
+static int step_rk4(moka_state *st, double dt, moka_tracer_tape *rec)
 {
-    if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
     HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
     const double *ssh0 = nullptr;
     int rc = rk4_begin(st, &ssh0);
@@ -1472,11 +1487,28 @@ int moka_step_rk4(moka_state *st, double dt)
         const StageArgs g = s13 ? rk13_stage_args(st, s, dt, ssh0) : rk4_stage_args(st, s, dt, ssh0);
         HIPCHK(c, run_stage(st, g));
         if (st->nTracers > 0) HIPCHK(c, tracer_stage(st, s, g));
+        if (rec) {
+            const Plan &p = st->mesh->plan;
+            const size_t nEK = (size_t)p.K * p.nE, nCK = (size_t)p.K * p.nC;
+            HIPCHK(c, hipMemcpyAsync(rec->pu + nEK * (4 * rec->n + s - 1), g.pu, nEK * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(rec->ph + nCK * (4 * rec->n + s - 1), g.ph, nCK * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+            if (s == 4) HIPCHK(c, hipMemcpyAsync(rec->hn + nCK * rec->n, g.nh_out, nCK * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        }
     }
     if (timed) HIPCHK(c, stamp());
     if (s13) rk13_end(st);
     else rk4_end(st);
     return MOKA_OK;
+}
+
+extern "C" {
+
+int moka_state_rk4_streams(const moka_state *st) { return !st ? 0 : rk13_usable(st) ? 13 : 16; }
+
+int moka_step_rk4(moka_state *st, double dt)
+{
+    if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
+    return step_rk4(st, dt, nullptr);
 }
 
 // Per-stage kernel durations of moka_step_rk4 from HIP events on the compute stream (bench.py's per-mode roofline lines).
@@ -1816,6 +1848,170 @@ int moka_tracer_diffusion(const moka_state *st, int32_t j, double *out)
     *out = st->trKappa.empty() ? 0.0 : st->trKappa[j];
     return MOKA_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// reverse mode of the tracer transport over a frozen flow (include/moka_hip.h: the algebra; tracer_adjoint.hip: the kernels).  A handle of
+// its own, separate from moka_tape: the tracer step is linear in phi, so its transpose needs the recorded provisional states only.
+// ---------------------------------------------------------------------------------------------
+static int ttape_alloc(moka_tracer_tape *t, double **out, size_t elems)
+{
+    void *d = nullptr;
+    const size_t bytes = elems * sizeof(double);
+    hipError_t e = hipMalloc(&d, std::max<size_t>(bytes, 16));
+    if (e != hipSuccess)
+        return fail(t->ctx, MOKA_ERR_ALLOC, std::string("tracer tape: hipMalloc of ") + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
+    t->allocs.push_back(d);
+    HIPCHK(t->ctx, hipMemsetAsync(d, 0, bytes, t->ctx->stream));
+    *out = static_cast<double *>(d);
+    return MOKA_OK;
+}
+
+int moka_tracer_tape_create(moka_state *st, int64_t capacity_steps, moka_tracer_tape **out)
+{
+    if (!st || !out || capacity_steps < 0) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "bad argument");
+    *out = nullptr;
+    if (st->nTracers == 0) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "tracer reverse mode: the state has no tracers (moka_set_tracers)");
+    const Plan &p = st->mesh->plan;
+    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    moka_tracer_tape *t = new (std::nothrow) moka_tracer_tape();
+    if (!t) return fail(st->ctx, MOKA_ERR_ALLOC, "out of host memory");
+    t->st = st; t->ctx = st->ctx;
+    t->nT = st->nTracers;
+    t->capacity = capacity_steps;
+    const size_t nEK = (size_t)p.K * p.nE, nCK = (size_t)p.K * p.nC, cap = (size_t)capacity_steps;
+    int rc = MOKA_OK;
+    auto A = [&](double **q, size_t n) { if (rc == MOKA_OK) rc = ttape_alloc(t, q, n); };
+    A(&t->pu, nEK * 4 * cap); A(&t->ph, nCK * 4 * cap); A(&t->hn, nCK * cap); A(&t->kap, (size_t)t->nT * cap);
+    A(&t->X, nCK * t->nT); A(&t->g, nCK * t->nT); A(&t->S, nCK * t->nT); A(&t->y[0], nCK * t->nT); A(&t->y[1], nCK * t->nT);
+    if (rc != MOKA_OK) { moka_tracer_tape_destroy(t); return rc; }
+    HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));
+    state_attach(st);
+    t->counted = true;
+    *out = t;
+    return MOKA_OK;
+}
+
+void moka_tracer_tape_destroy(moka_tracer_tape *t)
+{
+    if (!t) return;
+    bool alive;
+    {
+        std::lock_guard<std::mutex> lk(g_liveMutex);
+        alive = g_liveStates.count(t->st) != 0;
+    }
+    if (t->counted) state_detach(t->st);
+    if (alive) {                         // a state that went first synchronised its stream when it did: nothing of this tape is in flight
+        (void)hipSetDevice(t->ctx->device);
+        (void)hipStreamSynchronize(t->ctx->stream);
+    }
+    for (void *q : t->allocs) (void)hipFree(q);
+    delete t;
+}
+
+int moka_step_rk4_tracer_taped(moka_tracer_tape *t, double dt)
+{
+    if (!t) return fail(nullptr, MOKA_ERR_ARG, "tracer tape is NULL");
+    moka_state *st = t->st;
+    if (t->n >= t->capacity) return fail(t->ctx, MOKA_ERR_ARG, "tracer tape is full");
+    if (st->nTracers != t->nT) return fail(t->ctx, MOKA_ERR_ARG, "tracer tape: the state's tracer count has changed since the tape was created");
+    HIPCHK(t->ctx, hipSetDevice(t->ctx->device));
+    if (int rc = step_rk4(st, dt, t)) return rc;
+    // the diffusivities the step's launches read (every copy on the context's stream, device to device: no host buffer to keep alive)
+    double *kd = t->kap + (size_t)t->n * t->nT;
+    if (st->trKappaDev) HIPCHK(t->ctx, hipMemcpyAsync(kd, st->trKappaDev, (size_t)t->nT * sizeof(double), hipMemcpyDeviceToDevice, t->ctx->stream));
+    else HIPCHK(t->ctx, hipMemsetAsync(kd, 0, (size_t)t->nT * sizeof(double), t->ctx->stream));
+    for (int j = 0; j < t->nT; ++j) t->kappa.push_back(st->trKappa.empty() ? 0.0 : st->trKappa[j]);
+    t->dts.push_back(dt);
+    ++t->n;
+    t->seeded = false;
+    return MOKA_OK;
+}
+
+int moka_tracer_tape_steps(const moka_tracer_tape *t, int64_t *n)
+{
+    if (!t || !n) return fail(t ? t->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    *n = t->n;
+    return MOKA_OK;
+}
+
+static int ttape_field(moka_tracer_tape *t, int32_t j, double **out)
+{
+    if (!t) return fail(nullptr, MOKA_ERR_ARG, "tracer tape is NULL");
+    if (j < 0 || j >= t->nT) return fail(t->ctx, MOKA_ERR_ARG, "tracer index out of range (moka_tracer_tape_create)");
+    HIPCHK(t->ctx, hipSetDevice(t->ctx->device));
+    const Plan &p = t->st->mesh->plan;
+    *out = t->X + (size_t)j * p.K * p.nC;
+    return MOKA_OK;
+}
+
+int moka_tracer_adjoint_seed(moka_tracer_tape *t, int32_t j, const double *host)
+{
+    double *d = nullptr;
+    if (int rc = ttape_field(t, j, &d)) return rc;
+    const Plan &p = t->st->mesh->plan;
+    const size_t nCK = (size_t)p.K * p.nC;
+    if (!t->seeded) HIPCHK(t->ctx, hipMemsetAsync(t->X, 0, nCK * t->nT * sizeof(double), t->ctx->stream));
+    t->seeded = true;
+    if (!host) {
+        HIPCHK(t->ctx, hipMemsetAsync(d, 0, nCK * sizeof(double), t->ctx->stream));
+        return MOKA_OK;
+    }
+    return put_rows(t->st->mesh, d, host, MOKA_CELL, p.nC, p.K);
+}
+
+int moka_tracer_adjoint_sweep(moka_tracer_tape *t)
+{
+    if (!t) return fail(nullptr, MOKA_ERR_ARG, "tracer tape is NULL");
+    if (!t->seeded) return fail(t->ctx, MOKA_ERR_ARG, "tracer tape: seed first (moka_tracer_adjoint_seed)");
+    moka_state *st = t->st;
+    moka_mesh *mm = st->mesh;
+    const Plan &p = mm->plan;
+    HIPCHK(t->ctx, hipSetDevice(t->ctx->device));
+    hipStream_t s = t->ctx->stream;
+    bool diff = false;
+    for (double k : t->kappa) diff = diff || k != 0.0;
+    if (diff && !mm->dvdc)
+        if (int rc = upload_vec(mm, mm->plan.dvdc, &mm->dvdc)) return rc;
+    const MeshDev dev = launch_bounds(mm);
+    const bool generic = t->ctx->variant == 3;
+    const size_t nEK = (size_t)p.K * p.nE, nCK = (size_t)p.K * p.nC;
+    while (t->n > 0) {
+        const int64_t n = t->n - 1;
+        const double dt = t->dts[n];
+        const double a[3] = {dt / 2., dt / 2., dt};
+        const double b[4] = {dt / 6., dt / 3., dt / 3., dt / 6.};
+        int cur = 0;
+        HIPCHK(t->ctx, launch_tracer_adj_seed(dev, t->X, t->hn + nCK * n, t->g, t->y[cur], b[3], t->nT, s));
+        for (int rs = 3; rs >= 0; --rs) {
+            TracerAdjArgs q{};
+            q.nT = t->nT; q.rs = rs; q.stride = (int64_t)nCK;
+            q.pu = t->pu + nEK * (4 * n + rs); q.ph = t->ph + nCK * (4 * n + rs);
+            q.y = t->y[cur]; q.g = t->g; q.S = t->S;
+            q.out = rs > 0 ? t->y[cur ^ 1] : t->X;
+            q.cb = rs > 0 ? b[rs - 1] : 0.0; q.ca = rs > 0 ? a[rs - 1] : 0.0;
+            q.kappa = diff ? t->kap + (size_t)n * t->nT : nullptr;
+            q.dvdc = diff ? mm->dvdc : nullptr;
+            t->path = tracer_adjoint_kernel(dev, mm->lpc, q.nT, generic, diff).form;
+            HIPCHK(t->ctx, launch_tracer_adjoint(dev, q, mm->lpc, generic, s));
+            cur ^= 1;
+        }
+        t->n = n;
+        t->dts.pop_back();
+        t->kappa.resize((size_t)n * t->nT);
+    }
+    return MOKA_OK;
+}
+
+int moka_tracer_adjoint_download(moka_tracer_tape *t, int32_t j, double *host)
+{
+    double *d = nullptr;
+    if (int rc = ttape_field(t, j, &d)) return rc;
+    if (!host) return fail(t->ctx, MOKA_ERR_ARG, "NULL argument");
+    const Plan &p = t->st->mesh->plan;
+    return get_rows(t->st->mesh, host, d, MOKA_CELL, p.nC, p.K);
+}
+
+int moka_tracer_adjoint_path(const moka_tracer_tape *t) { return t ? t->path : 0; }
 
 // ---------------------------------------------------------------------------------------------
 // reverse mode of the Forward-Euler loop.  The reference differentiates

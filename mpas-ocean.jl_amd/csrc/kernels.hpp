@@ -213,6 +213,29 @@ struct TracerKernel {
 TracerKernel tracer_kernel(const MeshDev &m, int lpc, int nT, bool generic, bool diff);
 hipError_t launch_tracers(const MeshDev &m, const TracerArgs &a, int lpc, bool generic, hipStream_t s);
 
+// ---- reverse mode of the tracer step over a frozen flow (moka_tracer_tape_*; tracer_adjoint.hip): one launch per reverse stage ----
+// With r = R(P_rs, y) the transposed tendency of include/moka_hip.h, per tracer and element (hc = ph[k,c], invA = invArea[c]):
+//   rs > 0:  v = r / hc;  S = (rs == 3 ? v : S + v);  out = (cb * g + ca * v) * invA      the next gathered field
+//   rs == 0: out = hc * (g + S) + r                                                        the adjoint of the current level's tracers
+// y is gathered while out is written: the two never alias.
+struct TracerAdjArgs {
+    int nT, rs;                   // reverse stage 3, 2, 1, 0 = the forward stage whose provisional state is read
+    int64_t stride;               // K * nC
+    const double *pu, *ph;        // the recorded provisional normalVelocity / layerThickness of forward stage rs (gathered)
+    const double *y;              // the adjoint of the stage's tendency times invArea (gathered)
+    const double *g;              // X / hn of the step
+    double *S;                    // the running sum of v: written by rs 3, read + written by 2 and 1, read by 0
+    double *out;
+    double cb, ca;                // b[rs - 1], a[rs - 1] (unused by rs 0)
+    const double *kappa, *dvdc;   // as in TracerArgs; both nullptr in a sweep whose recorded steps all have every diffusivity zero
+};
+// the kernel that serves a reverse stage, for the launcher and for moka_tracer_adjoint_path: the forward choice (same rows in LDS)
+TracerKernel tracer_adjoint_kernel(const MeshDev &m, int lpc, int nT, bool generic, bool diff);
+hipError_t launch_tracer_adjoint(const MeshDev &m, const TracerAdjArgs &a, int lpc, bool generic, hipStream_t s);
+// g = X / hn and y = (b4 * g) * invArea, elementwise over nT fields: the head of a reverse step
+hipError_t launch_tracer_adj_seed(const MeshDev &m, const double *X, const double *hn, double *g, double *y, double b4, int nT,
+                                  hipStream_t s);
+
 // ---- reverse mode of one Forward-Euler step: gather form, the oracle's summation order ----
 struct AdjMesh {
     int32_t nC, nE, K, ME, W;          // W = width of the transposed Coriolis lists

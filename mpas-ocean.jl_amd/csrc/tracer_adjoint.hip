@@ -1,0 +1,308 @@
+// tracer_adjoint.hip -- reverse mode of the passive tracer transport over a frozen flow (gfx950; moka_tracer_tape_*, NOT in the reference).
+#include "kernels_common.hpp"
+
+namespace moka {
+
+// ------------------------------------------------------------------------------------------------
+// The tracer step is linear in phi once the provisional states P_s = (pu_s, ph_s) are given, so its reverse mode is the transpose of a
+// linear map and reads nothing but those states (include/moka_hip.h states the algebra).  The transposed tendency r = R(P, y) of a
+// field y that already carries invArea is again a gather over the slots of edgesOnCell, in slot order, with the forward skip rules:
+//     hE = 0.5 * (ph[k,c] + ph[k,c']);  F = pu[k,e] * hE                  (the forward bits)
+//     r += ((0.5 * F) * sdv[c,i]) * (y[k,c] - y[k,c'])
+//     DIFF:  r += ((kappa[j] * hE) * dvdc[c,i]) * (y[k,c'] - y[k,c])       a second, separate addition
+// -- sdv of the edge seen from c' is -sdv[c,i] and the mask belongs to the edge, so the scatter of the forward sum folds into the
+// difference; no atomics, the forward launch's streams.  What a reverse stage does with r: TracerAdjArgs (kernels.hpp).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void tracer_adj_update(const TracerAdjArgs &a, double r, double hc, double invA, double g, double sIn,
+                                                  double &sOut, double &out)
+{
+    if (a.rs == 0) {
+        sOut = sIn;
+        out = hc * (g + sIn) + r;
+        return;
+    }
+    const double v = r / hc;
+    sOut = a.rs == 3 ? v : sIn + v;
+    out = (a.cb * g + a.ca * v) * invA;
+}
+
+constexpr int TRA_NT = 256;   // threads of a k_tracer_adj_patch workgroup
+constexpr int TRA_TJ = 4;     // tracers whose sums a lane of k_tracer_adj_cell carries at once (the slot's factor is formed once per TRA_TJ)
+
+// g = X / hn and the first gathered field y = (b4 * g) * invArea of a reverse step: elementwise over (tracer, cell, level)
+__global__ __launch_bounds__(BLOCK) void k_tracer_adj_seed(const double *X, const double *hn, const double *invArea, double *g, double *y,
+                                                           double b4, int K, int64_t stride, int64_t n)
+{
+    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
+        const int64_t off = i % stride;
+        const double gg = X[i] / hn[off];
+        g[i] = gg;
+        y[i] = (b4 * gg) * invArea[off / K];
+    }
+}
+
+// Generic form: LPC lanes span a column, one cell per lane group, index records; any K, any maxEdges (the shape of k_tracer_cell).
+template <int LPC, bool DIFF>
+__global__ __launch_bounds__(BLOCK) void k_tracer_adj_cell(const MeshDev m, const TracerAdjArgs a)
+{
+    constexpr int NG = BLOCK / LPC;
+    const int grp = uniform_if_wave<LPC>(threadIdx.x / LPC), l = threadIdx.x % LPC;
+    const int K = m.K, ME = m.ME;
+    for (int c = blockIdx.x * NG + grp; c < m.nC; c += gridDim.x * NG) {
+        const double invA = cptr(m.invArea)[c];
+        for (int k = l; k < K; k += LPC) {
+            const size_t off = (size_t)c * K + k;
+            const double hc = a.ph[off];
+            for (int j0 = 0; j0 < a.nT; j0 += TRA_TJ) {
+                const int nj = min(TRA_TJ, a.nT - j0);
+                double r[TRA_TJ], yc[TRA_TJ], kap[TRA_TJ];
+#pragma unroll
+                for (int jj = 0; jj < TRA_TJ; ++jj) {
+                    r[jj] = 0.0;
+                    yc[jj] = jj < nj ? a.y[(size_t)(j0 + jj) * a.stride + off] : 0.0;
+                    kap[jj] = DIFF && jj < nj ? cptr(a.kappa)[j0 + jj] : 0.0;
+                }
+                for (int i = 0; i < ME; ++i) {
+                    const int e = cptr(m.eoc)[(size_t)c * ME + i];
+                    if (e < 0 || k >= cptr(m.mltc)[(size_t)c * ME + i]) continue;
+                    const size_t noff = (size_t)cptr(m.coc)[(size_t)c * ME + i] * K + k;
+                    const double hE = 0.5 * (hc + a.ph[noff]);
+                    const double F = a.pu[(size_t)e * K + k] * hE;
+                    const double w = (0.5 * F) * cptr(m.sdv)[(size_t)c * ME + i];
+                    const double dd = DIFF ? cptr(a.dvdc)[(size_t)c * ME + i] : 0.0;
+#pragma unroll
+                    for (int jj = 0; jj < TRA_TJ; ++jj)
+                        if (jj < nj) {
+                            const double yn = a.y[(size_t)(j0 + jj) * a.stride + noff];
+                            r[jj] += w * (yc[jj] - yn);
+                            if (DIFF) r[jj] += ((kap[jj] * hE) * dd) * (yn - yc[jj]);
+                        }
+                }
+#pragma unroll
+                for (int jj = 0; jj < TRA_TJ; ++jj)
+                    if (jj < nj) {
+                        const size_t joff = (size_t)(j0 + jj) * a.stride + off;
+                        double sOut, out;
+                        tracer_adj_update(a, r[jj], hc, invA, a.g[joff], a.rs == 3 ? 0.0 : a.S[joff], sOut, out);
+                        if (a.rs > 0) a.S[joff] = sOut;
+                        a.out[joff] = out;
+                    }
+            }
+        }
+    }
+}
+
+// Patch form (even 34 <= K <= 64, hexagon-width byte-offset records): k_tracer_patch's shape -- one workgroup per patch, half a wave per
+// cell, a lane owns levels 2l and 2l + 1.  The patch's records and the ph rows and the y rows of `chunk` tracers of its own cells are
+// staged in LDS (the forward kernel's layout, hence its LDS formula and its chunking: tracer_kernel); a cell reads its neighbours'
+// cached rows in one burst and overwrites the lanes of foreign rows with masked global loads by byte offset.  The slot factors
+// (0.5 * F) * sdv are formed once per cell and pass and reused by the tracer loop; v = r / ph_s and ph_0 * (g + S) use the staged own row.
+template <int ME_, bool DIFF>
+__global__ __launch_bounds__(TRA_NT, 2) void k_tracer_adj_patch(const MeshDev m, const TracerAdjArgs a, const int chunk)
+{
+    constexpr int NG = TRA_NT / 32;
+    static_assert(ME_ == 6, "burst width");
+    extern __shared__ __align__(16) unsigned char tra_smem[];
+    const int tid = threadIdx.x, grp = tid >> 5, l = tid & 31, K = m.K, CI = m.CI, mC = m.maxOwnC;
+    const bool act = 2 * l < K;
+    const unsigned rowB = (unsigned)K * 8u, lo = (unsigned)l * 16u;
+    double *sRows = reinterpret_cast<double *>(tra_smem);                   // [1 + chunk][maxOwnC][K]  ph rows, then y rows per tracer
+    double *sSd = sRows + (size_t)(1 + chunk) * mC * K;                     // [maxOwnC][ME]  sdv
+    double *sDd = sSd + (size_t)mC * ME_;                                   // [maxOwnC][ME]  dvdc (DIFF only)
+    double *sIa = sDd + (DIFF ? (size_t)mC * ME_ : 0);                      // [maxOwnC]      invArea
+    uint32_t *sRec = reinterpret_cast<uint32_t *>(sIa + mC);                // [maxOwnC][CI]  cRec
+    int *sMl = reinterpret_cast<int *>(sRec + (size_t)mC * CI);             // [maxOwnC][ME]  maxLevelEdgeTop of the slot's edge
+    const int pl_ = patch_of_block(m.nPatches);
+    if (pl_ >= m.nPatches) return;
+    const int p = pl_ + m.patchBegin;
+    const int c0 = m.patchCellStart[p], nc = m.patchCellStart[p + 1] - c0;
+    const unsigned ownB = (unsigned)c0 * rowB, ownN = (unsigned)nc * rowB;
+    const glb_bytes_t uG = (glb_bytes_t)a.pu, hG = (glb_bytes_t)a.ph;
+    const uint32_t ldsH = (uint32_t)(size_t)sRows + lo;
+
+    // rows [rb * nc, (1 + cj) * nc) of the cache from global memory: row type 0 = ph, 1 + jj = y of tracer j0 + jj; eight in flight per half-wave
+    auto stage_rows = [&](int rb, int j0, int cj) {
+        if (!act) return;
+        const int nrows = (1 + cj) * nc;
+        for (int q0 = rb * nc + grp; q0 < nrows; q0 += 8 * NG) {
+            double2 v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int q = q0 + j * NG;
+                v[j] = make_double2(0.0, 0.0);
+                if (q < nrows) {
+                    const int ty = q / nc, ci = q - ty * nc;
+                    const double *src = ty == 0 ? a.ph : a.y + (size_t)(j0 + ty - 1) * a.stride;
+                    v[j] = *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(src) + (ownB + (unsigned)ci * rowB + lo));
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int q = q0 + j * NG;
+                if (q < nrows) {
+                    const int ty = q / nc, ci = q - ty * nc;
+                    reinterpret_cast<double2 *>(sRows + ((size_t)ty * mC + ci) * K)[l] = v[j];
+                }
+            }
+        }
+    };
+
+    {   // records: as in k_tracer_patch, the first TRA_NT entries of each list go through registers ahead of the first LDS write
+        const int nRec = nc * CI, nSd = nc * ME_;
+        const uint32_t r0 = tid < nRec ? m.cRec[(size_t)c0 * CI + tid] : 0u;
+        const double sd0 = tid < nSd ? m.sdv[(size_t)c0 * ME_ + tid] : 0.0;
+        const double dd0 = DIFF && tid < nSd ? a.dvdc[(size_t)c0 * ME_ + tid] : 0.0;
+        const int ml0 = tid < nSd ? m.mltc[(size_t)c0 * ME_ + tid] : 0;
+        const double ia0 = tid < nc ? m.invArea[c0 + tid] : 0.0;
+        stage_rows(0, 0, min(chunk, a.nT));
+        if (tid < nRec) sRec[tid] = r0;
+        if (tid < nSd) { sSd[tid] = sd0; sMl[tid] = ml0; }
+        if (DIFF && tid < nSd) sDd[tid] = dd0;
+        if (tid < nc) sIa[tid] = ia0;
+        for (int i = tid + TRA_NT; i < nRec; i += TRA_NT) sRec[i] = m.cRec[(size_t)c0 * CI + i];
+        for (int i = tid + TRA_NT; i < nSd; i += TRA_NT) { sSd[i] = m.sdv[(size_t)c0 * ME_ + i]; sMl[i] = m.mltc[(size_t)c0 * ME_ + i]; }
+        if (DIFF)
+            for (int i = tid + TRA_NT; i < nSd; i += TRA_NT) sDd[i] = a.dvdc[(size_t)c0 * ME_ + i];
+        for (int i = tid + TRA_NT; i < nc; i += TRA_NT) sIa[i] = m.invArea[c0 + i];
+    }
+    for (int j0 = 0; j0 < a.nT; j0 += chunk) {
+        const int cj = min(chunk, a.nT - j0);
+        if (j0 > 0) {
+            __syncthreads();                      // the previous pass has read its rows
+            stage_rows(1, j0, cj);
+        }
+        __syncthreads();
+        if (!act) continue;
+        for (int ci = grp; ci < nc; ci += NG) {
+            const uint32_t *rec = sRec + (size_t)ci * CI;
+            const unsigned mask = rec[2 * ME_];
+            double2 w[ME_], hE[DIFF ? ME_ : 1];
+            bool ch[ME_], okx[ME_], oky[ME_];
+            uint32_t aoff[ME_], gh[ME_];
+            const double *sd = sSd + ci * ME_, *dd = sDd + ci * ME_;
+            const double2 hc = reinterpret_cast<const double2 *>(sRows + (size_t)ci * K)[l];
+            {
+                double2 uu[ME_];
+                uint32_t ah[ME_];
+                v4u_t rh[ME_];
+#pragma unroll
+                for (int i = 0; i < ME_; ++i) uu[i] = glb_row2(uG + (rec[i] + lo));
+#pragma unroll
+                for (int i = 0; i < ME_; ++i) {        // cached row or row 0 of the cache (then overwritten by the masked global load)
+                    const unsigned ho = rec[ME_ + i], loc = ho - ownB;
+                    ch[i] = loc < ownN;
+                    aoff[i] = ch[i] ? loc : 0u;
+                    gh[i] = ho + lo;
+                    asm("" : "+v"(gh[i]));             // the offset stays in a VGPR (see k_nl_prep5)
+                    ah[i] = ldsH + aoff[i];
+                }
+                lds_burst<ME_>(rh, ah);
+#pragma unroll
+                for (int i = 0; i < ME_; ++i) {
+                    double2 hh = __builtin_bit_cast(double2, rh[i]);
+                    if (!ch[i]) hh = glb_row2(hG + gh[i]);
+                    const double2 he = make_double2(0.5 * (hc.x + hh.x), 0.5 * (hc.y + hh.y));
+                    const double2 F = make_double2(uu[i].x * he.x, uu[i].y * he.y);
+                    w[i] = make_double2((0.5 * F.x) * sd[i], (0.5 * F.y) * sd[i]);
+                    if (DIFF) hE[i] = he;
+                    const int ml = sMl[ci * ME_ + i];
+                    const bool valid = (mask >> i) & 1u;
+                    okx[i] = valid && 2 * l < ml;
+                    oky[i] = valid && 2 * l + 1 < ml;
+                }
+            }
+            const double invA = sIa[ci];
+            const unsigned orow = ownB + (unsigned)ci * rowB + lo;       // the cell's own row in every (K, nC) array
+            for (int jj = 0; jj < cj; ++jj) {
+                const size_t jo = (size_t)(j0 + jj) * a.stride;
+                const double kap = DIFF ? a.kappa[j0 + jj] : 0.0;
+                const glb_bytes_t yG = (glb_bytes_t)(a.y + jo);
+                const uint32_t ldsY = ldsH + (uint32_t)(1 + jj) * (uint32_t)mC * rowB;
+                uint32_t ap[ME_];
+                v4u_t rp[ME_];
+#pragma unroll
+                for (int i = 0; i < ME_; ++i) ap[i] = ldsY + aoff[i];
+                lds_burst<ME_>(rp, ap);
+                const double2 yc = reinterpret_cast<const double2 *>(sRows + ((size_t)(1 + jj) * mC + ci) * K)[l];
+                double2 r = make_double2(0.0, 0.0);
+                double2 yy[ME_];
+#pragma unroll
+                for (int i = 0; i < ME_; ++i) {
+                    yy[i] = __builtin_bit_cast(double2, rp[i]);
+                    if (!ch[i]) yy[i] = glb_row2(yG + gh[i]);
+                }
+#pragma unroll
+                for (int i = 0; i < ME_; ++i) {
+                    double rx = r.x + w[i].x * (yc.x - yy[i].x), ry = r.y + w[i].y * (yc.y - yy[i].y);
+                    if (DIFF) {
+                        rx += ((kap * hE[i].x) * dd[i]) * (yy[i].x - yc.x);
+                        ry += ((kap * hE[i].y) * dd[i]) * (yy[i].y - yc.y);
+                    }
+                    r.x = okx[i] ? rx : r.x;
+                    r.y = oky[i] ? ry : r.y;
+                }
+                const double2 g = gload2(a.g + jo, orow);
+                const double2 sIn = a.rs == 3 ? make_double2(0.0, 0.0) : gload2(a.S + jo, orow);
+                double2 sOut, out;
+                tracer_adj_update(a, r.x, hc.x, invA, g.x, sIn.x, sOut.x, out.x);
+                tracer_adj_update(a, r.y, hc.y, invA, g.y, sIn.y, sOut.y, out.y);
+                if (a.rs > 0) gstore2(a.S + jo, orow, sOut);
+                gstore2(a.out + jo, orow, out);
+            }
+        }
+    }
+}
+
+// The reverse kernels stage what the forward ones do (ph rows and one gathered row set per resident tracer, the same records), so the
+// form, the LDS size and the chunk are tracer_kernel's: one decision for both directions.
+TracerKernel tracer_adjoint_kernel(const MeshDev &m, int lpc, int nT, bool generic, bool diff)
+{
+    return tracer_kernel(m, lpc, nT, generic, diff);
+}
+
+hipError_t launch_tracer_adj_seed(const MeshDev &m, const double *X, const double *hn, double *g, double *y, double b4, int nT,
+                                  hipStream_t s)
+{
+    if (nT <= 0) return hipSuccess;
+    const int64_t stride = (int64_t)m.K * m.nC, n = stride * nT;
+    const int grid = (int)std::min<int64_t>(std::max<int64_t>((n + BLOCK - 1) / BLOCK, 1), 65536);
+    hipLaunchKernelGGL(k_tracer_adj_seed, dim3(grid), dim3(BLOCK), 0, s, X, hn, m.invArea, g, y, b4, m.K, stride, n);
+    return hipGetLastError();
+}
+
+template <int LPC, bool DIFF>
+static hipError_t launch_tracer_adj_cell(const MeshDev &m, const TracerAdjArgs &a, hipStream_t s)
+{
+    const int ng = BLOCK / LPC;
+    const int grid = std::min(std::max((m.nC + ng - 1) / ng, 1), 65536);
+    hipLaunchKernelGGL((k_tracer_adj_cell<LPC, DIFF>), dim3(grid), dim3(BLOCK), 0, s, m, a);
+    return hipGetLastError();
+}
+
+template <bool DIFF>
+static hipError_t launch_tracer_adj_patch(const MeshDev &m, const TracerAdjArgs &a, const TracerKernel &k, hipStream_t s)
+{
+    if (k.lds > 64 * 1024)
+        if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_tracer_adj_patch<6, DIFF>)}, 80 * 1024); e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_tracer_adj_patch<6, DIFF>), dim3(patch_grid(m)), dim3(TRA_NT), k.lds, s, m, a, k.chunk);
+    return hipGetLastError();
+}
+
+template <bool DIFF>
+static hipError_t launch_tracer_adj_generic(const MeshDev &m, const TracerAdjArgs &a, int lpc, hipStream_t s)
+{
+#define CALL(L) launch_tracer_adj_cell<L, DIFF>(m, a, s)
+    DISPATCH_LPC(lpc, CALL)
+#undef CALL
+}
+
+hipError_t launch_tracer_adjoint(const MeshDev &m, const TracerAdjArgs &a, int lpc, bool generic, hipStream_t s)
+{
+    if (a.nT <= 0) return hipSuccess;
+    const bool diff = a.kappa != nullptr;       // (then a.dvdc is set too: moka_tracer_adjoint_sweep)
+    const TracerKernel k = tracer_adjoint_kernel(m, lpc, a.nT, generic, diff);
+    if (k.form == 1) return diff ? launch_tracer_adj_patch<true>(m, a, k, s) : launch_tracer_adj_patch<false>(m, a, k, s);
+    return diff ? launch_tracer_adj_generic<true>(m, a, lpc, s) : launch_tracer_adj_generic<false>(m, a, lpc, s);
+}
+
+}  // namespace moka

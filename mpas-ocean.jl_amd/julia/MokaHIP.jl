@@ -545,4 +545,51 @@ function gradient!(t::Tape, d_ssh::Vector{Float64}, d_u::Matrix{Float64}, d_h::M
     end
 end
 
+# reverse mode of the passive tracers over a frozen flow (include/moka_hip.h states the algebra): the gradient of a functional of the
+# final tracers with respect to the tracers at the start of the first recorded step -- linear, nonlinear, Del2 and Del4 dycores alike.
+mutable struct TracerTape
+    handle::Ptr{Cvoid}
+    state::State
+end
+function TracerTape(Prog::MProg, capacity::Integer)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    ref = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:moka_tracer_tape_create, lib), Cint, (Ptr{Cvoid}, Int64, Ref{Ptr{Cvoid}}), s.handle, capacity, ref), s.backend.ctx)
+    t = TracerTape(ref[], s)           # holds the state (hence mesh and context count) alive
+    retain!(s.backend)
+    s.tapes += 1
+    finalizer(t) do x
+        ccall((:moka_tracer_tape_destroy, lib), Cvoid, (Ptr{Cvoid},), x.handle)
+        x.state.tapes -= 1
+        x.state.dead && x.state.tapes == 0 && destroy_state!(x.state)
+        release!(x.state.backend)
+    end
+    t
+end
+function step_rk4!(t::TracerTape, dt)
+    check(ccall((:moka_step_rk4_tracer_taped, lib), Cint, (Ptr{Cvoid}, Cdouble), t.handle, dt), t.state.backend.ctx)
+    device_changed!(t.state)
+end
+function recorded_steps(t::TracerTape)
+    n = Ref{Int64}(0)
+    check(ccall((:moka_tracer_tape_steps, lib), Cint, (Ptr{Cvoid}, Ref{Int64}), t.handle, n), t.state.backend.ctx)
+    Int(n[])
+end
+"seeds[j] (a (nVertLevels, nCells) matrix, or nothing for zero) = d J / d tracer j at the end; grads[j] receives d J / d tracer j at the start"
+function gradient!(t::TracerTape, grads::Vector{Matrix{Float64}}, seeds::Vector)
+    ctx = t.state.backend.ctx
+    for (j, a) in enumerate(seeds)
+        p = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+        GC.@preserve a check(ccall((:moka_tracer_adjoint_seed, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), t.handle, j - 1, p), ctx)
+    end
+    check(ccall((:moka_tracer_adjoint_sweep, lib), Cint, (Ptr{Cvoid},), t.handle), ctx)
+    for (j, a) in enumerate(grads)
+        check(ccall((:moka_tracer_adjoint_download, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), t.handle, j - 1, a), ctx)
+    end
+    grads
+end
+# 1 the patch form, 2 the generic form of the reverse tracer kernel served the last reverse stage, 0 none yet
+tracer_adjoint_path(t::TracerTape) = Int(ccall((:moka_tracer_adjoint_path, lib), Cint, (Ptr{Cvoid},), t.handle))
+
 end # module

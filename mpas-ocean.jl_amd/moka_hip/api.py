@@ -30,7 +30,7 @@ __all__ = [
     "Clock", "OneTimeAlarm", "PeriodicAlarm", "Alarm", "advance", "isRinging", "reset", "stop", "changeTimeStep",
     "attachAlarm", "setCurrentTime", "ocn_setup_clock", "ocn_setup_mesh", "ocn_init", "write_netcdf",
     "ConfigRead", "ConfigGet", "GlobalConfig", "AdjointTape", "set_nonlinear", "REFERENCE_COMPAT", "prognostic_vars_best_placement",
-    "set_tracers", "Tracers",
+    "set_tracers", "Tracers", "TracerAdjointTape",
 ]
 
 MokaError = L.MokaError
@@ -707,6 +707,66 @@ class AdjointTape:
     def close(self):
         if self._h:
             _release(self, L.lib().moka_tape_destroy, self._h)
+            self._h = C.c_void_p()
+
+
+class TracerAdjointTape:
+    """Reverse mode of the passive tracers over a frozen flow (moka_tracer_tape_*; include/moka_hip.h states the algebra): record RK4
+    steps of a model with tracers, then turn d J / d (tracers after the last step) into d J / d (tracers before the first recorded
+    step), the flow held as it ran.  The tracer step is linear in the tracers, so this is an exact transpose; it works over the
+    linear, nonlinear, Del2 and Del4 dycores alike.  Sensitivities to the flow or to the diffusivities are out of scope."""
+
+    def __init__(self, Prog: "PrognosticVars", capacity_steps: int):
+        self._state = Prog._state
+        self._ctx = self._state.mesh.backend._h
+        self._shape = tuple(Prog.layerThickness[-1].shape)
+        self._h = C.c_void_p()
+        L.check(L.lib().moka_tracer_tape_create(self._state._h, int(capacity_steps), C.byref(self._h)), self._ctx)
+        _own(self, L.lib().moka_tracer_tape_destroy, self._h, self._state, self._state.mesh, self._state.mesh.backend)
+        self._state._dependents.append(weakref.ref(self))
+
+    def step(self, timestep):
+        """One RK4 step of the model (bit for bit moka_step_rk4), recorded."""
+        L.check(L.lib().moka_step_rk4_tracer_taped(self._h, float(np.asarray(timestep).reshape(-1)[0])), self._ctx)
+
+    def steps(self) -> int:
+        n = C.c_int64()
+        L.check(L.lib().moka_tracer_tape_steps(self._h, C.byref(n)), self._ctx)
+        return int(n.value)
+
+    def seed(self, j: int, a):
+        """The adjoint of tracer j := a, an (nCells, K) field; None = zeros.  The first seed after a recorded step zeroes the others."""
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape != self._shape:
+                a = a.reshape(self._shape)
+        L.check(L.lib().moka_tracer_adjoint_seed(self._h, int(j), None if a is None else L.f64(a)), self._ctx)
+
+    def sweep(self):
+        """Reverse over (and pop) every recorded step; the tape is then empty and reusable."""
+        L.check(L.lib().moka_tracer_adjoint_sweep(self._h), self._ctx)
+
+    def download(self, j: int) -> np.ndarray:
+        """The adjoint of tracer j as it stands (after a sweep: the gradient), caller's numbering."""
+        out = np.empty(self._shape, dtype=np.float64)
+        L.check(L.lib().moka_tracer_adjoint_download(self._h, int(j), L.f64(out)), self._ctx)
+        return out
+
+    def gradient(self, seeds) -> list:
+        """seeds: one entry per tracer, None meaning zero.  Seeds, sweeps and returns the list of gradients."""
+        seeds = list(seeds)
+        for j, a in enumerate(seeds):
+            self.seed(j, a)
+        self.sweep()
+        return [self.download(j) for j in range(len(seeds))]
+
+    def path(self) -> int:
+        """moka_tracer_adjoint_path: 1 the patch form, 2 the generic form of the reverse kernel, 0 before the first reverse stage."""
+        return int(L.lib().moka_tracer_adjoint_path(self._h))
+
+    def close(self):
+        if self._h:
+            _release(self, L.lib().moka_tracer_tape_destroy, self._h)
             self._h = C.c_void_p()
 
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""VGPR / SGPR / spill / LDS figures of the library's kernels from the compiler's own metadata (no GPU needed).
+"""VGPR / SGPR / spill / scratch / LDS figures of the library's kernels from the compiler's own metadata (no GPU needed).
 
     python3 tools/kernel_regs.py [pattern]        # default pattern: rec2c
 
@@ -30,6 +30,6 @@ for b in txt.split("- .agpr_count:")[1:]:
         dem = name
     if pat in dem:
         rows.append((dem.split("(")[0], int(g("vgpr_count")), int(g("sgpr_count")), int(g("vgpr_spill_count")),
-                     int(g("group_segment_fixed_size"))))
+                     int(g("group_segment_fixed_size")), int(g("private_segment_fixed_size"))))
 for r in sorted(rows):
-    print(f"{r[0]:75s} vgpr {r[1]:4d}  sgpr {r[2]:4d}  spill {r[3]:4d}  static LDS {r[4]}")
+    print(f"{r[0]:75s} vgpr {r[1]:4d}  sgpr {r[2]:4d}  spill {r[3]:4d}  scratch {r[5]:4d}  static LDS {r[4]}")
