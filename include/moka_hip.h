@@ -543,14 +543,22 @@ int  moka_state_del4_path(const moka_state *st);
  * stale: the contents Q exist inside a step only); layerThickness must be nonzero.  The tracers' time levels rotate with the state's
  * (moka_step_rk4, moka_run(MOKA_RUNGE_KUTTA_4), moka_advance_time_levels).  Tracers never feed back: the dycore's fields are, bit for bit,
  * those of a state without tracers, and moka_tendencies is unchanged.
+ * Sources (moka_tracer_source_upload; default none).  Tracer j may carry a source q_j[k,c] in tracer * m/s, the rate of change of the
+ * content h phi, constant in time until it is changed:
+ *   d(h phi)/dt = -div(F phi_e) + div(kappa_j h_e grad phi) + q_j.
+ * For every stage tendency, after the whole slot loop (advective and diffusive additions), one more addition follows with a rounding
+ * of its own:   T = T + q_j[k,c].   The RK4 recipe below is untouched, and all four stages see the same q.  Hence: T is never -0.0
+ * before that addition, so a source that is zero everywhere (+0.0 or -0.0) leaves every bit of the tracer unchanged; a tracer without a
+ * source beside sourced ones has the bits of a state that never had a source (it reads no source and adds nothing); the dycore never
+ * sees tracers, so the flow is unchanged bit for bit; and the unit tracer stays exactly 1.0 while it has no source.
  * moka_set_tracers allocates the arrays (zeros; any earlier tracers are dropped); 0 frees them and restores the behaviour of a state
  * that never had any.  MOKA_ERR_ARG for a negative count; MOKA_ERR_UNSUPPORTED for fp32-storage states, partitioned meshes and states
  * that have a halo or a tape.  While nTracers > 0, moka_step_fe, moka_run(MOKA_FORWARD_EULER), moka_tape_create, moka_halo_create and
  * the moka_rk4_dist_* calls return MOKA_ERR_UNSUPPORTED, and moka_set_tuning key 7 leaves the state on the running sum
  * (moka_state_rk4_streams: 16).  moka_state_optimize_placement neither times nor moves the tracer arrays.
  * Out of scope: upwind, FCT and higher-order edge values, biharmonic, anisotropic or spatially varying tracer diffusion, Forward Euler,
- * fp32 storage, partitioned meshes, reverse mode with respect to the flow or the diffusivities (with respect to the tracers themselves:
- * moka_tracer_tape_* below), the 13-stream form, YAML keys and NetCDF I/O of tracers, and fusing the tracer sum into the dycore's stage
+ * fp32 storage, partitioned meshes, reverse mode with respect to the flow or the diffusivities (with respect to the tracers themselves
+ * and to the sources: moka_tracer_tape_* below), time-dependent sources, point-source convenience calls, the 13-stream form, YAML keys and NetCDF I/O of tracers, and fusing the tracer sum into the dycore's stage
  * kernels. */
 int  moka_set_tracers(moka_state *st, int32_t nTracers);
 /* tracer j (0-based) at time_level 0 (previous) / 1 (current): (nVertLevels, nCells) doubles in the caller's cell numbering, like
@@ -569,6 +577,17 @@ int  moka_state_tracer_path(const moka_state *st);
 int  moka_set_tracer_diffusion(moka_state *st, const double *kappa);
 /* the diffusivity of tracer j (0-based) into *out; MOKA_ERR_ARG for j out of range */
 int  moka_tracer_diffusion(const moka_state *st, int32_t j, double *out);
+/* Tracer sources (algebra above).  host: the source of tracer j, (nVertLevels, nCells) doubles in the caller's cell numbering like
+ * moka_tracer_upload (any cell ordering of the mesh); NULL removes tracer j's source.  It takes effect with the next RK4 step or
+ * moka_run and stays until changed: the state's time levels rotate, sources do not.  MOKA_ERR_ARG for j out of range and, with nothing
+ * changed, for a NaN or infinite value.  Only sourced tracers own a device array; while no tracer has a source the tracer launches are
+ * those of a state that never had one.  moka_set_tracers (any count, 0 included) drops every source, as it resets the diffusivities.
+ * moka_state_tracer_path answers as without sources: a source is read from global memory, never staged. */
+int  moka_tracer_source_upload(moka_state *st, int32_t j, const double *host);
+/* the source of tracer j into host (zeros when tracer j has none); MOKA_ERR_ARG for j out of range or a NULL host */
+int  moka_tracer_source_download(moka_state *st, int32_t j, double *host);
+/* *out = 1 when tracer j has a source, else 0; MOKA_ERR_ARG for j out of range or a NULL out */
+int  moka_tracer_has_source(const moka_state *st, int32_t j, int *out);
 
 /* ---- reverse mode of passive tracer transport over a frozen flow (extension) ---------------------------------------
  * Once the flow is given the tracer step above is linear in phi, so d J(phi_N) / d phi_0 is the exact transpose of a linear map.  It
@@ -595,9 +614,19 @@ int  moka_tracer_diffusion(const moka_state *st, int32_t j, double *out);
  * beside diffused tracers has the bits of the undiffused sweep (adding +-0.0 never changes r, by the forward argument); and a sweep
  * whose recorded steps all have every kappa == 0 launches the instances without diffusion.
  * The result is the gradient with respect to the tracer fields at the start of the first recorded step, the flow held as it ran.
+ * Gradient with respect to the sources (moka_tracer_adjoint_want_source_gradient).  Let tau_3 = b[3] * g and, for s = 3, 2, 1,
+ * tau_{s-1} = b[s-1] * g + a[s-1] * v: exactly the values the lines above multiply by invA (y = tau * invA keeps its bits; no
+ * contraction, no reordering).  tau_s is the adjoint of stage s's tendency and, since T = (slot sum) + q, of q.  Per recorded step, in
+ * this order, for every tracer whose gradient is wanted, each addition with its own rounding:
+ *   G = G + tau_3  (with g);   G = G + tau_2  (reverse stage 3);   G = G + tau_1  (reverse stage 2);   G = G + tau_0  (reverse stage 1)
+ * -- reverse stage 0 does not touch G.  After the sweep G_j = d J / d q_j: the derivative with respect to a source that acts
+ * identically in every recorded step, the flow held as it ran.  Hence: G depends neither on the sources the forward run had nor on
+ * phi (the tape records nothing new), so two runs that differ only in q give the same G and the same X bit for bit; asking for G
+ * changes no bit of X; a zero seed gives G == 0 exactly; and the map is affine in q, so
+ *   <X, phi_N(phi_0, q) - phi_N(phi_0, 0)> = <G, q>   up to round-off.
  * Usage: tracer_tape_create -> n x step_rk4_tracer_taped -> seed (per tracer) -> sweep -> download (per tracer).
- * Out of scope: sensitivities of the tracers to the flow (d phi_N / d (u, h)) and to kappa, coupling to moka_tape, Forward Euler,
- * partitioned meshes, fp32 storage. */
+ * Out of scope: sensitivities of the tracers to the flow (d phi_N / d (u, h)) and to kappa, time-dependent sources and a per-step
+ * split of G, coupling to moka_tape, Forward Euler, partitioned meshes, fp32 storage. */
 typedef struct moka_tracer_tape moka_tracer_tape;
 /* MOKA_ERR_UNSUPPORTED on a state without tracers, MOKA_ERR_ARG for NULL arguments or a negative capacity.  The tape remembers the
  * state's tracer count and counts as a tape of the state: while it lives, moka_state_optimize_placement and moka_set_tracers(st, n > 0)
@@ -618,6 +647,13 @@ int  moka_tracer_adjoint_sweep(moka_tracer_tape *t);
 int  moka_tracer_adjoint_download(moka_tracer_tape *t, int32_t j, double *host);    /* X_j as it stands */
 /* which kernel served the last reverse stage: 1 the patch form, 2 the generic form (the conditions of moka_state_tracer_path), 0 none yet */
 int  moka_tracer_adjoint_path(const moka_tracer_tape *t);
+/* on != 0: the next sweeps also accumulate G_j (algebra above); 0: they no longer do (the accumulator stays readable).  May be called
+ * whenever the tape is not between a seed and its sweep (MOKA_ERR_ARG there, and for j out of range); the first call for a tracer
+ * allocates its (nVertLevels, nCells) accumulator.  The first seed after a recorded step zeroes every G, as it zeroes X.  A sweep in
+ * which no gradient is wanted launches the kernels of a tape that never asked for one. */
+int  moka_tracer_adjoint_want_source_gradient(moka_tracer_tape *t, int32_t j, int on);
+/* G_j as it stands, in the caller's cell numbering; MOKA_ERR_ARG for j out of range, a NULL host, or a tracer that was never flagged */
+int  moka_tracer_adjoint_source_download(moka_tracer_tape *t, int32_t j, double *host);
 
 /* ---- reverse mode of the Forward-Euler loop ----------------------------------------------------------------
  * The reference gets d sum(ssh^2) / d (initial normalVelocity, layerThickness) from Enzyme over ocn_run_loop

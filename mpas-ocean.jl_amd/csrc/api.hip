@@ -1437,6 +1437,7 @@ static hipError_t tracer_stage(moka_state *st, int s, const StageArgs &g)
     t.cphi = st->trPhi[1]; t.qn = st->trPhi[0];
     t.a = g.a; t.b = g.b;
     t.kappa = st->trKappaDev; t.dvdc = st->trKappaDev ? mm->dvdc : nullptr;
+    t.src = st->trSrcDev;
     const MeshDev dev = launch_bounds(mm);
     const bool generic = st->ctx->variant == 3;
     st->tracerPath = tracer_kernel(dev, mm->lpc, t.nT, generic, t.kappa != nullptr).form;
@@ -1455,7 +1456,13 @@ struct moka_tracer_tape {
     double *kap = nullptr;                           // capacity x nT: the diffusivities on the device
     std::vector<double> kappa, dts;                  // ... and on the host (n * nT values); dt of each step
     double *X = nullptr, *g = nullptr, *S = nullptr, *y[2] = {nullptr, nullptr};   // nT x (K, nC) each: the adjoint state and the sweep's work arrays
+    // gradient with respect to the sources (moka_tracer_adjoint_want_source_gradient): the (K, nC) accumulator of every tracer that was
+    // ever flagged (nullptr otherwise), whether it is wanted now, and the device table of the wanted ones that the sweep's launches read
+    std::vector<double *> G;
+    std::vector<char> wantG;
+    double **Gdev = nullptr;
     bool seeded = false;
+    bool pending = false;                            // seeded and not yet swept
     int path = 0;                                    // moka_tracer_adjoint_path
     std::vector<void *> allocs;
     bool counted = false;                            // st->attached includes this tape
@@ -1743,6 +1750,81 @@ int moka_set_viscosity_del4(moka_state *st, double viscDel4, const double *meshS
 
 int moka_state_del4_path(const moka_state *st) { return st ? st->del4Path : 0; }
 
+// ---- tracer sources: d(h phi_j)/dt gains q_j[k,c], constant in time until changed (include/moka_hip.h) ----
+static void state_free(moka_state *st, void *q)
+{
+    st->allocs.erase(std::remove(st->allocs.begin(), st->allocs.end(), q), st->allocs.end());
+    (void)hipFree(q);
+}
+
+// the caller has synchronised the stream: no launch reads the table or a source
+static void drop_sources(moka_state *st)
+{
+    for (double *q : st->trSrc)
+        if (q) state_free(st, q);
+    st->trSrc.clear();
+    if (st->trSrcDev) state_free(st, st->trSrcDev);
+    st->trSrcDev = nullptr;
+}
+
+int moka_tracer_source_upload(moka_state *st, int32_t j, const double *host)
+{
+    if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
+    if (j < 0 || j >= st->nTracers) return fail(st->ctx, MOKA_ERR_ARG, "tracer index out of range (moka_set_tracers)");
+    const Plan &p = st->mesh->plan;
+    const size_t nCK = (size_t)p.K * p.nC;
+    for (size_t i = 0; host && i < nCK; ++i)
+        if (!std::isfinite(host[i])) return fail(st->ctx, MOKA_ERR_ARG, "tracer source: every value must be finite");
+    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));      // no launch is reading the old table or the old values
+    const bool had = !st->trSrc.empty() && st->trSrc[j];
+    if (!host) {
+        if (!had) return MOKA_OK;
+        state_free(st, st->trSrc[j]);
+        st->trSrc[j] = nullptr;
+        if (std::all_of(st->trSrc.begin(), st->trSrc.end(), [](double *q) { return !q; })) {
+            drop_sources(st);
+            return MOKA_OK;
+        }
+    } else {
+        if (!had) {
+            double *d = nullptr;
+            if (int rc = alloc_field(st, &d, nCK)) return rc;
+            if (!st->trSrcDev)
+                if (int rc = alloc_field(st, reinterpret_cast<double **>(&st->trSrcDev), (size_t)st->nTracers, sizeof(double *))) {
+                    (void)hipStreamSynchronize(st->ctx->stream);
+                    state_free(st, d);
+                    return rc;
+                }
+            st->trSrc.resize((size_t)st->nTracers, nullptr);
+            st->trSrc[j] = d;
+        }
+        if (int rc = put_rows(st->mesh, st->trSrc[j], host, MOKA_CELL, p.nC, p.K)) return rc;
+    }
+    return h2d(st->ctx, st->trSrcDev, st->trSrc.data(), st->trSrc.size() * sizeof(double *));
+}
+
+int moka_tracer_source_download(moka_state *st, int32_t j, double *host)
+{
+    if (!st || !host) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    if (j < 0 || j >= st->nTracers) return fail(st->ctx, MOKA_ERR_ARG, "tracer index out of range (moka_set_tracers)");
+    const Plan &p = st->mesh->plan;
+    if (st->trSrc.empty() || !st->trSrc[j]) {
+        std::fill(host, host + (size_t)p.K * p.nC, 0.0);
+        return MOKA_OK;
+    }
+    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    return get_rows(st->mesh, host, st->trSrc[j], MOKA_CELL, p.nC, p.K);
+}
+
+int moka_tracer_has_source(const moka_state *st, int32_t j, int *out)
+{
+    if (!st || !out) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    if (j < 0 || j >= st->nTracers) return fail(st->ctx, MOKA_ERR_ARG, "tracer index out of range (moka_set_tracers)");
+    *out = !st->trSrc.empty() && st->trSrc[j] ? 1 : 0;
+    return MOKA_OK;
+}
+
 int moka_set_tracers(moka_state *st, int32_t nTracers)
 {
     if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
@@ -1758,6 +1840,7 @@ int moka_set_tracers(moka_state *st, int32_t nTracers)
     HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));
     double **arr[5] = {&st->trPhi[0], &st->trPhi[1], &st->trProv[0], &st->trProv[1], &st->trKappaDev};
     auto release = [&]() {
+        drop_sources(st);                // every source goes with the tracers
         for (double **q : arr) {
             if (!*q) continue;
             st->allocs.erase(std::remove(st->allocs.begin(), st->allocs.end(), (void *)*q), st->allocs.end());
@@ -1877,6 +1960,8 @@ int moka_tracer_tape_create(moka_state *st, int64_t capacity_steps, moka_tracer_
     if (!t) return fail(st->ctx, MOKA_ERR_ALLOC, "out of host memory");
     t->st = st; t->ctx = st->ctx;
     t->nT = st->nTracers;
+    t->G.assign((size_t)t->nT, nullptr);
+    t->wantG.assign((size_t)t->nT, 0);
     t->capacity = capacity_steps;
     const size_t nEK = (size_t)p.K * p.nE, nCK = (size_t)p.K * p.nC, cap = (size_t)capacity_steps;
     int rc = MOKA_OK;
@@ -1924,6 +2009,7 @@ int moka_step_rk4_tracer_taped(moka_tracer_tape *t, double dt)
     t->dts.push_back(dt);
     ++t->n;
     t->seeded = false;
+    t->pending = false;
     return MOKA_OK;
 }
 
@@ -1950,8 +2036,13 @@ int moka_tracer_adjoint_seed(moka_tracer_tape *t, int32_t j, const double *host)
     if (int rc = ttape_field(t, j, &d)) return rc;
     const Plan &p = t->st->mesh->plan;
     const size_t nCK = (size_t)p.K * p.nC;
-    if (!t->seeded) HIPCHK(t->ctx, hipMemsetAsync(t->X, 0, nCK * t->nT * sizeof(double), t->ctx->stream));
+    if (!t->seeded) {
+        HIPCHK(t->ctx, hipMemsetAsync(t->X, 0, nCK * t->nT * sizeof(double), t->ctx->stream));
+        for (double *G : t->G)
+            if (G) HIPCHK(t->ctx, hipMemsetAsync(G, 0, nCK * sizeof(double), t->ctx->stream));
+    }
     t->seeded = true;
+    t->pending = true;
     if (!host) {
         HIPCHK(t->ctx, hipMemsetAsync(d, 0, nCK * sizeof(double), t->ctx->stream));
         return MOKA_OK;
@@ -1975,13 +2066,15 @@ int moka_tracer_adjoint_sweep(moka_tracer_tape *t)
     const MeshDev dev = launch_bounds(mm);
     const bool generic = t->ctx->variant == 3;
     const size_t nEK = (size_t)p.K * p.nE, nCK = (size_t)p.K * p.nC;
+    double *const *G = std::any_of(t->wantG.begin(), t->wantG.end(), [](char w) { return w != 0; }) ? t->Gdev : nullptr;
+    t->pending = false;
     while (t->n > 0) {
         const int64_t n = t->n - 1;
         const double dt = t->dts[n];
         const double a[3] = {dt / 2., dt / 2., dt};
         const double b[4] = {dt / 6., dt / 3., dt / 3., dt / 6.};
         int cur = 0;
-        HIPCHK(t->ctx, launch_tracer_adj_seed(dev, t->X, t->hn + nCK * n, t->g, t->y[cur], b[3], t->nT, s));
+        HIPCHK(t->ctx, launch_tracer_adj_seed(dev, t->X, t->hn + nCK * n, t->g, t->y[cur], b[3], t->nT, G, s));
         for (int rs = 3; rs >= 0; --rs) {
             TracerAdjArgs q{};
             q.nT = t->nT; q.rs = rs; q.stride = (int64_t)nCK;
@@ -1991,6 +2084,7 @@ int moka_tracer_adjoint_sweep(moka_tracer_tape *t)
             q.cb = rs > 0 ? b[rs - 1] : 0.0; q.ca = rs > 0 ? a[rs - 1] : 0.0;
             q.kappa = diff ? t->kap + (size_t)n * t->nT : nullptr;
             q.dvdc = diff ? mm->dvdc : nullptr;
+            q.G = rs > 0 ? G : nullptr;         // reverse stage 0 does not touch G
             t->path = tracer_adjoint_kernel(dev, mm->lpc, q.nT, generic, diff).form;
             HIPCHK(t->ctx, launch_tracer_adjoint(dev, q, mm->lpc, generic, s));
             cur ^= 1;
@@ -2009,6 +2103,35 @@ int moka_tracer_adjoint_download(moka_tracer_tape *t, int32_t j, double *host)
     if (!host) return fail(t->ctx, MOKA_ERR_ARG, "NULL argument");
     const Plan &p = t->st->mesh->plan;
     return get_rows(t->st->mesh, host, d, MOKA_CELL, p.nC, p.K);
+}
+
+int moka_tracer_adjoint_want_source_gradient(moka_tracer_tape *t, int32_t j, int on)
+{
+    if (!t) return fail(nullptr, MOKA_ERR_ARG, "tracer tape is NULL");
+    if (j < 0 || j >= t->nT) return fail(t->ctx, MOKA_ERR_ARG, "tracer index out of range (moka_tracer_tape_create)");
+    if (t->pending) return fail(t->ctx, MOKA_ERR_ARG, "tracer tape: not between a seed and its sweep");
+    HIPCHK(t->ctx, hipSetDevice(t->ctx->device));
+    const Plan &p = t->st->mesh->plan;
+    if (on && !t->G[j])
+        if (int rc = ttape_alloc(t, &t->G[j], (size_t)p.K * p.nC)) return rc;
+    if (!t->Gdev)
+        if (int rc = ttape_alloc(t, reinterpret_cast<double **>(&t->Gdev), (size_t)t->nT * sizeof(double *) / sizeof(double))) return rc;
+    t->wantG[j] = on ? 1 : 0;
+    std::vector<double *> tab((size_t)t->nT, nullptr);
+    for (int i = 0; i < t->nT; ++i) tab[i] = t->wantG[i] ? t->G[i] : nullptr;
+    HIPCHK(t->ctx, hipStreamSynchronize(t->ctx->stream));        // no launch is reading the old table
+    return h2d(t->ctx, t->Gdev, tab.data(), tab.size() * sizeof(double *));
+}
+
+int moka_tracer_adjoint_source_download(moka_tracer_tape *t, int32_t j, double *host)
+{
+    if (!t) return fail(nullptr, MOKA_ERR_ARG, "tracer tape is NULL");
+    if (j < 0 || j >= t->nT) return fail(t->ctx, MOKA_ERR_ARG, "tracer index out of range (moka_tracer_tape_create)");
+    if (!host) return fail(t->ctx, MOKA_ERR_ARG, "NULL argument");
+    if (!t->G[j]) return fail(t->ctx, MOKA_ERR_ARG, "tracer tape: no source gradient was asked for this tracer (moka_tracer_adjoint_want_source_gradient)");
+    HIPCHK(t->ctx, hipSetDevice(t->ctx->device));
+    const Plan &p = t->st->mesh->plan;
+    return get_rows(t->st->mesh, host, t->G[j], MOKA_CELL, p.nC, p.K);
 }
 
 int moka_tracer_adjoint_path(const moka_tracer_tape *t) { return t ? t->path : 0; }

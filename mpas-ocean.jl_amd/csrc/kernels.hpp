@@ -200,6 +200,10 @@ struct TracerArgs {
     // harmonic diffusion (moka_set_tracer_diffusion): nT diffusivities and the plan's (nC, ME) dvEdge / dcEdge per slot; both nullptr
     // while every diffusivity of the state is zero (the launch is then the one of a state that never set any)
     const double *kappa, *dvdc;
+    // sources (moka_tracer_source_upload): nT device pointers, tracer j's (K, nC) source or nullptr for a tracer without one; the
+    // table itself is nullptr while no tracer of the state has a source (the launch is then the one of a state that never had any).
+    // After the slot loop T = T + q[k,c], the cell's own element, read from global memory.
+    const double *const *src;
 };
 // The kernel that serves a tracer launch, chosen in one place for the launcher and for moka_state_tracer_path.  form 1: k_tracer_patch
 // (even 34 <= K <= 64, hexagon-width byte-offset records, which exist only where every field's rows stay below 4 GiB; `chunk` tracers'
@@ -228,13 +232,18 @@ struct TracerAdjArgs {
     double *out;
     double cb, ca;                // b[rs - 1], a[rs - 1] (unused by rs 0)
     const double *kappa, *dvdc;   // as in TracerArgs; both nullptr in a sweep whose recorded steps all have every diffusivity zero
+    // gradient with respect to the sources (moka_tracer_adjoint_want_source_gradient): nT device pointers, tracer j's (K, nC)
+    // accumulator or nullptr where none is wanted; the table is nullptr in a sweep that wants none.  rs > 0 adds tau = cb * g + ca * v,
+    // the value `out` multiplies by invA, to the cell's own element: G = G + tau.  rs == 0 does not touch G.
+    double *const *G;
 };
 // the kernel that serves a reverse stage, for the launcher and for moka_tracer_adjoint_path: the forward choice (same rows in LDS)
 TracerKernel tracer_adjoint_kernel(const MeshDev &m, int lpc, int nT, bool generic, bool diff);
 hipError_t launch_tracer_adjoint(const MeshDev &m, const TracerAdjArgs &a, int lpc, bool generic, hipStream_t s);
 // g = X / hn and y = (b4 * g) * invArea, elementwise over nT fields: the head of a reverse step
+// G: TracerAdjArgs::G (nullptr: no gradient wanted); the head adds tau_3 = b4 * g, the value y multiplies by invArea
 hipError_t launch_tracer_adj_seed(const MeshDev &m, const double *X, const double *hn, double *g, double *y, double b4, int nT,
-                                  hipStream_t s);
+                                  double *const *G, hipStream_t s);
 
 // ---- reverse mode of one Forward-Euler step: gather form, the oracle's summation order ----
 struct AdjMesh {

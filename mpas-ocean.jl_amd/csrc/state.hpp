@@ -120,6 +120,12 @@ struct moka_state {
     // tracer launches read -- nullptr while every value is zero: the launches are then those of a state that never set any
     std::vector<double> trKappa;
     double *trKappaDev = nullptr;
+    // tracer sources (moka_tracer_source_upload): only a sourced tracer owns a (K, nC) device array.  trSrc holds nTracers pointers
+    // (nullptr = no source) and is empty while no tracer has a source; trSrcDev is its copy on the device, the table the tracer
+    // launches read -- nullptr while trSrc is empty: the launches are then those of a state that never had a source.  Sources do
+    // not rotate with the time levels.
+    std::vector<double *> trSrc;
+    double **trSrcDev = nullptr;
     std::vector<void *> allocs;
     // objects that hold or have exported the addresses of this state's arrays (halos, tapes): while any exists the arrays stay
     // where they are (moka_state_optimize_placement refuses)

@@ -12,37 +12,47 @@ namespace moka {
 //     DIFF:  r += ((kappa[j] * hE) * dvdc[c,i]) * (y[k,c'] - y[k,c])       a second, separate addition
 // -- sdv of the edge seen from c' is -sdv[c,i] and the mask belongs to the edge, so the scatter of the forward sum folds into the
 // difference; no atomics, the forward launch's streams.  What a reverse stage does with r: TracerAdjArgs (kernels.hpp).
+// SG (moka_tracer_adjoint_want_source_gradient): the head kernel and the reverse stages 3, 2, 1 add tau, the value they multiply by
+// invArea to form the next gathered field, to the accumulator of every tracer whose entry of TracerAdjArgs::G is not nullptr --
+// one read and one write of the cell's own element, nothing staged; y = tau * invA keeps its bits.  SG == false is the code of a sweep
+// that wants no gradient.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void tracer_adj_update(const TracerAdjArgs &a, double r, double hc, double invA, double g, double sIn,
-                                                  double &sOut, double &out)
+                                                  double &sOut, double &out, double &tau)
 {
     if (a.rs == 0) {
         sOut = sIn;
         out = hc * (g + sIn) + r;
+        tau = 0.0;
         return;
     }
     const double v = r / hc;
     sOut = a.rs == 3 ? v : sIn + v;
-    out = (a.cb * g + a.ca * v) * invA;
+    tau = a.cb * g + a.ca * v;
+    out = tau * invA;
 }
 
 constexpr int TRA_NT = 256;   // threads of a k_tracer_adj_patch workgroup
 constexpr int TRA_TJ = 4;     // tracers whose sums a lane of k_tracer_adj_cell carries at once (the slot's factor is formed once per TRA_TJ)
 
 // g = X / hn and the first gathered field y = (b4 * g) * invArea of a reverse step: elementwise over (tracer, cell, level)
+template <bool SG>
 __global__ __launch_bounds__(BLOCK) void k_tracer_adj_seed(const double *X, const double *hn, const double *invArea, double *g, double *y,
-                                                           double b4, int K, int64_t stride, int64_t n)
+                                                           double b4, int K, int64_t stride, int64_t n, double *const *G)
 {
     for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
         const int64_t off = i % stride;
         const double gg = X[i] / hn[off];
         g[i] = gg;
-        y[i] = (b4 * gg) * invArea[off / K];
+        const double tau = b4 * gg;
+        y[i] = tau * invArea[off / K];
+        if (SG)
+            if (double *G_ = G[i / stride]) G_[off] += tau;
     }
 }
 
 // Generic form: LPC lanes span a column, one cell per lane group, index records; any K, any maxEdges (the shape of k_tracer_cell).
-template <int LPC, bool DIFF>
+template <int LPC, bool DIFF, bool SG>
 __global__ __launch_bounds__(BLOCK) void k_tracer_adj_cell(const MeshDev m, const TracerAdjArgs a)
 {
     constexpr int NG = BLOCK / LPC;
@@ -82,10 +92,12 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_adj_cell(const MeshDev m, cons
                 for (int jj = 0; jj < TRA_TJ; ++jj)
                     if (jj < nj) {
                         const size_t joff = (size_t)(j0 + jj) * a.stride + off;
-                        double sOut, out;
-                        tracer_adj_update(a, r[jj], hc, invA, a.g[joff], a.rs == 3 ? 0.0 : a.S[joff], sOut, out);
+                        double sOut, out, tau;
+                        tracer_adj_update(a, r[jj], hc, invA, a.g[joff], a.rs == 3 ? 0.0 : a.S[joff], sOut, out, tau);
                         if (a.rs > 0) a.S[joff] = sOut;
                         a.out[joff] = out;
+                        if (SG && a.rs > 0)
+                            if (double *G_ = a.G[j0 + jj]) G_[off] += tau;
                     }
             }
         }
@@ -97,7 +109,7 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_adj_cell(const MeshDev m, cons
 // staged in LDS (the forward kernel's layout, hence its LDS formula and its chunking: tracer_kernel); a cell reads its neighbours'
 // cached rows in one burst and overwrites the lanes of foreign rows with masked global loads by byte offset.  The slot factors
 // (0.5 * F) * sdv are formed once per cell and pass and reused by the tracer loop; v = r / ph_s and ph_0 * (g + S) use the staged own row.
-template <int ME_, bool DIFF>
+template <int ME_, bool DIFF, bool SG>
 __global__ __launch_bounds__(TRA_NT, 2) void k_tracer_adj_patch(const MeshDev m, const TracerAdjArgs a, const int chunk)
 {
     constexpr int NG = TRA_NT / 32;
@@ -243,11 +255,16 @@ __global__ __launch_bounds__(TRA_NT, 2) void k_tracer_adj_patch(const MeshDev m,
                 }
                 const double2 g = gload2(a.g + jo, orow);
                 const double2 sIn = a.rs == 3 ? make_double2(0.0, 0.0) : gload2(a.S + jo, orow);
-                double2 sOut, out;
-                tracer_adj_update(a, r.x, hc.x, invA, g.x, sIn.x, sOut.x, out.x);
-                tracer_adj_update(a, r.y, hc.y, invA, g.y, sIn.y, sOut.y, out.y);
+                double2 sOut, out, tau;
+                tracer_adj_update(a, r.x, hc.x, invA, g.x, sIn.x, sOut.x, out.x, tau.x);
+                tracer_adj_update(a, r.y, hc.y, invA, g.y, sIn.y, sOut.y, out.y, tau.y);
                 if (a.rs > 0) gstore2(a.S + jo, orow, sOut);
                 gstore2(a.out + jo, orow, out);
+                if (SG && a.rs > 0)
+                    if (double *G_ = a.G[j0 + jj]) {
+                        const double2 G0 = gload2(G_, orow);
+                        gstore2(G_, orow, make_double2(G0.x + tau.x, G0.y + tau.y));
+                    }
             }
         }
     }
@@ -261,37 +278,38 @@ TracerKernel tracer_adjoint_kernel(const MeshDev &m, int lpc, int nT, bool gener
 }
 
 hipError_t launch_tracer_adj_seed(const MeshDev &m, const double *X, const double *hn, double *g, double *y, double b4, int nT,
-                                  hipStream_t s)
+                                  double *const *G, hipStream_t s)
 {
     if (nT <= 0) return hipSuccess;
     const int64_t stride = (int64_t)m.K * m.nC, n = stride * nT;
     const int grid = (int)std::min<int64_t>(std::max<int64_t>((n + BLOCK - 1) / BLOCK, 1), 65536);
-    hipLaunchKernelGGL(k_tracer_adj_seed, dim3(grid), dim3(BLOCK), 0, s, X, hn, m.invArea, g, y, b4, m.K, stride, n);
+    if (G) hipLaunchKernelGGL(k_tracer_adj_seed<true>, dim3(grid), dim3(BLOCK), 0, s, X, hn, m.invArea, g, y, b4, m.K, stride, n, G);
+    else hipLaunchKernelGGL(k_tracer_adj_seed<false>, dim3(grid), dim3(BLOCK), 0, s, X, hn, m.invArea, g, y, b4, m.K, stride, n, G);
     return hipGetLastError();
 }
 
-template <int LPC, bool DIFF>
+template <int LPC, bool DIFF, bool SG>
 static hipError_t launch_tracer_adj_cell(const MeshDev &m, const TracerAdjArgs &a, hipStream_t s)
 {
     const int ng = BLOCK / LPC;
     const int grid = std::min(std::max((m.nC + ng - 1) / ng, 1), 65536);
-    hipLaunchKernelGGL((k_tracer_adj_cell<LPC, DIFF>), dim3(grid), dim3(BLOCK), 0, s, m, a);
+    hipLaunchKernelGGL((k_tracer_adj_cell<LPC, DIFF, SG>), dim3(grid), dim3(BLOCK), 0, s, m, a);
     return hipGetLastError();
 }
 
-template <bool DIFF>
+template <bool DIFF, bool SG>
 static hipError_t launch_tracer_adj_patch(const MeshDev &m, const TracerAdjArgs &a, const TracerKernel &k, hipStream_t s)
 {
     if (k.lds > 64 * 1024)
-        if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_tracer_adj_patch<6, DIFF>)}, 80 * 1024); e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_tracer_adj_patch<6, DIFF>), dim3(patch_grid(m)), dim3(TRA_NT), k.lds, s, m, a, k.chunk);
+        if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_tracer_adj_patch<6, DIFF, SG>)}, 80 * 1024); e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_tracer_adj_patch<6, DIFF, SG>), dim3(patch_grid(m)), dim3(TRA_NT), k.lds, s, m, a, k.chunk);
     return hipGetLastError();
 }
 
-template <bool DIFF>
+template <bool DIFF, bool SG>
 static hipError_t launch_tracer_adj_generic(const MeshDev &m, const TracerAdjArgs &a, int lpc, hipStream_t s)
 {
-#define CALL(L) launch_tracer_adj_cell<L, DIFF>(m, a, s)
+#define CALL(L) launch_tracer_adj_cell<L, DIFF, SG>(m, a, s)
     DISPATCH_LPC(lpc, CALL)
 #undef CALL
 }
@@ -300,9 +318,14 @@ hipError_t launch_tracer_adjoint(const MeshDev &m, const TracerAdjArgs &a, int l
 {
     if (a.nT <= 0) return hipSuccess;
     const bool diff = a.kappa != nullptr;       // (then a.dvdc is set too: moka_tracer_adjoint_sweep)
+    const bool sg = a.G != nullptr;             // (some tracer's source gradient is wanted: moka_tracer_adjoint_sweep)
     const TracerKernel k = tracer_adjoint_kernel(m, lpc, a.nT, generic, diff);
-    if (k.form == 1) return diff ? launch_tracer_adj_patch<true>(m, a, k, s) : launch_tracer_adj_patch<false>(m, a, k, s);
-    return diff ? launch_tracer_adj_generic<true>(m, a, lpc, s) : launch_tracer_adj_generic<false>(m, a, lpc, s);
+#define PICK(F, ...)                                                                            \
+    (diff ? (sg ? F<true, true>(__VA_ARGS__) : F<true, false>(__VA_ARGS__))                       \
+          : (sg ? F<false, true>(__VA_ARGS__) : F<false, false>(__VA_ARGS__)))
+    if (k.form == 1) return PICK(launch_tracer_adj_patch, m, a, k, s);
+    return PICK(launch_tracer_adj_generic, m, a, lpc, s);
+#undef PICK
 }
 
 }  // namespace moka

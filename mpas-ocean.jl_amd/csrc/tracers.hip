@@ -16,6 +16,10 @@ namespace moka {
 //     G = pphi[k,c'] - pphi[k,c];  T += ((((kappa[j] * hE) * G) * dvdc[c,i]) * invArea[c]),   dvdc = dvEdge[e] / dcEdge[e] (plan.cpp)
 // -- G == 0 for a constant tracer, the product antisymmetric between the two cells of an edge, and +-0.0 for kappa[j] == 0, which
 // leaves the bits of T alone.  DIFF == false is the code of a state that never set a diffusivity.
+// SRC (moka_tracer_source_upload: some tracer has a source q_j) adds, behind the whole slot loop, T = T + q_j[k,c] with a rounding of its
+// own, for the tracers whose entry of TracerArgs::src is not nullptr; the others read no source byte and add nothing.  T is never -0.0
+// there (it starts at +0.0 and x + (-x) = +0.0), so a source of +-0.0 leaves its bits alone.  The source element is the cell's own,
+// read from global memory beside hnext, cphi and qn: nothing of it is staged.  SRC == false is the code of a state without sources.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void tracer_update(const TracerArgs &a, double t, double cphi, double hcur, double hnext, double qnIn,
                                               double &pOut, double &qOut)
@@ -29,7 +33,7 @@ __device__ __forceinline__ void tracer_update(const TracerArgs &a, double t, dou
 constexpr int TR_TJ = 4;      // tracers whose sums a lane of k_tracer_cell carries at once (F is formed once per TR_TJ tracers)
 
 // Generic form: LPC lanes span a column, one cell per lane group, index records; any K, any maxEdges (the shape of k_nl_cell).
-template <int LPC, bool DIFF>
+template <int LPC, bool DIFF, bool SRC>
 __global__ __launch_bounds__(BLOCK) void k_tracer_cell(const MeshDev m, const TracerArgs a)
 {
     constexpr int NG = BLOCK / LPC;
@@ -73,6 +77,8 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_cell(const MeshDev m, const Tr
                         const size_t joff = (size_t)(j0 + jj) * a.stride + off;
                         const double cphi = s1 ? pc[jj] : s4 ? 0.0 : a.cphi[joff];
                         double pOut, qOut;
+                        if (SRC)
+                            if (const double *q = a.src[j0 + jj]) t[jj] += q[off];
                         tracer_update(a, t[jj], cphi, hcur, hnext, s1 ? 0.0 : a.qn[joff], pOut, qOut);
                         if (!s4) a.pphi_out[joff] = pOut;
                         a.qn[joff] = qOut;
@@ -87,10 +93,11 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_cell(const MeshDev m, const Tr
 // are staged in LDS in one phase; a cell then reads its neighbours' cached rows in one burst of ds_read_b128 and overwrites the lanes
 // of foreign rows with exec-masked global loads by 32-bit byte offset (k_nl_prep5's row cache).  `chunk` tracers' rows are resident
 // at a time: a state with more takes further passes over the patch (the pphi rows re-staged, F re-formed once per pass).
-// DIFF: the patch's dvdc entries are staged beside sdv, and a cell keeps hE of its slots beside F.
+// DIFF: the patch's dvdc entries are staged beside sdv, and a cell keeps hE of its slots beside F.  SRC: one more own-row load per
+// sourced tracer, not staged (the LDS layout and the chunking do not know about sources).
 constexpr int TR_NT = 256;
 
-template <int ME_, bool DIFF>
+template <int ME_, bool DIFF, bool SRC>
 __global__ __launch_bounds__(TR_NT, 2) void k_tracer_patch(const MeshDev m, const TracerArgs a, const int chunk)
 {
     constexpr int NG = TR_NT / 32;
@@ -242,6 +249,12 @@ __global__ __launch_bounds__(TR_NT, 2) void k_tracer_patch(const MeshDev m, cons
                 const double2 cphi = s1 ? pc : s4 ? make_double2(0.0, 0.0) : gload2(a.cphi + jo, orow);
                 const double2 qnIn = s1 ? make_double2(0.0, 0.0) : gload2(a.qn + jo, orow);
                 double2 pOut, qOut;
+                if (SRC)
+                    if (const double *q = a.src[j0 + jj]) {
+                        const double2 qq = gload2(q, orow);
+                        t.x += qq.x;
+                        t.y += qq.y;
+                    }
                 tracer_update(a, t.x, cphi.x, hcur.x, hnext.x, qnIn.x, pOut.x, qOut.x);
                 tracer_update(a, t.y, cphi.y, hcur.y, hnext.y, qnIn.y, pOut.y, qOut.y);
                 if (!s4) gstore2(a.pphi_out + jo, orow, pOut);
@@ -270,28 +283,28 @@ TracerKernel tracer_kernel(const MeshDev &m, int lpc, int nT, bool generic, bool
     return {2, 0, 0};
 }
 
-template <int LPC, bool DIFF>
+template <int LPC, bool DIFF, bool SRC>
 static hipError_t launch_tracer_cell(const MeshDev &m, const TracerArgs &a, hipStream_t s)
 {
     const int ng = BLOCK / LPC;
     const int grid = std::min(std::max((m.nC + ng - 1) / ng, 1), 65536);
-    hipLaunchKernelGGL((k_tracer_cell<LPC, DIFF>), dim3(grid), dim3(BLOCK), 0, s, m, a);
+    hipLaunchKernelGGL((k_tracer_cell<LPC, DIFF, SRC>), dim3(grid), dim3(BLOCK), 0, s, m, a);
     return hipGetLastError();
 }
 
-template <bool DIFF>
+template <bool DIFF, bool SRC>
 static hipError_t launch_tracer_patch(const MeshDev &m, const TracerArgs &a, const TracerKernel &k, hipStream_t s)
 {
     if (k.lds > 64 * 1024)
-        if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_tracer_patch<6, DIFF>)}, 80 * 1024); e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_tracer_patch<6, DIFF>), dim3(patch_grid(m)), dim3(TR_NT), k.lds, s, m, a, k.chunk);
+        if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_tracer_patch<6, DIFF, SRC>)}, 80 * 1024); e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_tracer_patch<6, DIFF, SRC>), dim3(patch_grid(m)), dim3(TR_NT), k.lds, s, m, a, k.chunk);
     return hipGetLastError();
 }
 
-template <bool DIFF>
+template <bool DIFF, bool SRC>
 static hipError_t launch_tracer_generic(const MeshDev &m, const TracerArgs &a, int lpc, hipStream_t s)
 {
-#define CALL(L) launch_tracer_cell<L, DIFF>(m, a, s)
+#define CALL(L) launch_tracer_cell<L, DIFF, SRC>(m, a, s)
     DISPATCH_LPC(lpc, CALL)
 #undef CALL
 }
@@ -300,9 +313,14 @@ hipError_t launch_tracers(const MeshDev &m, const TracerArgs &a, int lpc, bool g
 {
     if (a.nT <= 0) return hipSuccess;
     const bool diff = a.kappa != nullptr;       // (then a.dvdc is set too: tracer_stage)
+    const bool src = a.src != nullptr;          // (some tracer of the state has a source: tracer_stage)
     const TracerKernel k = tracer_kernel(m, lpc, a.nT, generic, diff);
-    if (k.form == 1) return diff ? launch_tracer_patch<true>(m, a, k, s) : launch_tracer_patch<false>(m, a, k, s);
-    return diff ? launch_tracer_generic<true>(m, a, lpc, s) : launch_tracer_generic<false>(m, a, lpc, s);
+#define PICK(F, ...)                                                                            \
+    (diff ? (src ? F<true, true>(__VA_ARGS__) : F<true, false>(__VA_ARGS__))                      \
+          : (src ? F<false, true>(__VA_ARGS__) : F<false, false>(__VA_ARGS__)))
+    if (k.form == 1) return PICK(launch_tracer_patch, m, a, k, s);
+    return PICK(launch_tracer_generic, m, a, lpc, s);
+#undef PICK
 }
 
 }  // namespace moka

@@ -486,6 +486,28 @@ function tracer!(out::Matrix{Float64}, Prog::MProg, j::Integer; level::Integer =
     check(ccall((:moka_tracer_download, lib), Cint, (Ptr{Cvoid}, Int32, Cint, Ptr{Float64}), s.handle, j - 1, level, out), s.backend.ctx)
     out
 end
+# Tracer sources (include/moka_hip.h): q of tracer j (1-based), a (nVertLevels, nCells) matrix in tracer * m/s, the rate of change of the
+# content h phi, constant in time until changed; nothing removes it.  Takes effect with the next RK4 step.
+function set_tracer_source!(Prog::MProg, j::Integer, q::Union{Matrix{Float64}, Nothing})
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    p = q === nothing ? Ptr{Float64}(C_NULL) : pointer(q)
+    GC.@preserve q check(ccall((:moka_tracer_source_upload, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), s.handle, j - 1, p), s.backend.ctx)
+end
+# the source of tracer j (1-based) into `out` (zeros when it has none)
+function tracer_source!(out::Matrix{Float64}, Prog::MProg, j::Integer)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    check(ccall((:moka_tracer_source_download, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), s.handle, j - 1, out), s.backend.ctx)
+    out
+end
+function tracer_has_source(Prog::MProg, j::Integer)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    out = Ref{Cint}(0)
+    check(ccall((:moka_tracer_has_source, lib), Cint, (Ptr{Cvoid}, Int32, Ref{Cint}), s.handle, j - 1, out), s.backend.ctx)
+    out[] != 0
+end
 # 1 the patch form, 2 the generic form of the tracer kernel served the last RK4 stage, 0 none yet
 function tracer_path(Prog::MProg)
     s = Prog.ssh[end].state
@@ -588,6 +610,16 @@ function gradient!(t::TracerTape, grads::Vector{Matrix{Float64}}, seeds::Vector)
         check(ccall((:moka_tracer_adjoint_download, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), t.handle, j - 1, a), ctx)
     end
     grads
+end
+# the following sweeps also accumulate d J / d q_j for tracer j (1-based), q_j a source that acts identically in every recorded step
+# (on = false: no longer); not between a seed and its sweep
+function want_source_gradient!(t::TracerTape, j::Integer, on::Bool = true)
+    check(ccall((:moka_tracer_adjoint_want_source_gradient, lib), Cint, (Ptr{Cvoid}, Int32, Cint), t.handle, j - 1, on ? 1 : 0), t.state.backend.ctx)
+end
+# d J / d q_j as it stands into `out`; the tracer must have been flagged with want_source_gradient!
+function source_gradient!(out::Matrix{Float64}, t::TracerTape, j::Integer)
+    check(ccall((:moka_tracer_adjoint_source_download, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), t.handle, j - 1, out), t.state.backend.ctx)
+    out
 end
 # 1 the patch form, 2 the generic form of the reverse tracer kernel served the last reverse stage, 0 none yet
 tracer_adjoint_path(t::TracerTape) = Int(ccall((:moka_tracer_adjoint_path, lib), Cint, (Ptr{Cvoid},), t.handle))

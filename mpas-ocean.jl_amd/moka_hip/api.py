@@ -639,12 +639,34 @@ class Tracers:
             out[j] = v.value
         return out
 
+    def set_source(self, j: int, a):
+        """moka_tracer_source_upload: the source q_j of tracer j, an (nCells, K) field in tracer * m/s (the rate of change of the
+        content h phi), constant in time until changed; None removes it.  Takes effect with the next RK4 step or run.  Every value
+        must be finite."""
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape != self.shape:
+                a = a.reshape(self.shape)
+        L.check(L.lib().moka_tracer_source_upload(self._s._h, int(j), None if a is None else L.f64(a)), self._s.mesh.backend._h)
 
-def set_tracers(Prog: "PrognosticVars", arrays, diffusivity=None) -> Tracers:
+    def source(self, j: int) -> np.ndarray:
+        """moka_tracer_source_download: the source of tracer j (zeros when it has none)."""
+        out = np.empty(self.shape, dtype=np.float64)
+        L.check(L.lib().moka_tracer_source_download(self._s._h, int(j), L.f64(out)), self._s.mesh.backend._h)
+        return out
+
+    def has_source(self, j: int) -> bool:
+        v = C.c_int()
+        L.check(L.lib().moka_tracer_has_source(self._s._h, int(j), C.byref(v)), self._s.mesh.backend._h)
+        return bool(v.value)
+
+
+def set_tracers(Prog: "PrognosticVars", arrays, diffusivity=None, sources=None) -> Tracers:
     """Give this model passive tracers (moka_set_tracers): `arrays` is a list of (nCells, K) fields, uploaded into both time levels;
     an empty list removes the tracers again.  An extension (the reference has none): centred flux-form transport by the thickness
     flux inside RK4 steps (include/moka_hip.h states the algebra); Forward Euler, tapes and halos refuse a state with tracers.
-    diffusivity: a scalar or one value per tracer (Tracers.set_diffusivity); None leaves the tracers undiffused."""
+    diffusivity: a scalar or one value per tracer (Tracers.set_diffusivity); None leaves the tracers undiffused.
+    sources: one entry per tracer, an (nCells, K) field or None for a tracer without a source (Tracers.set_source)."""
     s = Prog._state
     arrays = list(arrays)
     L.check(L.lib().moka_set_tracers(s._h, len(arrays)), s.mesh.backend._h)
@@ -654,6 +676,13 @@ def set_tracers(Prog: "PrognosticVars", arrays, diffusivity=None) -> Tracers:
         tr.set(j, a, 1)
     if diffusivity is not None:
         tr.set_diffusivity(diffusivity)
+    if sources is not None:
+        sources = list(sources)
+        if len(sources) != len(arrays):
+            raise ValueError(f"sources: {len(sources)} entries for {len(arrays)} tracers")
+        for j, q in enumerate(sources):
+            if q is not None:
+                tr.set_source(j, q)
     return tr
 
 
@@ -714,7 +743,8 @@ class TracerAdjointTape:
     """Reverse mode of the passive tracers over a frozen flow (moka_tracer_tape_*; include/moka_hip.h states the algebra): record RK4
     steps of a model with tracers, then turn d J / d (tracers after the last step) into d J / d (tracers before the first recorded
     step), the flow held as it ran.  The tracer step is linear in the tracers, so this is an exact transpose; it works over the
-    linear, nonlinear, Del2 and Del4 dycores alike.  Sensitivities to the flow or to the diffusivities are out of scope."""
+    linear, nonlinear, Del2 and Del4 dycores alike.  want_source_gradient(j) makes the sweep also return d J / d q_j for a source
+    q_j that acts identically in every recorded step.  Sensitivities to the flow or to the diffusivities are out of scope."""
 
     def __init__(self, Prog: "PrognosticVars", capacity_steps: int):
         self._state = Prog._state
@@ -752,13 +782,32 @@ class TracerAdjointTape:
         L.check(L.lib().moka_tracer_adjoint_download(self._h, int(j), L.f64(out)), self._ctx)
         return out
 
-    def gradient(self, seeds) -> list:
-        """seeds: one entry per tracer, None meaning zero.  Seeds, sweeps and returns the list of gradients."""
+    def want_source_gradient(self, j: int, on: bool = True):
+        """moka_tracer_adjoint_want_source_gradient: the following sweeps also accumulate d J / d q_j (on=False: no longer).  Not
+        between a seed and its sweep."""
+        L.check(L.lib().moka_tracer_adjoint_want_source_gradient(self._h, int(j), 1 if on else 0), self._ctx)
+
+    def source_gradient(self, j: int) -> np.ndarray:
+        """d J / d q_j as it stands (after a sweep: the gradient with respect to a source constant over the recorded steps), caller's
+        numbering.  The tracer must have been flagged with want_source_gradient."""
+        out = np.empty(self._shape, dtype=np.float64)
+        L.check(L.lib().moka_tracer_adjoint_source_download(self._h, int(j), L.f64(out)), self._ctx)
+        return out
+
+    def gradient(self, seeds, sources: bool = False):
+        """seeds: one entry per tracer, None meaning zero.  Seeds, sweeps and returns the list of gradients d J / d phi_0; with
+        sources=True every tracer's source gradient is asked for and (dphi0, dq) is returned."""
         seeds = list(seeds)
+        if sources:
+            for j in range(len(seeds)):
+                self.want_source_gradient(j)
         for j, a in enumerate(seeds):
             self.seed(j, a)
         self.sweep()
-        return [self.download(j) for j in range(len(seeds))]
+        dphi0 = [self.download(j) for j in range(len(seeds))]
+        if sources:
+            return dphi0, [self.source_gradient(j) for j in range(len(seeds))]
+        return dphi0
 
     def path(self) -> int:
         """moka_tracer_adjoint_path: 1 the patch form, 2 the generic form of the reverse kernel, 0 before the first reverse stage."""

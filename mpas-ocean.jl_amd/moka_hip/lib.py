@@ -102,6 +102,8 @@ EXPORTS = [
     "moka_state_rk4_streams",
     "moka_set_tracers", "moka_tracer_upload", "moka_tracer_download", "moka_state_tracer_path",
     "moka_set_tracer_diffusion", "moka_tracer_diffusion",
+    "moka_tracer_source_upload", "moka_tracer_source_download", "moka_tracer_has_source",
+    "moka_tracer_adjoint_want_source_gradient", "moka_tracer_adjoint_source_download",
     "moka_tracer_tape_create", "moka_tracer_tape_destroy", "moka_step_rk4_tracer_taped", "moka_tracer_tape_steps",
     "moka_tracer_adjoint_seed", "moka_tracer_adjoint_sweep", "moka_tracer_adjoint_download", "moka_tracer_adjoint_path",
 ]
@@ -254,6 +256,11 @@ def lib():
     L.moka_tracer_adjoint_sweep.argtypes = [vp]
     L.moka_tracer_adjoint_download.argtypes = [vp, C.c_int32, vp]
     L.moka_tracer_adjoint_path.argtypes = [vp]
+    L.moka_tracer_source_upload.argtypes = [vp, C.c_int32, vp]
+    L.moka_tracer_source_download.argtypes = [vp, C.c_int32, vp]
+    L.moka_tracer_has_source.argtypes = [vp, C.c_int32, C.POINTER(C.c_int)]
+    L.moka_tracer_adjoint_want_source_gradient.argtypes = [vp, C.c_int32, C.c_int]
+    L.moka_tracer_adjoint_source_download.argtypes = [vp, C.c_int32, vp]
     L.moka_tape_create.argtypes = [vp, C.c_int64, C.POINTER(vp)]
     L.moka_tape_destroy.argtypes = [vp]
     L.moka_tape_destroy.restype = None

@@ -8,6 +8,9 @@ process, alternated round by round, every figure a median of moka_mark intervals
   reverse   the sweep over one recorded step: the elementwise head (g, the first y) and the four reverse stage launches; per launch =
             the sweep / 4, the head included.  The seeds are zeros (moka_tracer_adjoint_seed(j, NULL)): the kernels' work does not
             depend on the values, and a recorded step un-seeds the tape, so every repetition seeds again without a host copy
+  sources   the same forward step with a source on every tracer (moka_tracer_source_upload), and the same sweep with every tracer's
+            source gradient wanted (moka_tracer_adjoint_want_source_gradient): one more own-row stream per tracer and forward launch,
+            two more (G in + out) per tracer in the head and in three of the four reverse launches
   copy      the copy rate of the same run (moka_bw_probe)
 
 Config 4 (icosahedral m = 320, 1 024 002 cells x 60 levels); --small: config 3 (m = 64).  Prints one JSON line and, with --out FILE,
@@ -57,6 +60,9 @@ sh = Prog._state._h
 fwd = {n: [] for n in counts}
 taped = {n: [] for n in counts if n}
 rev = {n: [] for n in counts if n}
+fwd_src = {n: [] for n in counts if n}
+rev_g = {n: [] for n in counts if n}
+qsrc = np.random.default_rng(2).uniform(-1.0, 1.0, (mesh.nCells, K)) * (float(h.mean()) / (1000.0 * dts))
 paths = {}
 for _ in range(args.rounds):
     for n in counts:
@@ -73,23 +79,42 @@ for _ in range(args.rounds):
         fwd[n] += list(b.marks_read())
         if not n:
             continue
+        for j in range(n):
+            tr.set_source(j, qsrc)
+        for _ in range(args.warmup):
+            L.check(lib.moka_step_rk4(sh, C.c_double(dts)), b._h)
+        b.synchronize()
+        b.marks_reset()
+        b.mark()
+        for _ in range(args.steps):
+            L.check(lib.moka_step_rk4(sh, C.c_double(dts)), b._h)
+            b.mark()
+        b.synchronize()
+        fwd_src[n] += list(b.marks_read())
+        for j in range(n):
+            tr.set_source(j, None)
         tape = mk.TracerAdjointTape(Prog, 1)
-        for rep in range(args.warmup + args.steps):
-            b.synchronize()
-            b.marks_reset()
-            b.mark()
-            tape.step(dts)
-            b.mark()
+        for want in (False, True):
             for j in range(n):
-                tape.seed(j, None)
-            b.mark()
-            tape.sweep()
-            b.mark()
-            b.synchronize()
-            iv = list(b.marks_read())
-            if rep >= args.warmup:
-                taped[n].append(iv[0])
-                rev[n].append(iv[2])
+                tape.want_source_gradient(j, want)
+            for rep in range(args.warmup + args.steps):
+                b.synchronize()
+                b.marks_reset()
+                b.mark()
+                tape.step(dts)
+                b.mark()
+                for j in range(n):
+                    tape.seed(j, None)
+                b.mark()
+                tape.sweep()
+                b.mark()
+                b.synchronize()
+                iv = list(b.marks_read())
+                if rep >= args.warmup and want:
+                    rev_g[n].append(iv[2])
+                elif rep >= args.warmup:
+                    taped[n].append(iv[0])
+                    rev[n].append(iv[2])
         paths[n] = (tr.path(), tape.path())
         tape.close()
 mk.set_tracers(Prog, [])
@@ -99,7 +124,9 @@ nE, nC = mesh.nEdges, mesh.nCells
 result = {"cells": nC, "edges": nE, "K": K, "rounds": args.rounds, "steps_per_round": args.steps, "copy_GBs": bw.get("copy_GBs"),
           "paths_forward_reverse": paths, "forward_ms_per_step": {n: med(v) for n, v in fwd.items()},
           "taped_ms_per_step": {n: med(v) for n, v in taped.items()}, "sweep_ms_per_step": {n: med(v) for n, v in rev.items()},
-          "sweep_ms_min_max": {n: (min(v), max(v)) for n, v in rev.items()}}
+          "sweep_ms_min_max": {n: (min(v), max(v)) for n, v in rev.items()},
+          "forward_with_sources_ms_per_step": {n: med(v) for n, v in fwd_src.items()},
+          "sweep_with_source_gradients_ms_per_step": {n: med(v) for n, v in rev_g.items()}}
 rows = []
 for n in counts:
     if not n:
@@ -124,4 +151,11 @@ if args.out:
                  "taping ms / step\n")
         for r in rows:
             fh.write(f"   {r[0]:<9d} {r[1]:<19.3f} {r[2]:<19.3f} {r[3]:<19.2f} {r[4]:<6.2f} {r[5]:<26.2f} {r[6]:<5.2f} {r[7]:<12.2f} {r[8]:.3f}\n")
+        fh.write("\n   a source on every tracer / every source gradient wanted, same run, medians\n"
+                 "   tracers   forward step ms (without, with sources)   per launch   sweep ms (without, with gradients)   per launch\n")
+        for n in counts:
+            if n:
+                f0, f1 = result["forward_ms_per_step"][n], result["forward_with_sources_ms_per_step"][n]
+                r0, r1 = result["sweep_ms_per_step"][n], result["sweep_with_source_gradients_ms_per_step"][n]
+                fh.write(f"   {n:<9d} {f0:<9.3f} {f1:<35.3f} {(f1 - f0) / 4:<+12.3f} {r0:<9.3f} {r1:<27.3f} {(r1 - r0) / 4:+.3f}\n")
 Prog._state.close(); Setup.mesh.close()

@@ -5,7 +5,9 @@ round and each step timed between two moka_mark events (median, min, max) -- fir
 in its patch form), then with kernel variant 3 (generic dycore kernels, the tracer launch in its generic form).  The tracer launch
 alone is the difference to the same run's tracer-free step, over the four launches of a step; the diffusion-off legs run the
 instantiations of a state that never set a diffusivity, so they are the baseline of the diffusion-on legs.  Shader clock and package
-power are sampled from sysfs while the 3-tracer steps run back to back, diffusion off and on (bench.py's under_load).  Config 4 (icosahedral
+power are sampled from sysfs while the 3-tracer steps run back to back, diffusion off and on (bench.py's under_load).  A third set of
+legs gives every tracer a source (moka_tracer_source_upload; the SRC instantiations, one more own-row stream of 8 K nC bytes per sourced
+tracer and launch), diffusion off, and with three tracers also on; they alternate with the other legs in the same rounds.  Config 4 (icosahedral
 m = 320, 1 024 002 cells x 60 levels); --small: config 3 (m = 64).  Prints one JSON line and, with --out FILE, writes the summary
 table there.
 
@@ -50,8 +52,10 @@ rng = np.random.default_rng(1)
 phi = rng.uniform(0.5, 1.5, (mesh.nCells, K))
 counts = (0, 1, 3)
 kappa = 0.02 * float(mesh.dcEdge.min()) ** 2 / dts
-settings = [(0, False)] + [(n, d) for n in counts if n for d in (False, True)]
-key = lambda n, d: f"{n}{'+diff' if d else ''}"      # noqa: E731
+settings = [(0, False, False)] + [(n, d, False) for n in counts if n for d in (False, True)]
+settings += [(n, False, True) for n in counts if n] + [(3, True, True)]
+key = lambda n, d, s=False: f"{n}{'+diff' if d else ''}{'+src' if s else ''}"      # noqa: E731
+qsrc = rng.uniform(-1.0, 1.0, (mesh.nCells, K)) * (float(h.mean()) / (1000.0 * dts))
 result = {"cells": mesh.nCells, "edges": mesh.nEdges, "K": K, "rounds": args.rounds, "steps_per_round": args.steps, "kappa": kappa,
           "forms": {}}
 for variant, form in ((0, "patch"), (3, "generic")):
@@ -59,11 +63,12 @@ for variant, form in ((0, "patch"), (3, "generic")):
     Setup, Diag, Tend, Prog = mk.ocn_init_from_arrays(mesh, ssh, u, h, rest, cfg, b, multilayer=True)
     sh = Prog._state._h
     steps = {n: [] for n in counts}
-    dsteps = {key(n, d): [] for n, d in settings}
+    dsteps = {key(n, d): [] for n, d, s in settings if not s}
+    ssteps = {key(n, d, True): [] for n, d, s in settings if s}
     path = 0
     for _ in range(args.rounds):
-        for n, diff in settings:
-            tr = mk.set_tracers(Prog, [phi] * n, diffusivity=kappa if diff else None)
+        for n, diff, src in settings:
+            tr = mk.set_tracers(Prog, [phi] * n, diffusivity=kappa if diff else None, sources=[qsrc] * n if src else None)
             for _ in range(args.warmup):                                     # lazy allocations, LDS attributes, clocks
                 L.check(lib.moka_step_rk4(sh, C.c_double(dts)), b._h)
             b.synchronize()
@@ -73,6 +78,9 @@ for variant, form in ((0, "patch"), (3, "generic")):
                 L.check(lib.moka_step_rk4(sh, C.c_double(dts)), b._h)
                 b.mark()
             b.synchronize()
+            if src:
+                ssteps[key(n, diff, True)] += list(b.marks_read())
+                continue
             dsteps[key(n, diff)] += list(b.marks_read())
             if not diff:
                 steps[n] = dsteps[key(n, False)]
@@ -95,6 +103,9 @@ for variant, form in ((0, "patch"), (3, "generic")):
                           "p25": statistics.quantiles(v, n=4)[0], "p75": statistics.quantiles(v, n=4)[2]} for k, v in dsteps.items()},
         "diffusion_launch_delta_ms": {n: (statistics.median(dsteps[key(n, True)]) - statistics.median(dsteps[key(n, False)])) / 4
                                       for n in counts if n},
+        "sources": {k: {"median": statistics.median(v), "min": min(v), "max": max(v), "p25": statistics.quantiles(v, n=4)[0],
+                        "p75": statistics.quantiles(v, n=4)[2],
+                        "launch_delta_ms": (statistics.median(v) - statistics.median(dsteps[k[:-4]])) / 4} for k, v in ssteps.items()},
         "under_load": load}
     Prog._state.close(); Setup.mesh.close()
 b.set_kernel_variant(0)
@@ -128,6 +139,11 @@ if args.out:
                 if k.endswith("+diff"):
                     line += f" {f['diffusion_launch_delta_ms'][int(k.split('+')[0])]:+.3f}"
                 fh.write(line.rstrip() + "\n")
+            fh.write("\n   a source on every tracer (moka_tracer_source_upload), ms / RK4 step; the leg without '+src' is the row above\n"
+                     "   setting     median    min       p25       p75       max       with - without source per tracer launch\n")
+            for k, d in f["sources"].items():
+                fh.write(f"   {k:<11s} {d['median']:<9.3f} {d['min']:<9.3f} {d['p25']:<9.3f} {d['p75']:<9.3f} {d['max']:<9.3f} "
+                         f"{d['launch_delta_ms']:+.3f}\n")
             for k, u in f["under_load"].items():
                 fh.write(f"   under load, {k}: sclk {u['sclk_mhz_mean']} MHz (min {u['sclk_mhz_min']}), power {u['power_w_mean']} W "
                          f"(max {u['power_w_max']}), {u['ms_per_call_sustained']:.3f} ms / step sustained\n")
