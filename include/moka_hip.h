@@ -534,6 +534,24 @@ int  moka_state_del4_path(const moka_state *st);
  * kappa; (kappa * hE) * G * dvdc is exactly antisymmetric between the two cells of an edge, so the content sum_c A_c sum_k phi h is
  * conserved to round-off as by the advective flux; and adding +-0.0 never changes the bits of T (it starts at +0.0 and cannot become
  * -0.0 under round-to-nearest), so a tracer with kappa_j == 0 beside diffused ones equals the undiffused result bit for bit.
+ * Biharmonic diffusion (moka_set_tracer_biharmonic; default off).  With a coefficient kappa4_j >= 0 (m^4/s) per tracer the scheme is
+ *   d(h phi)/dt = -div(F phi_e) + div(kappa_j h_e grad phi) - div(kappa4_j h_e grad L_j) + q_j,
+ *   L_j = (1/(A h)) sum_e h_e (dv/dc) (phi_c' - phi_c)          the thickness-weighted Laplacian of phi_j.
+ * Laplacian pass.  For a cell field x over the thickness ph, per cell c and level k: start from s = 0.0 and run over the slots of
+ * edgesOnCell in slot order with the skip rules above (empty slots, slots with k >= maxLevelEdgeTop[e]); per slot
+ *   hE = 0.5 * (ph[k,c] + ph[k,c']);  s += (hE * (x[k,c'] - x[k,c])) * dvdc[c,i];
+ * and Lap(ph, x)[k,c] = (s * (1/areaCell[c])) / ph[k,c].  One rounding per operation, no contraction.
+ * Forward, per stage: L_j = Lap(ph_s, pphi_j) for the tracers with kappa4_j != 0; in the tendency's slot loop a third, separate
+ * addition follows the advective and the harmonic ones:
+ *   T = T - ((((kappa4_j * hE) * (L_j[k,c'] - L_j[k,c])) * dvdc[c,i]) * (1/areaCell[c]))
+ * The source addition and the RK4 recipe are untouched.  Hence: a constant tracer has L == 0 exactly, so the unit tracer stays exactly
+ * 1.0; the product is exactly antisymmetric between the two cells of an edge, so content is conserved to round-off; a tracer with
+ * kappa4_j == 0 keeps the bits it has without the term, also beside tracers that do have kappa4 != 0, forwards and backwards (T is
+ * never -0.0, so the added term would be +-0.0 and change nothing; the library skips it, and never reads L of such a tracer);
+ * tracer variance decays by exactly -kappa4 sum_c A_c h_c L_c^2 (sum_c A_c phi_c T4_c, the operator being self-adjoint under the area
+ * weight).  The explicit limit is kappa4 dt / dcEdge_min^4 <~ 0.043: RK4 reaches -2.78 on the real axis and the hexagon Laplacian
+ * reaches 8 / dc^2, so (kappa 8/dc^2 + kappa4 64/dc^4) dt, the sum of the harmonic and the biharmonic parts, must stay inside 2.78.  It
+ * is not checked, as for kappa.
  * One RK4 step, per tracer, with a = (dt/2, dt/2, dt), b = (dt/6, dt/3, dt/3, dt/6) and (pu_s, ph_s), ph_{s+1}, h_new the step's own
  * provisional and new states, whatever terms are switched on (linear, nonlinear, Del2, Del4):
  *   Qc = phi_cur * h_cur;  Qn = Qc;  pphi = phi_cur
@@ -556,8 +574,9 @@ int  moka_state_del4_path(const moka_state *st);
  * that have a halo or a tape.  While nTracers > 0, moka_step_fe, moka_run(MOKA_FORWARD_EULER), moka_tape_create, moka_halo_create and
  * the moka_rk4_dist_* calls return MOKA_ERR_UNSUPPORTED, and moka_set_tuning key 7 leaves the state on the running sum
  * (moka_state_rk4_streams: 16).  moka_state_optimize_placement neither times nor moves the tracer arrays.
- * Out of scope: upwind, FCT and higher-order edge values, biharmonic, anisotropic or spatially varying tracer diffusion, Forward Euler,
- * fp32 storage, partitioned meshes, reverse mode with respect to the flow or the diffusivities (with respect to the tracers themselves
+ * Out of scope: upwind, FCT and higher-order edge values, a spatially varying kappa or kappa4 or a mesh scaling per edge, anisotropic
+ * mixing, Forward Euler,
+ * fp32 storage, partitioned meshes, reverse mode with respect to the flow, kappa or kappa4 (with respect to the tracers themselves
  * and to the sources: moka_tracer_tape_* below), time-dependent sources, point-source convenience calls, the 13-stream form, YAML keys and NetCDF I/O of tracers, and fusing the tracer sum into the dycore's stage
  * kernels. */
 int  moka_set_tracers(moka_state *st, int32_t nTracers);
@@ -577,6 +596,16 @@ int  moka_state_tracer_path(const moka_state *st);
 int  moka_set_tracer_diffusion(moka_state *st, const double *kappa);
 /* the diffusivity of tracer j (0-based) into *out; MOKA_ERR_ARG for j out of range */
 int  moka_tracer_diffusion(const moka_state *st, int32_t j, double *out);
+/* Biharmonic tracer diffusion (algebra above).  kappa4: nTracers coefficients in m^4/s, NULL = all zero; the values take effect with
+ * the next RK4 step or moka_run.  MOKA_ERR_ARG, with nothing changed, for a negative, NaN or infinite value and for a non-NULL kappa4
+ * on a state without tracers.  The first nonzero value allocates the coefficient array and the scratch of L (nTracers * nVertLevels *
+ * nCells doubles); every stage then has one more launch, the Laplacian pass, ahead of the tracer launch.  While every value is zero
+ * the launches are those of a state that never set one.  moka_set_tracers (any count, 0 included) resets every coefficient to zero.
+ * moka_state_tracer_path: the patch form keeps two row sets per resident tracer then (phi and L) and gives way to the generic form
+ * when not even one tracer's two fit. */
+int  moka_set_tracer_biharmonic(moka_state *st, const double *kappa4);
+/* the biharmonic coefficient of tracer j (0-based) into *out; MOKA_ERR_ARG for j out of range */
+int  moka_tracer_biharmonic(const moka_state *st, int32_t j, double *out);
 /* Tracer sources (algebra above).  host: the source of tracer j, (nVertLevels, nCells) doubles in the caller's cell numbering like
  * moka_tracer_upload (any cell ordering of the mesh); NULL removes tracer j's source.  It takes effect with the next RK4 step or
  * moka_run and stays until changed: the state's time levels rotate, sources do not.  MOKA_ERR_ARG for j out of range and, with nothing
@@ -605,6 +634,12 @@ int  moka_tracer_has_source(const moka_state *st, int32_t j, int *out);
  * -- sdv of the edge seen from c' is -sdv[c,i] and the mask belongs to the edge, so the transposed scatter folds into the difference
  * y[c] - y[c'] with y = w * invArea; the diffusion operator is self-adjoint under the area weight.  A gather over the forward stencil:
  * the forward launch's traffic, no atomics.
+ * Biharmonic diffusion is self-adjoint under the area weight too: the reverse mode applies the same two passes to y.  Per reverse
+ * stage s, with the recorded kappa4_j of the step and y carrying invArea already:  M_j = Lap(ph_s, y_j)  (the Laplacian pass above,
+ * the same kernel forwards and backwards), and in R(P_s, y), after the harmonic addition of a slot, a third, separate one:
+ *   r = r - ((kappa4_j * hE) * dvdc[c,i]) * (M_j[k,c'] - M_j[k,c])
+ * Nothing else in the reverse step changes: tau_s, and therefore G below, keep their definitions.  A sweep whose recorded steps all
+ * have every kappa4 == 0 launches what it launches without the term.
  * One step backwards, per tracer j and element (k, c); X the adjoint of phi_new, S a scratch field, invA = invArea[c]:
  *   g = X / hn
  *   y = (b[3] * g) * invA
@@ -625,17 +660,17 @@ int  moka_tracer_has_source(const moka_state *st, int32_t j, int *out);
  * changes no bit of X; a zero seed gives G == 0 exactly; and the map is affine in q, so
  *   <X, phi_N(phi_0, q) - phi_N(phi_0, 0)> = <G, q>   up to round-off.
  * Usage: tracer_tape_create -> n x step_rk4_tracer_taped -> seed (per tracer) -> sweep -> download (per tracer).
- * Out of scope: sensitivities of the tracers to the flow (d phi_N / d (u, h)) and to kappa, time-dependent sources and a per-step
+ * Out of scope: sensitivities of the tracers to the flow (d phi_N / d (u, h)), to kappa and to kappa4, time-dependent sources and a per-step
  * split of G, coupling to moka_tape, Forward Euler, partitioned meshes, fp32 storage. */
 typedef struct moka_tracer_tape moka_tracer_tape;
 /* MOKA_ERR_UNSUPPORTED on a state without tracers, MOKA_ERR_ARG for NULL arguments or a negative capacity.  The tape remembers the
  * state's tracer count and counts as a tape of the state: while it lives, moka_state_optimize_placement and moka_set_tracers(st, n > 0)
- * refuse.  K * (4 nEdges + 5 nCells) doubles per step of capacity (the four P_s and hn), nTracers more for the diffusivities, and five
- * work arrays of nTracers * K * nCells doubles.  State and tape may be destroyed in either order. */
+ * refuse.  K * (4 nEdges + 5 nCells) doubles per step of capacity (the four P_s and hn), nTracers more for the diffusivities and nTracers
+ * for the biharmonic coefficients, and six work arrays of nTracers * K * nCells doubles (the sixth holds M).  State and tape may be destroyed in either order. */
 int  moka_tracer_tape_create(moka_state *st, int64_t capacity_steps, moka_tracer_tape **out);
 void moka_tracer_tape_destroy(moka_tracer_tape *t);
 /* exactly moka_step_rk4 on the tape's state -- state and tracers end up bit for bit as after the untaped call -- with P_0..P_3, hn and
- * the diffusivities recorded by copies behind the stage launches.  MOKA_ERR_ARG when the tape is full or the state's tracer count is no
+ * the diffusivities and biharmonic coefficients recorded by copies behind the stage launches.  MOKA_ERR_ARG when the tape is full or the state's tracer count is no
  * longer the tape's.  A recorded step un-seeds the tape. */
 int  moka_step_rk4_tracer_taped(moka_tracer_tape *t, double dt);
 int  moka_tracer_tape_steps(const moka_tracer_tape *t, int64_t *n);                /* recorded and not yet reversed */

@@ -1436,11 +1436,19 @@ static hipError_t tracer_stage(moka_state *st, int s, const StageArgs &g)
     t.pphi_out = s == 4 ? nullptr : st->trProv[s == 2 ? 1 : 0];
     t.cphi = st->trPhi[1]; t.qn = st->trPhi[0];
     t.a = g.a; t.b = g.b;
-    t.kappa = st->trKappaDev; t.dvdc = st->trKappaDev ? mm->dvdc : nullptr;
+    const bool bih = st->trKappa4Dev != nullptr;
+    t.kappa = st->trKappaDev ? st->trKappaDev : bih ? st->trKappa4Dev + t.nT : nullptr;      // (bih alone: the array of zeros)
+    t.dvdc = t.kappa ? mm->dvdc : nullptr;
     t.src = st->trSrcDev;
+    t.kappa4 = st->trKappa4Dev; t.lap = bih ? st->trLap : nullptr;
     const MeshDev dev = launch_bounds(mm);
     const bool generic = st->ctx->variant == 3;
-    st->tracerPath = tracer_kernel(dev, mm->lpc, t.nT, generic, t.kappa != nullptr).form;
+    st->tracerPath = tracer_kernel(dev, mm->lpc, t.nT, generic, t.kappa != nullptr, bih).form;
+    if (bih) {          // L = Lap(ph_s, pphi) of the tracers with kappa4 != 0, behind the dycore's launch and ahead of the tracer launch
+        TracerLapArgs q{};
+        q.nT = t.nT; q.stride = t.stride; q.ph = t.ph; q.x = t.pphi; q.kappa4 = t.kappa4; q.dvdc = t.dvdc; q.out = st->trLap;
+        if (hipError_t e = launch_tracer_lap(dev, q, mm->lpc, generic, st->ctx->stream); e != hipSuccess) return e;
+    }
     return launch_tracers(dev, t, mm->lpc, generic, st->ctx->stream);
 }
 
@@ -1453,8 +1461,9 @@ struct moka_tracer_tape {
     int64_t capacity = 0, n = 0;
     double *pu = nullptr, *ph = nullptr;             // capacity x 4 x (K, nE) / (K, nC): pu_s, ph_s of stage s = 0..3
     double *hn = nullptr;                            // capacity x (K, nC): layerThickness of the new level
-    double *kap = nullptr;                           // capacity x nT: the diffusivities on the device
-    std::vector<double> kappa, dts;                  // ... and on the host (n * nT values); dt of each step
+    double *kap = nullptr, *kap4 = nullptr;          // capacity x nT each: the diffusivities and the biharmonic coefficients on the device
+    std::vector<double> kappa, kappa4, dts;          // ... and on the host (n * nT values each); dt of each step
+    double *M = nullptr;                             // nT x (K, nC): Lap(ph_s, y) of a reverse stage (biharmonic term)
     double *X = nullptr, *g = nullptr, *S = nullptr, *y[2] = {nullptr, nullptr};   // nT x (K, nC) each: the adjoint state and the sweep's work arrays
     // gradient with respect to the sources (moka_tracer_adjoint_want_source_gradient): the (K, nC) accumulator of every tracer that was
     // ever flagged (nullptr otherwise), whether it is wanted now, and the device table of the wanted ones that the sweep's launches read
@@ -1838,7 +1847,7 @@ int moka_set_tracers(moka_state *st, int32_t nTracers)
     }
     HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
     HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));
-    double **arr[5] = {&st->trPhi[0], &st->trPhi[1], &st->trProv[0], &st->trProv[1], &st->trKappaDev};
+    double **arr[7] = {&st->trPhi[0], &st->trPhi[1], &st->trProv[0], &st->trProv[1], &st->trKappaDev, &st->trKappa4Dev, &st->trLap};
     auto release = [&]() {
         drop_sources(st);                // every source goes with the tracers
         for (double **q : arr) {
@@ -1850,11 +1859,12 @@ int moka_set_tracers(moka_state *st, int32_t nTracers)
         st->nTracers = 0;
         st->tracerPath = 0;
         st->trKappa.clear();             // every diffusivity back to zero
+        st->trKappa4.clear();            // ... and every biharmonic coefficient
     };
     release();
     if (nTracers == 0) return MOKA_OK;
     for (double **q : arr)
-        if (q == &st->trKappaDev) continue;      // allocated by moka_set_tracer_diffusion
+        if (q == &st->trKappaDev || q == &st->trKappa4Dev || q == &st->trLap) continue;      // allocated by their setters
         else if (int rc = alloc_field(st, q, (size_t)nTracers * p.K * p.nC)) {
             (void)hipStreamSynchronize(st->ctx->stream);
             release();
@@ -1932,6 +1942,56 @@ int moka_tracer_diffusion(const moka_state *st, int32_t j, double *out)
     return MOKA_OK;
 }
 
+int moka_set_tracer_biharmonic(moka_state *st, const double *kappa4)
+{
+    if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
+    const int nT = st->nTracers;
+    if (kappa4 && nT == 0) return fail(st->ctx, MOKA_ERR_ARG, "tracer biharmonic diffusion: the state has no tracers (moka_set_tracers)");
+    bool any = false;
+    for (int j = 0; kappa4 && j < nT; ++j) {
+        if (!(kappa4[j] >= 0.0) || !std::isfinite(kappa4[j]))
+            return fail(st->ctx, MOKA_ERR_ARG, "tracer biharmonic diffusion: every coefficient must be finite and >= 0");
+        any = any || kappa4[j] != 0.0;
+    }
+    moka_mesh *mm = st->mesh;
+    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));      // no launch is reading the old values
+    auto drop = [&](double **q) {
+        if (!*q) return;
+        st->allocs.erase(std::remove(st->allocs.begin(), st->allocs.end(), (void *)*q), st->allocs.end());
+        (void)hipFree(*q);
+        *q = nullptr;
+    };
+    if (!any) {
+        drop(&st->trKappa4Dev);
+        drop(&st->trLap);
+        st->trKappa4.clear();
+        return MOKA_OK;
+    }
+    const Plan &p = mm->plan;
+    if (!mm->dvdc)
+        if (int rc = upload_vec(mm, mm->plan.dvdc, &mm->dvdc)) return rc;
+    if (!st->trLap)
+        if (int rc = alloc_field(st, &st->trLap, (size_t)nT * p.K * p.nC)) return rc;
+    if (!st->trKappa4Dev)           // (alloc_field zero-fills: the second half stays the array of zeros)
+        if (int rc = alloc_field(st, &st->trKappa4Dev, 2 * (size_t)nT)) {
+            (void)hipStreamSynchronize(st->ctx->stream);
+            drop(&st->trLap);
+            return rc;
+        }
+    if (int rc = h2d(st->ctx, st->trKappa4Dev, kappa4, (size_t)nT * sizeof(double))) return rc;
+    st->trKappa4.assign(kappa4, kappa4 + nT);
+    return MOKA_OK;
+}
+
+int moka_tracer_biharmonic(const moka_state *st, int32_t j, double *out)
+{
+    if (!st || !out) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    if (j < 0 || j >= st->nTracers) return fail(st->ctx, MOKA_ERR_ARG, "tracer index out of range (moka_set_tracers)");
+    *out = st->trKappa4.empty() ? 0.0 : st->trKappa4[j];
+    return MOKA_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // reverse mode of the tracer transport over a frozen flow (include/moka_hip.h: the algebra; tracer_adjoint.hip: the kernels).  A handle of
 // its own, separate from moka_tape: the tracer step is linear in phi, so its transpose needs the recorded provisional states only.
@@ -1966,8 +2026,8 @@ int moka_tracer_tape_create(moka_state *st, int64_t capacity_steps, moka_tracer_
     const size_t nEK = (size_t)p.K * p.nE, nCK = (size_t)p.K * p.nC, cap = (size_t)capacity_steps;
     int rc = MOKA_OK;
     auto A = [&](double **q, size_t n) { if (rc == MOKA_OK) rc = ttape_alloc(t, q, n); };
-    A(&t->pu, nEK * 4 * cap); A(&t->ph, nCK * 4 * cap); A(&t->hn, nCK * cap); A(&t->kap, (size_t)t->nT * cap);
-    A(&t->X, nCK * t->nT); A(&t->g, nCK * t->nT); A(&t->S, nCK * t->nT); A(&t->y[0], nCK * t->nT); A(&t->y[1], nCK * t->nT);
+    A(&t->pu, nEK * 4 * cap); A(&t->ph, nCK * 4 * cap); A(&t->hn, nCK * cap); A(&t->kap, (size_t)t->nT * cap); A(&t->kap4, (size_t)t->nT * cap);
+    A(&t->X, nCK * t->nT); A(&t->g, nCK * t->nT); A(&t->S, nCK * t->nT); A(&t->y[0], nCK * t->nT); A(&t->y[1], nCK * t->nT); A(&t->M, nCK * t->nT);
     if (rc != MOKA_OK) { moka_tracer_tape_destroy(t); return rc; }
     HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));
     state_attach(st);
@@ -2006,6 +2066,10 @@ int moka_step_rk4_tracer_taped(moka_tracer_tape *t, double dt)
     if (st->trKappaDev) HIPCHK(t->ctx, hipMemcpyAsync(kd, st->trKappaDev, (size_t)t->nT * sizeof(double), hipMemcpyDeviceToDevice, t->ctx->stream));
     else HIPCHK(t->ctx, hipMemsetAsync(kd, 0, (size_t)t->nT * sizeof(double), t->ctx->stream));
     for (int j = 0; j < t->nT; ++j) t->kappa.push_back(st->trKappa.empty() ? 0.0 : st->trKappa[j]);
+    double *k4d = t->kap4 + (size_t)t->n * t->nT;
+    if (st->trKappa4Dev) HIPCHK(t->ctx, hipMemcpyAsync(k4d, st->trKappa4Dev, (size_t)t->nT * sizeof(double), hipMemcpyDeviceToDevice, t->ctx->stream));
+    else HIPCHK(t->ctx, hipMemsetAsync(k4d, 0, (size_t)t->nT * sizeof(double), t->ctx->stream));
+    for (int j = 0; j < t->nT; ++j) t->kappa4.push_back(st->trKappa4.empty() ? 0.0 : st->trKappa4[j]);
     t->dts.push_back(dt);
     ++t->n;
     t->seeded = false;
@@ -2059,8 +2123,10 @@ int moka_tracer_adjoint_sweep(moka_tracer_tape *t)
     const Plan &p = mm->plan;
     HIPCHK(t->ctx, hipSetDevice(t->ctx->device));
     hipStream_t s = t->ctx->stream;
-    bool diff = false;
+    bool diff = false, bih = false;
+    for (double k : t->kappa4) bih = bih || k != 0.0;
     for (double k : t->kappa) diff = diff || k != 0.0;
+    diff = diff || bih;                 // the BIH kernels exist only together with DIFF (a step without diffusivities recorded zeros)
     if (diff && !mm->dvdc)
         if (int rc = upload_vec(mm, mm->plan.dvdc, &mm->dvdc)) return rc;
     const MeshDev dev = launch_bounds(mm);
@@ -2085,13 +2151,21 @@ int moka_tracer_adjoint_sweep(moka_tracer_tape *t)
             q.kappa = diff ? t->kap + (size_t)n * t->nT : nullptr;
             q.dvdc = diff ? mm->dvdc : nullptr;
             q.G = rs > 0 ? G : nullptr;         // reverse stage 0 does not touch G
-            t->path = tracer_adjoint_kernel(dev, mm->lpc, q.nT, generic, diff).form;
+            q.kappa4 = bih ? t->kap4 + (size_t)n * t->nT : nullptr;
+            q.lapy = bih ? t->M : nullptr;
+            if (bih && std::any_of(t->kappa4.begin() + n * t->nT, t->kappa4.begin() + (n + 1) * t->nT, [](double k) { return k != 0.0; })) {
+                TracerLapArgs w{};          // M = Lap(ph_s, y) of the tracers whose recorded kappa4 is not zero
+                w.nT = q.nT; w.stride = q.stride; w.ph = q.ph; w.x = q.y; w.kappa4 = q.kappa4; w.dvdc = q.dvdc; w.out = t->M;
+                HIPCHK(t->ctx, launch_tracer_lap(dev, w, mm->lpc, generic, s));
+            }
+            t->path = tracer_adjoint_kernel(dev, mm->lpc, q.nT, generic, diff, bih).form;
             HIPCHK(t->ctx, launch_tracer_adjoint(dev, q, mm->lpc, generic, s));
             cur ^= 1;
         }
         t->n = n;
         t->dts.pop_back();
         t->kappa.resize((size_t)n * t->nT);
+        t->kappa4.resize((size_t)n * t->nT);
     }
     return MOKA_OK;
 }

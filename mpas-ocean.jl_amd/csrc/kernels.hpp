@@ -204,18 +204,42 @@ struct TracerArgs {
     // table itself is nullptr while no tracer of the state has a source (the launch is then the one of a state that never had any).
     // After the slot loop T = T + q[k,c], the cell's own element, read from global memory.
     const double *const *src;
+    // biharmonic diffusion (moka_set_tracer_biharmonic): nT coefficients kappa4 and the base of L = Lap(ph, pphi) (nT fields `stride`
+    // apart, written by launch_tracer_lap on the same stream); both nullptr while every kappa4 of the state is zero (the launch is then
+    // the one of a state that never set any).  L of a tracer with kappa4[j] == 0 is never written and never read.  Set only together
+    // with kappa and dvdc (a state whose diffusivities are all zero passes an array of zeros).
+    const double *kappa4, *lap;
 };
 // The kernel that serves a tracer launch, chosen in one place for the launcher and for moka_state_tracer_path.  form 1: k_tracer_patch
 // (even 34 <= K <= 64, hexagon-width byte-offset records, which exist only where every field's rows stay below 4 GiB; `chunk` tracers'
 // rows resident in `lds` bytes of dynamic LDS per pass), form 2: k_tracer_cell.  generic: the caller asks for form 2 (kernel variant 3).
 // diff: the DIFF instantiations (the patch form then stages dvdc too: more LDS, possibly a smaller chunk).
+// bih: the BIH instantiations (a resident tracer takes a second row set, for L: half as many tracers per pass; form 2 when not even
+// one tracer's two row sets fit).
 struct TracerKernel {
     int form;
     size_t lds;
     int chunk;
 };
-TracerKernel tracer_kernel(const MeshDev &m, int lpc, int nT, bool generic, bool diff);
+TracerKernel tracer_kernel(const MeshDev &m, int lpc, int nT, bool generic, bool diff, bool bih);
 hipError_t launch_tracers(const MeshDev &m, const TracerArgs &a, int lpc, bool generic, hipStream_t s);
+
+// The Laplacian pass of the biharmonic term (tracers.hip), one launch for every field j with kappa4[j] != 0; the others are neither
+// read nor written.  Per cell c and level k, from s = 0.0 over the slots of edgesOnCell in slot order with the tendency's skip rules:
+//   hE = 0.5 * (ph[k,c] + ph[k,c']);  s += (hE * (x[k,c'] - x[k,c])) * dvdc[c,i];      out[k,c] = (s * invArea[c]) / ph[k,c]
+// Two callers: the forward step on (ph_s, pphi) ahead of the tracer launch, the reverse sweep on (ph_s, y) ahead of a reverse stage.
+struct TracerLapArgs {
+    int nT;
+    int64_t stride;               // K * nC: fields of x and of out lie this far apart
+    const double *ph;             // the thickness (gathered)
+    const double *x;              // the fields (gathered)
+    const double *kappa4, *dvdc;  // nT coefficients (only their being zero or not matters here); the plan's (nC, ME) dvEdge / dcEdge
+    double *out;
+};
+// the kernel that serves the pass: k_tracer_patch's layout without the harmonic extras (dvdc takes the place of sdv), so
+// tracer_kernel(m, lpc, nT, generic, false, false) decides.  form 1: k_tracer_lap_patch, form 2: k_tracer_lap_cell.
+TracerKernel tracer_lap_kernel(const MeshDev &m, int lpc, int nT, bool generic);
+hipError_t launch_tracer_lap(const MeshDev &m, const TracerLapArgs &a, int lpc, bool generic, hipStream_t s);
 
 // ---- reverse mode of the tracer step over a frozen flow (moka_tracer_tape_*; tracer_adjoint.hip): one launch per reverse stage ----
 // With r = R(P_rs, y) the transposed tendency of include/moka_hip.h, per tracer and element (hc = ph[k,c], invA = invArea[c]):
@@ -236,9 +260,13 @@ struct TracerAdjArgs {
     // accumulator or nullptr where none is wanted; the table is nullptr in a sweep that wants none.  rs > 0 adds tau = cb * g + ca * v,
     // the value `out` multiplies by invA, to the cell's own element: G = G + tau.  rs == 0 does not touch G.
     double *const *G;
+    // biharmonic diffusion: the recorded nT coefficients of the step and the base of M = Lap(ph, y) (launch_tracer_lap on the same
+    // stream); both nullptr in a sweep whose recorded steps all have every kappa4 zero.  As in TracerArgs: only together with kappa and
+    // dvdc, and M of a tracer with kappa4[j] == 0 is never read.
+    const double *kappa4, *lapy;
 };
 // the kernel that serves a reverse stage, for the launcher and for moka_tracer_adjoint_path: the forward choice (same rows in LDS)
-TracerKernel tracer_adjoint_kernel(const MeshDev &m, int lpc, int nT, bool generic, bool diff);
+TracerKernel tracer_adjoint_kernel(const MeshDev &m, int lpc, int nT, bool generic, bool diff, bool bih);
 hipError_t launch_tracer_adjoint(const MeshDev &m, const TracerAdjArgs &a, int lpc, bool generic, hipStream_t s);
 // g = X / hn and y = (b4 * g) * invArea, elementwise over nT fields: the head of a reverse step
 // G: TracerAdjArgs::G (nullptr: no gradient wanted); the head adds tau_3 = b4 * g, the value y multiplies by invArea

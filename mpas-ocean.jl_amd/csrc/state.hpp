@@ -120,6 +120,12 @@ struct moka_state {
     // tracer launches read -- nullptr while every value is zero: the launches are then those of a state that never set any
     std::vector<double> trKappa;
     double *trKappaDev = nullptr;
+    // biharmonic tracer diffusion (moka_set_tracer_biharmonic): the host copy beside trKappa (empty = all zero); the device array of
+    // 2 * nTracers doubles -- the coefficients, then nTracers zeros that stand in for the diffusivities while those are all zero (the
+    // BIH kernels exist only together with DIFF) -- and the scratch of L = Lap(ph, pphi), nTracers x (K, nC).  Both are allocated when a
+    // nonzero value is first set, never inside a step, and nullptr while every value is zero.
+    std::vector<double> trKappa4;
+    double *trKappa4Dev = nullptr, *trLap = nullptr;
     // tracer sources (moka_tracer_source_upload): only a sourced tracer owns a (K, nC) device array.  trSrc holds nTracers pointers
     // (nullptr = no source) and is empty while no tracer has a source; trSrcDev is its copy on the device, the table the tracer
     // launches read -- nullptr while trSrc is empty: the launches are then those of a state that never had a source.  Sources do

@@ -16,6 +16,11 @@ namespace moka {
 // invArea to form the next gathered field, to the accumulator of every tracer whose entry of TracerAdjArgs::G is not nullptr --
 // one read and one write of the cell's own element, nothing staged; y = tau * invA keeps its bits.  SG == false is the code of a sweep
 // that wants no gradient.
+// BIH (some recorded kappa4_j != 0; only together with DIFF): the biharmonic term is self-adjoint under the area weight, so its
+// transpose is the same two passes applied to y.  M_j = Lap(ph_s, y_j) comes from launch_tracer_lap (tracers.hip: the forward pass's
+// kernel) ahead of the reverse stage, and after the harmonic addition of a slot
+//     r -= ((kappa4[j] * hE) * dvdc[c,i]) * (M[k,c'] - M[k,c])              a third, separate addition
+// skipped by a wave-uniform branch for the tracers with kappa4[j] == 0, whose M is never written and never read.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void tracer_adj_update(const TracerAdjArgs &a, double r, double hc, double invA, double g, double sIn,
                                                   double &sOut, double &out, double &tau)
@@ -52,7 +57,7 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_adj_seed(const double *X, cons
 }
 
 // Generic form: LPC lanes span a column, one cell per lane group, index records; any K, any maxEdges (the shape of k_tracer_cell).
-template <int LPC, bool DIFF, bool SG>
+template <int LPC, bool DIFF, bool SG, bool BIH>
 __global__ __launch_bounds__(BLOCK) void k_tracer_adj_cell(const MeshDev m, const TracerAdjArgs a)
 {
     constexpr int NG = BLOCK / LPC;
@@ -65,12 +70,16 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_adj_cell(const MeshDev m, cons
             const double hc = a.ph[off];
             for (int j0 = 0; j0 < a.nT; j0 += TRA_TJ) {
                 const int nj = min(TRA_TJ, a.nT - j0);
-                double r[TRA_TJ], yc[TRA_TJ], kap[TRA_TJ];
+                double r[TRA_TJ], yc[TRA_TJ], kap[TRA_TJ], k4[BIH ? TRA_TJ : 1], mc[BIH ? TRA_TJ : 1];
 #pragma unroll
                 for (int jj = 0; jj < TRA_TJ; ++jj) {
                     r[jj] = 0.0;
                     yc[jj] = jj < nj ? a.y[(size_t)(j0 + jj) * a.stride + off] : 0.0;
                     kap[jj] = DIFF && jj < nj ? cptr(a.kappa)[j0 + jj] : 0.0;
+                    if (BIH) {
+                        k4[jj] = jj < nj ? cptr(a.kappa4)[j0 + jj] : 0.0;
+                        mc[jj] = k4[jj] != 0.0 ? a.lapy[(size_t)(j0 + jj) * a.stride + off] : 0.0;
+                    }
                 }
                 for (int i = 0; i < ME; ++i) {
                     const int e = cptr(m.eoc)[(size_t)c * ME + i];
@@ -86,6 +95,9 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_adj_cell(const MeshDev m, cons
                             const double yn = a.y[(size_t)(j0 + jj) * a.stride + noff];
                             r[jj] += w * (yc[jj] - yn);
                             if (DIFF) r[jj] += ((kap[jj] * hE) * dd) * (yn - yc[jj]);
+                            if (BIH)
+                                if (k4[jj] != 0.0)
+                                    r[jj] -= ((k4[jj] * hE) * dd) * (a.lapy[(size_t)(j0 + jj) * a.stride + noff] - mc[jj]);
                         }
                 }
 #pragma unroll
@@ -109,17 +121,19 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_adj_cell(const MeshDev m, cons
 // staged in LDS (the forward kernel's layout, hence its LDS formula and its chunking: tracer_kernel); a cell reads its neighbours'
 // cached rows in one burst and overwrites the lanes of foreign rows with masked global loads by byte offset.  The slot factors
 // (0.5 * F) * sdv are formed once per cell and pass and reused by the tracer loop; v = r / ph_s and ph_0 * (g + S) use the staged own row.
-template <int ME_, bool DIFF, bool SG>
+// BIH: a resident tracer takes a second row set, for M (row type 1 + chunk + jj), as in k_tracer_patch.
+template <int ME_, bool DIFF, bool SG, bool BIH>
 __global__ __launch_bounds__(TRA_NT, 2) void k_tracer_adj_patch(const MeshDev m, const TracerAdjArgs a, const int chunk)
 {
     constexpr int NG = TRA_NT / 32;
     static_assert(ME_ == 6, "burst width");
+    static_assert(DIFF || !BIH, "BIH instantiates only together with DIFF");
     extern __shared__ __align__(16) unsigned char tra_smem[];
     const int tid = threadIdx.x, grp = tid >> 5, l = tid & 31, K = m.K, CI = m.CI, mC = m.maxOwnC;
     const bool act = 2 * l < K;
     const unsigned rowB = (unsigned)K * 8u, lo = (unsigned)l * 16u;
     double *sRows = reinterpret_cast<double *>(tra_smem);                   // [1 + chunk][maxOwnC][K]  ph rows, then y rows per tracer
-    double *sSd = sRows + (size_t)(1 + chunk) * mC * K;                     // [maxOwnC][ME]  sdv
+    double *sSd = sRows + (size_t)(1 + (BIH ? 2 : 1) * chunk) * mC * K;     // (BIH: then M rows per tracer)  [maxOwnC][ME]  sdv
     double *sDd = sSd + (size_t)mC * ME_;                                   // [maxOwnC][ME]  dvdc (DIFF only)
     double *sIa = sDd + (DIFF ? (size_t)mC * ME_ : 0);                      // [maxOwnC]      invArea
     uint32_t *sRec = reinterpret_cast<uint32_t *>(sIa + mC);                // [maxOwnC][CI]  cRec
@@ -157,6 +171,14 @@ __global__ __launch_bounds__(TRA_NT, 2) void k_tracer_adj_patch(const MeshDev m,
                 }
             }
         }
+        if (BIH)      // the M rows of the pass's tracers with kappa4 != 0: row type 1 + chunk + jj
+            for (int jj = 0; jj < cj; ++jj) {
+                if (a.kappa4[j0 + jj] == 0.0) continue;
+                const char *src = reinterpret_cast<const char *>(a.lapy + (size_t)(j0 + jj) * a.stride);
+                double *dst = sRows + (size_t)(1 + chunk + jj) * mC * K;
+                for (int ci = grp; ci < nc; ci += NG)
+                    reinterpret_cast<double2 *>(dst + (size_t)ci * K)[l] = *reinterpret_cast<const double2 *>(src + (ownB + (unsigned)ci * rowB + lo));
+            }
     };
 
     {   // records: as in k_tracer_patch, the first TRA_NT entries of each list go through registers ahead of the first LDS write
@@ -243,6 +265,28 @@ __global__ __launch_bounds__(TRA_NT, 2) void k_tracer_adj_patch(const MeshDev m,
                     yy[i] = __builtin_bit_cast(double2, rp[i]);
                     if (!ch[i]) yy[i] = glb_row2(yG + gh[i]);
                 }
+                const double kap4 = BIH ? a.kappa4[j0 + jj] : 0.0;
+                const bool b4 = BIH && kap4 != 0.0;             // wave-uniform
+                double2 mm[BIH ? ME_ : 1], mc = make_double2(0.0, 0.0);
+                if (BIH) {
+#pragma unroll
+                    for (int i = 0; i < ME_; ++i) mm[i] = make_double2(0.0, 0.0);
+                    if (b4) {                                   // M gathered as y is, from its own row set
+                        const glb_bytes_t mG = (glb_bytes_t)(a.lapy + jo);
+                        const uint32_t ldsM = ldsH + (uint32_t)(1 + chunk + jj) * (uint32_t)mC * rowB;
+                        uint32_t al[ME_];
+                        v4u_t rl[ME_];
+#pragma unroll
+                        for (int i = 0; i < ME_; ++i) al[i] = ldsM + aoff[i];
+                        lds_burst<ME_>(rl, al);
+                        mc = reinterpret_cast<const double2 *>(sRows + ((size_t)(1 + chunk + jj) * mC + ci) * K)[l];
+#pragma unroll
+                        for (int i = 0; i < ME_; ++i) {
+                            mm[i] = __builtin_bit_cast(double2, rl[i]);
+                            if (!ch[i]) mm[i] = glb_row2(mG + gh[i]);
+                        }
+                    }
+                }
 #pragma unroll
                 for (int i = 0; i < ME_; ++i) {
                     double rx = r.x + w[i].x * (yc.x - yy[i].x), ry = r.y + w[i].y * (yc.y - yy[i].y);
@@ -250,6 +294,11 @@ __global__ __launch_bounds__(TRA_NT, 2) void k_tracer_adj_patch(const MeshDev m,
                         rx += ((kap * hE[i].x) * dd[i]) * (yy[i].x - yc.x);
                         ry += ((kap * hE[i].y) * dd[i]) * (yy[i].y - yc.y);
                     }
+                    if (BIH)
+                        if (b4) {
+                            rx -= ((kap4 * hE[i].x) * dd[i]) * (mm[i].x - mc.x);
+                            ry -= ((kap4 * hE[i].y) * dd[i]) * (mm[i].y - mc.y);
+                        }
                     r.x = okx[i] ? rx : r.x;
                     r.y = oky[i] ? ry : r.y;
                 }
@@ -270,11 +319,11 @@ __global__ __launch_bounds__(TRA_NT, 2) void k_tracer_adj_patch(const MeshDev m,
     }
 }
 
-// The reverse kernels stage what the forward ones do (ph rows and one gathered row set per resident tracer, the same records), so the
-// form, the LDS size and the chunk are tracer_kernel's: one decision for both directions.
-TracerKernel tracer_adjoint_kernel(const MeshDev &m, int lpc, int nT, bool generic, bool diff)
+// The reverse kernels stage what the forward ones do (ph rows and one gathered row set per resident tracer, two with bih, the same
+// records), so the form, the LDS size and the chunk are tracer_kernel's: one decision for both directions.
+TracerKernel tracer_adjoint_kernel(const MeshDev &m, int lpc, int nT, bool generic, bool diff, bool bih)
 {
-    return tracer_kernel(m, lpc, nT, generic, diff);
+    return tracer_kernel(m, lpc, nT, generic, diff, bih);
 }
 
 hipError_t launch_tracer_adj_seed(const MeshDev &m, const double *X, const double *hn, double *g, double *y, double b4, int nT,
@@ -288,28 +337,29 @@ hipError_t launch_tracer_adj_seed(const MeshDev &m, const double *X, const doubl
     return hipGetLastError();
 }
 
-template <int LPC, bool DIFF, bool SG>
+template <int LPC, bool DIFF, bool SG, bool BIH>
 static hipError_t launch_tracer_adj_cell(const MeshDev &m, const TracerAdjArgs &a, hipStream_t s)
 {
     const int ng = BLOCK / LPC;
     const int grid = std::min(std::max((m.nC + ng - 1) / ng, 1), 65536);
-    hipLaunchKernelGGL((k_tracer_adj_cell<LPC, DIFF, SG>), dim3(grid), dim3(BLOCK), 0, s, m, a);
+    hipLaunchKernelGGL((k_tracer_adj_cell<LPC, DIFF, SG, BIH>), dim3(grid), dim3(BLOCK), 0, s, m, a);
     return hipGetLastError();
 }
 
-template <bool DIFF, bool SG>
+template <bool DIFF, bool SG, bool BIH>
 static hipError_t launch_tracer_adj_patch(const MeshDev &m, const TracerAdjArgs &a, const TracerKernel &k, hipStream_t s)
 {
     if (k.lds > 64 * 1024)
-        if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_tracer_adj_patch<6, DIFF, SG>)}, 80 * 1024); e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_tracer_adj_patch<6, DIFF, SG>), dim3(patch_grid(m)), dim3(TRA_NT), k.lds, s, m, a, k.chunk);
+        if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_tracer_adj_patch<6, DIFF, SG, BIH>)}, 80 * 1024); e != hipSuccess)
+            return e;
+    hipLaunchKernelGGL((k_tracer_adj_patch<6, DIFF, SG, BIH>), dim3(patch_grid(m)), dim3(TRA_NT), k.lds, s, m, a, k.chunk);
     return hipGetLastError();
 }
 
-template <bool DIFF, bool SG>
+template <bool DIFF, bool SG, bool BIH>
 static hipError_t launch_tracer_adj_generic(const MeshDev &m, const TracerAdjArgs &a, int lpc, hipStream_t s)
 {
-#define CALL(L) launch_tracer_adj_cell<L, DIFF, SG>(m, a, s)
+#define CALL(L) launch_tracer_adj_cell<L, DIFF, SG, BIH>(m, a, s)
     DISPATCH_LPC(lpc, CALL)
 #undef CALL
 }
@@ -319,10 +369,13 @@ hipError_t launch_tracer_adjoint(const MeshDev &m, const TracerAdjArgs &a, int l
     if (a.nT <= 0) return hipSuccess;
     const bool diff = a.kappa != nullptr;       // (then a.dvdc is set too: moka_tracer_adjoint_sweep)
     const bool sg = a.G != nullptr;             // (some tracer's source gradient is wanted: moka_tracer_adjoint_sweep)
-    const TracerKernel k = tracer_adjoint_kernel(m, lpc, a.nT, generic, diff);
-#define PICK(F, ...)                                                                            \
-    (diff ? (sg ? F<true, true>(__VA_ARGS__) : F<true, false>(__VA_ARGS__))                       \
-          : (sg ? F<false, true>(__VA_ARGS__) : F<false, false>(__VA_ARGS__)))
+    const bool bih = a.kappa4 != nullptr;       // (then a.lapy, a.kappa and a.dvdc are set too: moka_tracer_adjoint_sweep)
+    if (bih && !diff) return hipErrorInvalidValue;      // BIH instantiates only together with DIFF
+    const TracerKernel k = tracer_adjoint_kernel(m, lpc, a.nT, generic, diff, bih);
+#define PICK(F, ...)                                                                                          \
+    (bih    ? (sg ? F<true, true, true>(__VA_ARGS__) : F<true, false, true>(__VA_ARGS__))                       \
+     : diff ? (sg ? F<true, true, false>(__VA_ARGS__) : F<true, false, false>(__VA_ARGS__))                     \
+            : (sg ? F<false, true, false>(__VA_ARGS__) : F<false, false, false>(__VA_ARGS__)))
     if (k.form == 1) return PICK(launch_tracer_adj_patch, m, a, k, s);
     return PICK(launch_tracer_adj_generic, m, a, lpc, s);
 #undef PICK

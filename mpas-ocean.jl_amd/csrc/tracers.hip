@@ -20,6 +20,12 @@ namespace moka {
 // own, for the tracers whose entry of TracerArgs::src is not nullptr; the others read no source byte and add nothing.  T is never -0.0
 // there (it starts at +0.0 and x + (-x) = +0.0), so a source of +-0.0 leaves its bits alone.  The source element is the cell's own,
 // read from global memory beside hnext, cphi and qn: nothing of it is staged.  SRC == false is the code of a state without sources.
+// BIH (moka_set_tracer_biharmonic: some kappa4_j != 0; only together with DIFF) adds -div(kappa4_j h_e grad L_j) with
+// L_j = Lap(ph, pphi_j) of launch_tracer_lap (further down): after the harmonic addition of a slot, a third, separate one,
+//     T -= ((((kappa4[j] * hE) * (L[k,c'] - L[k,c])) * dvdc[c,i]) * invArea[c])
+// skipped by a wave-uniform branch for the tracers with kappa4[j] == 0, whose L is never written and never read (an uninitialised NaN
+// times zero would be NaN).  A constant tracer has L == 0 exactly; the product is antisymmetric between the two cells of an edge.
+// BIH == false is the code of a state that never set a kappa4.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void tracer_update(const TracerArgs &a, double t, double cphi, double hcur, double hnext, double qnIn,
                                               double &pOut, double &qOut)
@@ -33,7 +39,7 @@ __device__ __forceinline__ void tracer_update(const TracerArgs &a, double t, dou
 constexpr int TR_TJ = 4;      // tracers whose sums a lane of k_tracer_cell carries at once (F is formed once per TR_TJ tracers)
 
 // Generic form: LPC lanes span a column, one cell per lane group, index records; any K, any maxEdges (the shape of k_nl_cell).
-template <int LPC, bool DIFF, bool SRC>
+template <int LPC, bool DIFF, bool SRC, bool BIH>
 __global__ __launch_bounds__(BLOCK) void k_tracer_cell(const MeshDev m, const TracerArgs a)
 {
     constexpr int NG = BLOCK / LPC;
@@ -47,12 +53,16 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_cell(const MeshDev m, const Tr
             const double hc = a.ph[off], hnext = a.hnext[off], hcur = s4 ? 0.0 : a.hcur[off];
             for (int j0 = 0; j0 < a.nT; j0 += TR_TJ) {
                 const int nj = min(TR_TJ, a.nT - j0);
-                double t[TR_TJ], pc[TR_TJ], kap[TR_TJ];
+                double t[TR_TJ], pc[TR_TJ], kap[TR_TJ], k4[BIH ? TR_TJ : 1], lc[BIH ? TR_TJ : 1];
 #pragma unroll
                 for (int jj = 0; jj < TR_TJ; ++jj) {
                     t[jj] = 0.0;
                     pc[jj] = jj < nj ? a.pphi[(size_t)(j0 + jj) * a.stride + off] : 0.0;
                     kap[jj] = DIFF && jj < nj ? cptr(a.kappa)[j0 + jj] : 0.0;
+                    if (BIH) {
+                        k4[jj] = jj < nj ? cptr(a.kappa4)[j0 + jj] : 0.0;
+                        lc[jj] = k4[jj] != 0.0 ? a.lap[(size_t)(j0 + jj) * a.stride + off] : 0.0;
+                    }
                 }
                 for (int i = 0; i < ME; ++i) {
                     const int e = cptr(m.eoc)[(size_t)c * ME + i];
@@ -69,6 +79,9 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_cell(const MeshDev m, const Tr
                             const double pE = 0.5 * (pc[jj] + pn);
                             t[jj] += ((F * pE) * sd) * invA;
                             if (DIFF) t[jj] += (((kap[jj] * hE) * (pn - pc[jj])) * dd) * invA;
+                            if (BIH)
+                                if (k4[jj] != 0.0)
+                                    t[jj] -= (((k4[jj] * hE) * (a.lap[(size_t)(j0 + jj) * a.stride + noff] - lc[jj])) * dd) * invA;
                         }
                 }
 #pragma unroll
@@ -94,20 +107,22 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_cell(const MeshDev m, const Tr
 // of foreign rows with exec-masked global loads by 32-bit byte offset (k_nl_prep5's row cache).  `chunk` tracers' rows are resident
 // at a time: a state with more takes further passes over the patch (the pphi rows re-staged, F re-formed once per pass).
 // DIFF: the patch's dvdc entries are staged beside sdv, and a cell keeps hE of its slots beside F.  SRC: one more own-row load per
-// sourced tracer, not staged (the LDS layout and the chunking do not know about sources).
+// sourced tracer, not staged (the LDS layout and the chunking do not know about sources).  BIH: a resident tracer takes a second row
+// set, for L (row type 1 + chunk + jj), staged and gathered as pphi is -- for the tracers with kappa4 != 0 only.
 constexpr int TR_NT = 256;
 
-template <int ME_, bool DIFF, bool SRC>
+template <int ME_, bool DIFF, bool SRC, bool BIH>
 __global__ __launch_bounds__(TR_NT, 2) void k_tracer_patch(const MeshDev m, const TracerArgs a, const int chunk)
 {
     constexpr int NG = TR_NT / 32;
     static_assert(ME_ == 6, "burst width");
+    static_assert(DIFF || !BIH, "BIH instantiates only together with DIFF");
     extern __shared__ __align__(16) unsigned char tr_smem[];
     const int tid = threadIdx.x, grp = tid >> 5, l = tid & 31, K = m.K, CI = m.CI, mC = m.maxOwnC;
     const bool act = 2 * l < K;
     const unsigned rowB = (unsigned)K * 8u, lo = (unsigned)l * 16u;
     double *sRows = reinterpret_cast<double *>(tr_smem);                    // [1 + chunk][maxOwnC][K]  ph rows, then pphi rows per tracer
-    double *sSd = sRows + (size_t)(1 + chunk) * mC * K;                     // [maxOwnC][ME]  sdv
+    double *sSd = sRows + (size_t)(1 + (BIH ? 2 : 1) * chunk) * mC * K;     // (BIH: then L rows per tracer)  [maxOwnC][ME]  sdv
     double *sDd = sSd + (size_t)mC * ME_;                                   // [maxOwnC][ME]  dvdc (DIFF only)
     double *sIa = sDd + (DIFF ? (size_t)mC * ME_ : 0);                      // [maxOwnC]      invArea
     uint32_t *sRec = reinterpret_cast<uint32_t *>(sIa + mC);                // [maxOwnC][CI]  cRec
@@ -146,6 +161,14 @@ __global__ __launch_bounds__(TR_NT, 2) void k_tracer_patch(const MeshDev m, cons
                 }
             }
         }
+        if (BIH)      // the L rows of the pass's tracers with kappa4 != 0: row type 1 + chunk + jj
+            for (int jj = 0; jj < cj; ++jj) {
+                if (a.kappa4[j0 + jj] == 0.0) continue;
+                const char *src = reinterpret_cast<const char *>(a.lap + (size_t)(j0 + jj) * a.stride);
+                double *dst = sRows + (size_t)(1 + chunk + jj) * mC * K;
+                for (int ci = grp; ci < nc; ci += NG)
+                    reinterpret_cast<double2 *>(dst + (size_t)ci * K)[l] = *reinterpret_cast<const double2 *>(src + (ownB + (unsigned)ci * rowB + lo));
+            }
     };
 
     {   // records: the first TR_NT entries of each list go through registers, so that every global load of the phase (rows included)
@@ -235,6 +258,28 @@ __global__ __launch_bounds__(TR_NT, 2) void k_tracer_patch(const MeshDev m, cons
                     pp[i] = __builtin_bit_cast(double2, rp[i]);
                     if (!ch[i]) pp[i] = glb_row2(pG + gh[i]);
                 }
+                const double kap4 = BIH ? a.kappa4[j0 + jj] : 0.0;
+                const bool b4 = BIH && kap4 != 0.0;             // wave-uniform
+                double2 ll[BIH ? ME_ : 1], lc = make_double2(0.0, 0.0);
+                if (BIH) {
+#pragma unroll
+                    for (int i = 0; i < ME_; ++i) ll[i] = make_double2(0.0, 0.0);
+                    if (b4) {                                   // L gathered as pphi is, from its own row set
+                        const glb_bytes_t lG = (glb_bytes_t)(a.lap + jo);
+                        const uint32_t ldsL = ldsH + (uint32_t)(1 + chunk + jj) * (uint32_t)mC * rowB;
+                        uint32_t al[ME_];
+                        v4u_t rl[ME_];
+#pragma unroll
+                        for (int i = 0; i < ME_; ++i) al[i] = ldsL + aoff[i];
+                        lds_burst<ME_>(rl, al);
+                        lc = reinterpret_cast<const double2 *>(sRows + ((size_t)(1 + chunk + jj) * mC + ci) * K)[l];
+#pragma unroll
+                        for (int i = 0; i < ME_; ++i) {
+                            ll[i] = __builtin_bit_cast(double2, rl[i]);
+                            if (!ch[i]) ll[i] = glb_row2(lG + gh[i]);
+                        }
+                    }
+                }
 #pragma unroll
                 for (int i = 0; i < ME_; ++i) {
                     const double ex = 0.5 * (pc.x + pp[i].x), ey = 0.5 * (pc.y + pp[i].y);
@@ -243,6 +288,11 @@ __global__ __launch_bounds__(TR_NT, 2) void k_tracer_patch(const MeshDev m, cons
                         tx += (((kap * hE[i].x) * (pp[i].x - pc.x)) * dd[i]) * invA;
                         ty += (((kap * hE[i].y) * (pp[i].y - pc.y)) * dd[i]) * invA;
                     }
+                    if (BIH)
+                        if (b4) {
+                            tx -= (((kap4 * hE[i].x) * (ll[i].x - lc.x)) * dd[i]) * invA;
+                            ty -= (((kap4 * hE[i].y) * (ll[i].y - lc.y)) * dd[i]) * invA;
+                        }
                     t.x = okx[i] ? tx : t.x;
                     t.y = oky[i] ? ty : t.y;
                 }
@@ -264,47 +314,49 @@ __global__ __launch_bounds__(TR_NT, 2) void k_tracer_patch(const MeshDev m, cons
     }
 }
 
-static inline size_t tracer_patch_lds(const MeshDev &m, int chunk, bool diff)
+static inline size_t tracer_patch_lds(const MeshDev &m, int chunk, bool diff, bool bih)
 {
-    return (size_t)(1 + chunk) * m.maxOwnC * m.K * 8 + (size_t)m.maxOwnC * (m.ME + 1) * 8 + (size_t)m.maxOwnC * (m.CI + m.ME) * 4 +
-           (diff ? (size_t)m.maxOwnC * m.ME * 8 : 0);
+    return (size_t)(1 + (bih ? 2 : 1) * chunk) * m.maxOwnC * m.K * 8 + (size_t)m.maxOwnC * (m.ME + 1) * 8 +
+           (size_t)m.maxOwnC * (m.CI + m.ME) * 4 + (diff ? (size_t)m.maxOwnC * m.ME * 8 : 0);
 }
 
-TracerKernel tracer_kernel(const MeshDev &m, int lpc, int nT, bool generic, bool diff)
+TracerKernel tracer_kernel(const MeshDev &m, int lpc, int nT, bool generic, bool diff, bool bih)
 {
     if (!generic && lpc == 64 && m.K >= 34 && m.K <= 64 && !(m.K & 1) && m.ME == 6 && m.cRec && m.maxOwnC > 0) {
-        // as many tracers' rows resident as 80 KB hold (two workgroups per CU), at least one
-        const size_t budget = 80 * 1024, fixed = tracer_patch_lds(m, 0, diff), perT = (size_t)m.maxOwnC * m.K * 8;
+        // as many tracers' rows resident as 80 KB hold (two workgroups per CU), at least one; with bih a resident tracer takes two row
+        // sets (pphi and L), so half as many fit, and the generic form serves when not even one tracer's two sets do
+        const size_t budget = 80 * 1024, fixed = tracer_patch_lds(m, 0, diff, bih), perT = (size_t)m.maxOwnC * m.K * 8 * (bih ? 2 : 1);
         if (fixed + perT <= budget) {
             const int chunk = (int)std::min<size_t>((size_t)std::max(nT, 1), (budget - fixed) / perT);
-            return {1, tracer_patch_lds(m, chunk, diff), chunk};
+            return {1, tracer_patch_lds(m, chunk, diff, bih), chunk};
         }
     }
     return {2, 0, 0};
 }
 
-template <int LPC, bool DIFF, bool SRC>
+template <int LPC, bool DIFF, bool SRC, bool BIH>
 static hipError_t launch_tracer_cell(const MeshDev &m, const TracerArgs &a, hipStream_t s)
 {
     const int ng = BLOCK / LPC;
     const int grid = std::min(std::max((m.nC + ng - 1) / ng, 1), 65536);
-    hipLaunchKernelGGL((k_tracer_cell<LPC, DIFF, SRC>), dim3(grid), dim3(BLOCK), 0, s, m, a);
+    hipLaunchKernelGGL((k_tracer_cell<LPC, DIFF, SRC, BIH>), dim3(grid), dim3(BLOCK), 0, s, m, a);
     return hipGetLastError();
 }
 
-template <bool DIFF, bool SRC>
+template <bool DIFF, bool SRC, bool BIH>
 static hipError_t launch_tracer_patch(const MeshDev &m, const TracerArgs &a, const TracerKernel &k, hipStream_t s)
 {
     if (k.lds > 64 * 1024)
-        if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_tracer_patch<6, DIFF, SRC>)}, 80 * 1024); e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_tracer_patch<6, DIFF, SRC>), dim3(patch_grid(m)), dim3(TR_NT), k.lds, s, m, a, k.chunk);
+        if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_tracer_patch<6, DIFF, SRC, BIH>)}, 80 * 1024); e != hipSuccess)
+            return e;
+    hipLaunchKernelGGL((k_tracer_patch<6, DIFF, SRC, BIH>), dim3(patch_grid(m)), dim3(TR_NT), k.lds, s, m, a, k.chunk);
     return hipGetLastError();
 }
 
-template <bool DIFF, bool SRC>
+template <bool DIFF, bool SRC, bool BIH>
 static hipError_t launch_tracer_generic(const MeshDev &m, const TracerArgs &a, int lpc, hipStream_t s)
 {
-#define CALL(L) launch_tracer_cell<L, DIFF, SRC>(m, a, s)
+#define CALL(L) launch_tracer_cell<L, DIFF, SRC, BIH>(m, a, s)
     DISPATCH_LPC(lpc, CALL)
 #undef CALL
 }
@@ -314,13 +366,210 @@ hipError_t launch_tracers(const MeshDev &m, const TracerArgs &a, int lpc, bool g
     if (a.nT <= 0) return hipSuccess;
     const bool diff = a.kappa != nullptr;       // (then a.dvdc is set too: tracer_stage)
     const bool src = a.src != nullptr;          // (some tracer of the state has a source: tracer_stage)
-    const TracerKernel k = tracer_kernel(m, lpc, a.nT, generic, diff);
-#define PICK(F, ...)                                                                            \
-    (diff ? (src ? F<true, true>(__VA_ARGS__) : F<true, false>(__VA_ARGS__))                      \
-          : (src ? F<false, true>(__VA_ARGS__) : F<false, false>(__VA_ARGS__)))
+    const bool bih = a.kappa4 != nullptr;       // (then a.lap, a.kappa and a.dvdc are set too: tracer_stage)
+    if (bih && !diff) return hipErrorInvalidValue;      // BIH instantiates only together with DIFF
+    const TracerKernel k = tracer_kernel(m, lpc, a.nT, generic, diff, bih);
+#define PICK(F, ...)                                                                                          \
+    (bih    ? (src ? F<true, true, true>(__VA_ARGS__) : F<true, false, true>(__VA_ARGS__))                      \
+     : diff ? (src ? F<true, true, false>(__VA_ARGS__) : F<true, false, false>(__VA_ARGS__))                    \
+            : (src ? F<false, true, false>(__VA_ARGS__) : F<false, false, false>(__VA_ARGS__)))
     if (k.form == 1) return PICK(launch_tracer_patch, m, a, k, s);
     return PICK(launch_tracer_generic, m, a, lpc, s);
 #undef PICK
+}
+
+// ------------------------------------------------------------------------------------------------
+// The Laplacian pass (TracerLapArgs, kernels.hpp): out_j = Lap(ph, x_j) for every field with kappa4[j] != 0, one launch.  One kernel
+// with two callers: the forward step hands it (ph_s, pphi), the reverse sweep (ph_s, y).  It does not read u.
+// ------------------------------------------------------------------------------------------------
+// Generic form: k_tracer_cell's shape.
+template <int LPC>
+__global__ __launch_bounds__(BLOCK) void k_tracer_lap_cell(const MeshDev m, const TracerLapArgs a)
+{
+    constexpr int NG = BLOCK / LPC;
+    const int grp = uniform_if_wave<LPC>(threadIdx.x / LPC), l = threadIdx.x % LPC;
+    const int K = m.K, ME = m.ME;
+    for (int c = blockIdx.x * NG + grp; c < m.nC; c += gridDim.x * NG) {
+        const double invA = cptr(m.invArea)[c];
+        for (int k = l; k < K; k += LPC) {
+            const size_t off = (size_t)c * K + k;
+            const double hc = a.ph[off];
+            for (int j0 = 0; j0 < a.nT; j0 += TR_TJ) {
+                const int nj = min(TR_TJ, a.nT - j0);
+                double s[TR_TJ], xc[TR_TJ];
+                bool on[TR_TJ];
+                bool any = false;
+#pragma unroll
+                for (int jj = 0; jj < TR_TJ; ++jj) {
+                    on[jj] = jj < nj && cptr(a.kappa4)[j0 + jj] != 0.0;      // wave-uniform
+                    any = any || on[jj];
+                    s[jj] = 0.0;
+                    xc[jj] = on[jj] ? a.x[(size_t)(j0 + jj) * a.stride + off] : 0.0;
+                }
+                if (!any) continue;
+                for (int i = 0; i < ME; ++i) {
+                    const int e = cptr(m.eoc)[(size_t)c * ME + i];
+                    if (e < 0 || k >= cptr(m.mltc)[(size_t)c * ME + i]) continue;
+                    const size_t noff = (size_t)cptr(m.coc)[(size_t)c * ME + i] * K + k;
+                    const double hE = 0.5 * (hc + a.ph[noff]);
+                    const double dd = cptr(a.dvdc)[(size_t)c * ME + i];
+#pragma unroll
+                    for (int jj = 0; jj < TR_TJ; ++jj)
+                        if (on[jj]) s[jj] += (hE * (a.x[(size_t)(j0 + jj) * a.stride + noff] - xc[jj])) * dd;
+                }
+#pragma unroll
+                for (int jj = 0; jj < TR_TJ; ++jj)
+                    if (on[jj]) a.out[(size_t)(j0 + jj) * a.stride + off] = (s[jj] * invA) / hc;
+            }
+        }
+    }
+}
+
+// Patch form: k_tracer_patch's shape and LDS layout with dvdc where that one keeps sdv -- the patch's cRec records, dvdc, invArea and
+// maxLevelEdgeTop entries, the ph rows and the x rows of `chunk` fields of its own cells in LDS; neighbours' rows in one burst, foreign
+// rows by masked global loads at 32-bit byte offsets.  Fields with kappa4 == 0 are not staged, not gathered, not written.
+template <int ME_>
+__global__ __launch_bounds__(TR_NT, 2) void k_tracer_lap_patch(const MeshDev m, const TracerLapArgs a, const int chunk)
+{
+    constexpr int NG = TR_NT / 32;
+    static_assert(ME_ == 6, "burst width");
+    extern __shared__ __align__(16) unsigned char trl_smem[];
+    const int tid = threadIdx.x, grp = tid >> 5, l = tid & 31, K = m.K, CI = m.CI, mC = m.maxOwnC;
+    const bool act = 2 * l < K;
+    const unsigned rowB = (unsigned)K * 8u, lo = (unsigned)l * 16u;
+    double *sRows = reinterpret_cast<double *>(trl_smem);                   // [1 + chunk][maxOwnC][K]  ph rows, then x rows per field
+    double *sDd = sRows + (size_t)(1 + chunk) * mC * K;                     // [maxOwnC][ME]  dvdc
+    double *sIa = sDd + (size_t)mC * ME_;                                   // [maxOwnC]      invArea
+    uint32_t *sRec = reinterpret_cast<uint32_t *>(sIa + mC);                // [maxOwnC][CI]  cRec
+    int *sMl = reinterpret_cast<int *>(sRec + (size_t)mC * CI);             // [maxOwnC][ME]  maxLevelEdgeTop of the slot's edge
+    const int pl_ = patch_of_block(m.nPatches);
+    if (pl_ >= m.nPatches) return;
+    const int p = pl_ + m.patchBegin;
+    const int c0 = m.patchCellStart[p], nc = m.patchCellStart[p + 1] - c0;
+    const unsigned ownB = (unsigned)c0 * rowB, ownN = (unsigned)nc * rowB;
+    const glb_bytes_t hG = (glb_bytes_t)a.ph;
+    const uint32_t ldsH = (uint32_t)(size_t)sRows + lo;
+
+    // row set ty of the cache (0 = ph, 1 + jj = field j0 + jj) from global memory, the patch's own cells
+    auto stage_set = [&](int ty, const double *base) {
+        if (!act) return;
+        const char *src = reinterpret_cast<const char *>(base);
+        double *dst = sRows + (size_t)ty * mC * K;
+        for (int ci = grp; ci < nc; ci += NG)
+            reinterpret_cast<double2 *>(dst + (size_t)ci * K)[l] = *reinterpret_cast<const double2 *>(src + (ownB + (unsigned)ci * rowB + lo));
+    };
+    auto stage_fields = [&](int j0, int cj) {
+        for (int jj = 0; jj < cj; ++jj)
+            if (a.kappa4[j0 + jj] != 0.0) stage_set(1 + jj, a.x + (size_t)(j0 + jj) * a.stride);
+    };
+
+    {
+        const int nRec = nc * CI, nSd = nc * ME_;
+        stage_set(0, a.ph);
+        stage_fields(0, min(chunk, a.nT));
+        for (int i = tid; i < nRec; i += TR_NT) sRec[i] = m.cRec[(size_t)c0 * CI + i];
+        for (int i = tid; i < nSd; i += TR_NT) { sDd[i] = a.dvdc[(size_t)c0 * ME_ + i]; sMl[i] = m.mltc[(size_t)c0 * ME_ + i]; }
+        for (int i = tid; i < nc; i += TR_NT) sIa[i] = m.invArea[c0 + i];
+    }
+    for (int j0 = 0; j0 < a.nT; j0 += chunk) {
+        const int cj = min(chunk, a.nT - j0);
+        if (j0 > 0) {
+            __syncthreads();                      // the previous pass has read its rows
+            stage_fields(j0, cj);
+        }
+        __syncthreads();
+        if (!act) continue;
+        for (int ci = grp; ci < nc; ci += NG) {
+            const uint32_t *rec = sRec + (size_t)ci * CI;
+            const unsigned mask = rec[2 * ME_];
+            double2 hE[ME_];
+            bool ch[ME_], okx[ME_], oky[ME_];
+            uint32_t aoff[ME_], gh[ME_];
+            const double2 hc = reinterpret_cast<const double2 *>(sRows + (size_t)ci * K)[l];
+            {
+                uint32_t ah[ME_];
+                v4u_t rh[ME_];
+#pragma unroll
+                for (int i = 0; i < ME_; ++i) {        // cached row or row 0 of the cache (then overwritten by the masked global load)
+                    const unsigned ho = rec[ME_ + i], loc = ho - ownB;
+                    ch[i] = loc < ownN;
+                    aoff[i] = ch[i] ? loc : 0u;
+                    gh[i] = ho + lo;
+                    asm("" : "+v"(gh[i]));             // the offset stays in a VGPR (see k_nl_prep5)
+                    ah[i] = ldsH + aoff[i];
+                }
+                lds_burst<ME_>(rh, ah);
+#pragma unroll
+                for (int i = 0; i < ME_; ++i) {
+                    double2 hh = __builtin_bit_cast(double2, rh[i]);
+                    if (!ch[i]) hh = glb_row2(hG + gh[i]);
+                    hE[i] = make_double2(0.5 * (hc.x + hh.x), 0.5 * (hc.y + hh.y));
+                    const int ml = sMl[ci * ME_ + i];
+                    const bool valid = (mask >> i) & 1u;
+                    okx[i] = valid && 2 * l < ml;
+                    oky[i] = valid && 2 * l + 1 < ml;
+                }
+            }
+            const double *dd = sDd + ci * ME_;
+            const double invA = sIa[ci];
+            const unsigned orow = ownB + (unsigned)ci * rowB + lo;       // the cell's own row in every (K, nC) array
+            for (int jj = 0; jj < cj; ++jj) {
+                if (a.kappa4[j0 + jj] == 0.0) continue;                  // wave-uniform
+                const size_t jo = (size_t)(j0 + jj) * a.stride;
+                const glb_bytes_t xG = (glb_bytes_t)(a.x + jo);
+                const uint32_t ldsX = ldsH + (uint32_t)(1 + jj) * (uint32_t)mC * rowB;
+                uint32_t ap[ME_];
+                v4u_t rp[ME_];
+#pragma unroll
+                for (int i = 0; i < ME_; ++i) ap[i] = ldsX + aoff[i];
+                lds_burst<ME_>(rp, ap);
+                const double2 xc = reinterpret_cast<const double2 *>(sRows + ((size_t)(1 + jj) * mC + ci) * K)[l];
+                double2 s = make_double2(0.0, 0.0);
+                double2 xx[ME_];
+#pragma unroll
+                for (int i = 0; i < ME_; ++i) {
+                    xx[i] = __builtin_bit_cast(double2, rp[i]);
+                    if (!ch[i]) xx[i] = glb_row2(xG + gh[i]);
+                }
+#pragma unroll
+                for (int i = 0; i < ME_; ++i) {
+                    const double sx = s.x + (hE[i].x * (xx[i].x - xc.x)) * dd[i], sy = s.y + (hE[i].y * (xx[i].y - xc.y)) * dd[i];
+                    s.x = okx[i] ? sx : s.x;
+                    s.y = oky[i] ? sy : s.y;
+                }
+                gstore2(a.out + jo, orow, make_double2((s.x * invA) / hc.x, (s.y * invA) / hc.y));
+            }
+        }
+    }
+}
+
+TracerKernel tracer_lap_kernel(const MeshDev &m, int lpc, int nT, bool generic)
+{
+    return tracer_kernel(m, lpc, nT, generic, false, false);
+}
+
+template <int LPC>
+static hipError_t launch_tracer_lap_cell(const MeshDev &m, const TracerLapArgs &a, hipStream_t s)
+{
+    const int ng = BLOCK / LPC;
+    const int grid = std::min(std::max((m.nC + ng - 1) / ng, 1), 65536);
+    hipLaunchKernelGGL((k_tracer_lap_cell<LPC>), dim3(grid), dim3(BLOCK), 0, s, m, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_tracer_lap(const MeshDev &m, const TracerLapArgs &a, int lpc, bool generic, hipStream_t s)
+{
+    if (a.nT <= 0) return hipSuccess;
+    const TracerKernel k = tracer_lap_kernel(m, lpc, a.nT, generic);
+    if (k.form == 1) {
+        if (k.lds > 64 * 1024)
+            if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_tracer_lap_patch<6>)}, 80 * 1024); e != hipSuccess) return e;
+        hipLaunchKernelGGL((k_tracer_lap_patch<6>), dim3(patch_grid(m)), dim3(TR_NT), k.lds, s, m, a, k.chunk);
+        return hipGetLastError();
+    }
+#define CALL(L) launch_tracer_lap_cell<L>(m, a, s)
+    DISPATCH_LPC(lpc, CALL)
+#undef CALL
 }
 
 }  // namespace moka

@@ -458,7 +458,9 @@ end
 # fields: (nVertLevels, nCells) matrices, uploaded into both time levels; an empty vector removes the tracers again.
 # diffusivity: harmonic diffusion div(kappa h_e grad phi) beside the transport -- one value (m^2/s, >= 0) for all tracers or one per
 # tracer; nothing leaves them undiffused.  The explicit stability limit (kappa dt / dcEdge_min^2 <~ 0.35) is not checked.
-function set_tracers!(Prog::MProg, fields::Vector{Matrix{Float64}}; diffusivity = nothing)
+# biharmonic: -div(kappa4 h_e grad L), L the thickness-weighted Laplacian of phi -- one coefficient (m^4/s, >= 0) for all tracers or one
+# per tracer; nothing leaves the term off.  Its limit (kappa4 dt / dcEdge_min^4 <~ 0.043, shared with kappa) is not checked either.
+function set_tracers!(Prog::MProg, fields::Vector{Matrix{Float64}}; diffusivity = nothing, biharmonic = nothing)
     s = Prog.ssh[end].state
     s === nothing && error("MokaHIP: the model is not on the device yet")
     check(ccall((:moka_set_tracers, lib), Cint, (Ptr{Cvoid}, Int32), s.handle, length(fields)), s.backend.ctx)
@@ -470,6 +472,19 @@ function set_tracers!(Prog::MProg, fields::Vector{Matrix{Float64}}; diffusivity 
         length(kappa) == length(fields) || error("MokaHIP: $(length(kappa)) diffusivities for $(length(fields)) tracers")
         check(ccall((:moka_set_tracer_diffusion, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), s.handle, kappa), s.backend.ctx)
     end
+    if biharmonic !== nothing
+        kappa4 = biharmonic isa Number ? fill(Float64(biharmonic), length(fields)) : Vector{Float64}(biharmonic)
+        length(kappa4) == length(fields) || error("MokaHIP: $(length(kappa4)) biharmonic coefficients for $(length(fields)) tracers")
+        check(ccall((:moka_set_tracer_biharmonic, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), s.handle, kappa4), s.backend.ctx)
+    end
+end
+# the biharmonic coefficient of tracer j (1-based), 0.0 unless set_tracers! was given one
+function tracer_biharmonic(Prog::MProg, j::Integer)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    out = Ref{Float64}(0.0)
+    check(ccall((:moka_tracer_biharmonic, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), s.handle, j - 1, out), s.backend.ctx)
+    out[]
 end
 # the diffusivity of tracer j (1-based), 0.0 unless set_tracers! was given one
 function tracer_diffusivity(Prog::MProg, j::Integer)

@@ -639,6 +639,30 @@ class Tracers:
             out[j] = v.value
         return out
 
+    def set_biharmonic(self, values):
+        """moka_set_tracer_biharmonic: biharmonic diffusion -div(kappa4 h_e grad L), L the thickness-weighted Laplacian of phi, beside
+        the transport and the harmonic term.  `values`: one coefficient (m^4/s, finite, >= 0) for every tracer or one per tracer; None
+        or 0 switches it off.  Takes effect with the next RK4 step or run.  The explicit stability limit
+        (kappa4 dt / dcEdge_min^4 <~ 0.043, shared with the harmonic part) is not checked."""
+        k = None
+        if values is not None:
+            k = np.asarray(values, dtype=np.float64)
+            k = np.full(self.n, float(k)) if k.ndim == 0 else np.ascontiguousarray(k.ravel())
+            if k.size != self.n:
+                raise ValueError(f"biharmonic: {k.size} values for {self.n} tracers")
+        if k is not None and self.n == 0 and not k.size:
+            k = None
+        L.check(L.lib().moka_set_tracer_biharmonic(self._s._h, None if k is None else k.ctypes.data), self._s.mesh.backend._h)
+
+    def biharmonic(self) -> np.ndarray:
+        """moka_tracer_biharmonic: the biharmonic coefficient of every tracer (zeros unless set_biharmonic was called)."""
+        out = np.zeros(self.n, dtype=np.float64)
+        v = C.c_double()
+        for j in range(self.n):
+            L.check(L.lib().moka_tracer_biharmonic(self._s._h, j, C.byref(v)), self._s.mesh.backend._h)
+            out[j] = v.value
+        return out
+
     def set_source(self, j: int, a):
         """moka_tracer_source_upload: the source q_j of tracer j, an (nCells, K) field in tracer * m/s (the rate of change of the
         content h phi), constant in time until changed; None removes it.  Takes effect with the next RK4 step or run.  Every value
@@ -661,12 +685,13 @@ class Tracers:
         return bool(v.value)
 
 
-def set_tracers(Prog: "PrognosticVars", arrays, diffusivity=None, sources=None) -> Tracers:
+def set_tracers(Prog: "PrognosticVars", arrays, diffusivity=None, sources=None, biharmonic=None) -> Tracers:
     """Give this model passive tracers (moka_set_tracers): `arrays` is a list of (nCells, K) fields, uploaded into both time levels;
     an empty list removes the tracers again.  An extension (the reference has none): centred flux-form transport by the thickness
     flux inside RK4 steps (include/moka_hip.h states the algebra); Forward Euler, tapes and halos refuse a state with tracers.
     diffusivity: a scalar or one value per tracer (Tracers.set_diffusivity); None leaves the tracers undiffused.
-    sources: one entry per tracer, an (nCells, K) field or None for a tracer without a source (Tracers.set_source)."""
+    sources: one entry per tracer, an (nCells, K) field or None for a tracer without a source (Tracers.set_source).
+    biharmonic: a scalar or one coefficient per tracer (Tracers.set_biharmonic); None leaves the term off."""
     s = Prog._state
     arrays = list(arrays)
     L.check(L.lib().moka_set_tracers(s._h, len(arrays)), s.mesh.backend._h)
@@ -676,6 +701,8 @@ def set_tracers(Prog: "PrognosticVars", arrays, diffusivity=None, sources=None) 
         tr.set(j, a, 1)
     if diffusivity is not None:
         tr.set_diffusivity(diffusivity)
+    if biharmonic is not None:
+        tr.set_biharmonic(biharmonic)
     if sources is not None:
         sources = list(sources)
         if len(sources) != len(arrays):

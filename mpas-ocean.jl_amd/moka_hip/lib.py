@@ -102,6 +102,7 @@ EXPORTS = [
     "moka_state_rk4_streams",
     "moka_set_tracers", "moka_tracer_upload", "moka_tracer_download", "moka_state_tracer_path",
     "moka_set_tracer_diffusion", "moka_tracer_diffusion",
+    "moka_set_tracer_biharmonic", "moka_tracer_biharmonic",
     "moka_tracer_source_upload", "moka_tracer_source_download", "moka_tracer_has_source",
     "moka_tracer_adjoint_want_source_gradient", "moka_tracer_adjoint_source_download",
     "moka_tracer_tape_create", "moka_tracer_tape_destroy", "moka_step_rk4_tracer_taped", "moka_tracer_tape_steps",
@@ -247,6 +248,8 @@ def lib():
     L.moka_state_tracer_path.argtypes = [vp]
     L.moka_set_tracer_diffusion.argtypes = [vp, vp]
     L.moka_tracer_diffusion.argtypes = [vp, C.c_int32, C.POINTER(C.c_double)]
+    L.moka_set_tracer_biharmonic.argtypes = [vp, vp]
+    L.moka_tracer_biharmonic.argtypes = [vp, C.c_int32, C.POINTER(C.c_double)]
     L.moka_tracer_tape_create.argtypes = [vp, C.c_int64, C.POINTER(vp)]
     L.moka_tracer_tape_destroy.argtypes = [vp]
     L.moka_tracer_tape_destroy.restype = None

@@ -11,6 +11,9 @@ process, alternated round by round, every figure a median of moka_mark intervals
   sources   the same forward step with a source on every tracer (moka_tracer_source_upload), and the same sweep with every tracer's
             source gradient wanted (moka_tracer_adjoint_want_source_gradient): one more own-row stream per tracer and forward launch,
             two more (G in + out) per tracer in the head and in three of the four reverse launches
+  biharmonic  the same forward step and the same sweep with a biharmonic coefficient on every tracer (moka_set_tracer_biharmonic,
+            kappa4 = 0.002 dcEdge_min^4 / dt): one Laplacian launch more ahead of every forward and every reverse stage launch
+            (8 K nC (1 + 2 B) bytes) and one more gathered stream per tracer in the stage launch itself (8 K nC B)
   copy      the copy rate of the same run (moka_bw_probe)
 
 Config 4 (icosahedral m = 320, 1 024 002 cells x 60 levels); --small: config 3 (m = 64).  Prints one JSON line and, with --out FILE,
@@ -62,6 +65,9 @@ taped = {n: [] for n in counts if n}
 rev = {n: [] for n in counts if n}
 fwd_src = {n: [] for n in counts if n}
 rev_g = {n: [] for n in counts if n}
+fwd_b = {n: [] for n in counts if n}
+rev_b = {n: [] for n in counts if n}
+kappa4 = 0.002 * float(mesh.dcEdge.min()) ** 4 / dts
 qsrc = np.random.default_rng(2).uniform(-1.0, 1.0, (mesh.nCells, K)) * (float(h.mean()) / (1000.0 * dts))
 paths = {}
 for _ in range(args.rounds):
@@ -116,6 +122,33 @@ for _ in range(args.rounds):
                     taped[n].append(iv[0])
                     rev[n].append(iv[2])
         paths[n] = (tr.path(), tape.path())
+        for j in range(n):
+            tape.want_source_gradient(j, False)
+        tr.set_biharmonic(kappa4)                                            # the biharmonic legs, in the same round
+        for rep in range(args.warmup + args.steps):
+            b.synchronize()
+            b.marks_reset()
+            b.mark()
+            tape.step(dts)
+            b.mark()
+            for j in range(n):
+                tape.seed(j, None)
+            b.mark()
+            tape.sweep()
+            b.mark()
+            b.synchronize()
+            iv = list(b.marks_read())
+            if rep >= args.warmup:
+                rev_b[n].append(iv[2])
+        b.marks_reset()
+        b.mark()
+        for _ in range(args.steps):
+            L.check(lib.moka_step_rk4(sh, C.c_double(dts)), b._h)
+            b.mark()
+        b.synchronize()
+        fwd_b[n] += list(b.marks_read())
+        paths[(n, "bih")] = (tr.path(), tape.path())
+        tr.set_biharmonic(None)
         tape.close()
 mk.set_tracers(Prog, [])
 bw = b.bw_probe()
@@ -126,7 +159,10 @@ result = {"cells": nC, "edges": nE, "K": K, "rounds": args.rounds, "steps_per_ro
           "taped_ms_per_step": {n: med(v) for n, v in taped.items()}, "sweep_ms_per_step": {n: med(v) for n, v in rev.items()},
           "sweep_ms_min_max": {n: (min(v), max(v)) for n, v in rev.items()},
           "forward_with_sources_ms_per_step": {n: med(v) for n, v in fwd_src.items()},
-          "sweep_with_source_gradients_ms_per_step": {n: med(v) for n, v in rev_g.items()}}
+          "sweep_with_source_gradients_ms_per_step": {n: med(v) for n, v in rev_g.items()},
+          "forward_with_biharmonic_ms_per_step": {n: med(v) for n, v in fwd_b.items()},
+          "sweep_with_biharmonic_ms_per_step": {n: med(v) for n, v in rev_b.items()}}
+result["paths_forward_reverse"] = {str(k): v for k, v in paths.items()}
 rows = []
 for n in counts:
     if not n:
@@ -158,4 +194,12 @@ if args.out:
                 f0, f1 = result["forward_ms_per_step"][n], result["forward_with_sources_ms_per_step"][n]
                 r0, r1 = result["sweep_ms_per_step"][n], result["sweep_with_source_gradients_ms_per_step"][n]
                 fh.write(f"   {n:<9d} {f0:<9.3f} {f1:<35.3f} {(f1 - f0) / 4:<+12.3f} {r0:<9.3f} {r1:<27.3f} {(r1 - r0) / 4:+.3f}\n")
+        fh.write("\n   a biharmonic coefficient on every tracer (no harmonic one), same run, medians; model = 8 K nC (1 + 3 B) bytes per stage at the copy rate\n"
+                 "   tracers   forward step ms (without, with)   per stage   sweep ms (without, with)   per reverse stage   model per stage\n")
+        for n in counts:
+            if n:
+                f0, f1 = result["forward_ms_per_step"][n], result["forward_with_biharmonic_ms_per_step"][n]
+                r0, r1 = result["sweep_ms_per_step"][n], result["sweep_with_biharmonic_ms_per_step"][n]
+                model = 8 * K * nC * (1 + 3 * n) / (result["copy_GBs"] * 1e9) * 1e3
+                fh.write(f"   {n:<9d} {f0:<9.3f} {f1:<23.3f} {(f1 - f0) / 4:<+11.3f} {r0:<9.3f} {r1:<16.3f} {(r1 - r0) / 4:<+19.3f} {model:+.3f}\n")
 Prog._state.close(); Setup.mesh.close()

@@ -7,7 +7,10 @@ alone is the difference to the same run's tracer-free step, over the four launch
 instantiations of a state that never set a diffusivity, so they are the baseline of the diffusion-on legs.  Shader clock and package
 power are sampled from sysfs while the 3-tracer steps run back to back, diffusion off and on (bench.py's under_load).  A third set of
 legs gives every tracer a source (moka_tracer_source_upload; the SRC instantiations, one more own-row stream of 8 K nC bytes per sourced
-tracer and launch), diffusion off, and with three tracers also on; they alternate with the other legs in the same rounds.  Config 4 (icosahedral
+tracer and launch), diffusion off, and with three tracers also on; they alternate with the other legs in the same rounds.  A fourth set
+gives every tracer a biharmonic coefficient (moka_set_tracer_biharmonic, kappa4 = 0.002 dcEdge_min^4 / dt; the Laplacian launch and the BIH
+instantiations), diffusion off and on; byte model per stage with B such tracers: 8 K nC (1 + 2 B) for the Laplacian launch, 8 K nC B more in
+the tracer launch.  Config 4 (icosahedral
 m = 320, 1 024 002 cells x 60 levels); --small: config 3 (m = 64).  Prints one JSON line and, with --out FILE, writes the summary
 table there.
 
@@ -55,8 +58,10 @@ kappa = 0.02 * float(mesh.dcEdge.min()) ** 2 / dts
 settings = [(0, False, False)] + [(n, d, False) for n in counts if n for d in (False, True)]
 settings += [(n, False, True) for n in counts if n] + [(3, True, True)]
 key = lambda n, d, s=False: f"{n}{'+diff' if d else ''}{'+src' if s else ''}"      # noqa: E731
+kappa4 = 0.002 * float(mesh.dcEdge.min()) ** 4 / dts
+bsettings = [(n, d) for n in counts if n for d in (False, True)]
 qsrc = rng.uniform(-1.0, 1.0, (mesh.nCells, K)) * (float(h.mean()) / (1000.0 * dts))
-result = {"cells": mesh.nCells, "edges": mesh.nEdges, "K": K, "rounds": args.rounds, "steps_per_round": args.steps, "kappa": kappa,
+result = {"cells": mesh.nCells, "edges": mesh.nEdges, "K": K, "rounds": args.rounds, "steps_per_round": args.steps, "kappa": kappa, "kappa4": kappa4,
           "forms": {}}
 for variant, form in ((0, "patch"), (3, "generic")):
     b.set_kernel_variant(variant)
@@ -65,6 +70,8 @@ for variant, form in ((0, "patch"), (3, "generic")):
     steps = {n: [] for n in counts}
     dsteps = {key(n, d): [] for n, d, s in settings if not s}
     ssteps = {key(n, d, True): [] for n, d, s in settings if s}
+    bsteps = {key(n, d) + "+bih": [] for n, d in bsettings}
+    bpath = 0
     path = 0
     for _ in range(args.rounds):
         for n, diff, src in settings:
@@ -86,10 +93,25 @@ for variant, form in ((0, "patch"), (3, "generic")):
                 steps[n] = dsteps[key(n, False)]
             if n:
                 path = tr.path()
+        for n, diff in bsettings:                                            # the biharmonic legs, in the same round
+            tr = mk.set_tracers(Prog, [phi] * n, diffusivity=kappa if diff else None, biharmonic=kappa4)
+            for _ in range(args.warmup):
+                L.check(lib.moka_step_rk4(sh, C.c_double(dts)), b._h)
+            b.synchronize()
+            b.marks_reset()
+            b.mark()
+            for _ in range(args.steps):
+                L.check(lib.moka_step_rk4(sh, C.c_double(dts)), b._h)
+                b.mark()
+            b.synchronize()
+            bsteps[key(n, diff) + "+bih"] += list(b.marks_read())
+            bpath = tr.path()
     load = {}
     for diff in (False, True):                                               # clock and power while the 3-tracer steps run
         mk.set_tracers(Prog, [phi] * 3, diffusivity=kappa if diff else None)
         load[key(3, diff)] = bench.under_load(b, lambda: L.check(lib.moka_step_rk4(sh, C.c_double(dts)), b._h), seconds=1.5, batch=5)
+    mk.set_tracers(Prog, [phi] * 3, diffusivity=kappa, biharmonic=kappa4)
+    load["3+diff+bih"] = bench.under_load(b, lambda: L.check(lib.moka_step_rk4(sh, C.c_double(dts)), b._h), seconds=1.5, batch=5)
     mk.set_tracers(Prog, [])
     med = {n: statistics.median(v) for n, v in steps.items()}
     contract = {n: 8 * K * (4 * mesh.nEdges + 10 * mesh.nCells + 16 * n * mesh.nCells) for n in counts if n}
@@ -106,6 +128,11 @@ for variant, form in ((0, "patch"), (3, "generic")):
         "sources": {k: {"median": statistics.median(v), "min": min(v), "max": max(v), "p25": statistics.quantiles(v, n=4)[0],
                         "p75": statistics.quantiles(v, n=4)[2],
                         "launch_delta_ms": (statistics.median(v) - statistics.median(dsteps[k[:-4]])) / 4} for k, v in ssteps.items()},
+        "biharmonic": {k: {"median": statistics.median(v), "min": min(v), "max": max(v), "p25": statistics.quantiles(v, n=4)[0],
+                           "p75": statistics.quantiles(v, n=4)[2],
+                           "stage_delta_ms": (statistics.median(v) - statistics.median(dsteps[k[:-4]])) / 4} for k, v in bsteps.items()},
+        "biharmonic_tracer_path": bpath,
+        "biharmonic_model_stage_delta_ms": {n: 8 * K * mesh.nCells * (1 + 3 * n) / 1e9 for n in counts if n},   # ms at 1 TB/s; scaled below
         "under_load": load}
     Prog._state.close(); Setup.mesh.close()
 b.set_kernel_variant(0)
@@ -113,6 +140,7 @@ bw = b.bw_probe()
 result["copy_GBs"] = bw.get("copy_GBs")
 for f in result["forms"].values():
     f["contract_fraction_of_copy_rate"] = {n: f["contract_TBps"][n] * 1e3 / result["copy_GBs"] for n in f["contract_TBps"]}
+    f["biharmonic_model_stage_delta_ms"] = {n: v * 1e3 / result["copy_GBs"] for n, v in f["biharmonic_model_stage_delta_ms"].items()}
 print(json.dumps(result), flush=True)
 if args.out:
     with open(args.out, "w") as fh:
@@ -144,6 +172,13 @@ if args.out:
             for k, d in f["sources"].items():
                 fh.write(f"   {k:<11s} {d['median']:<9.3f} {d['min']:<9.3f} {d['p25']:<9.3f} {d['p75']:<9.3f} {d['max']:<9.3f} "
                          f"{d['launch_delta_ms']:+.3f}\n")
+            fh.write(f"\n   a biharmonic coefficient on every tracer (moka_set_tracer_biharmonic, kappa4 = 0.002 dcEdge_min^4 / dt; tracer path "
+                     f"{f['biharmonic_tracer_path']}), ms / RK4 step;\n   the leg without '+bih' is the row above.  Per stage = the Laplacian launch "
+                     "+ what the tracer launch gains; model = 8 K nC (1 + 3 B) bytes at the copy rate\n"
+                     "   setting       median    min       p25       p75       max       with - without per stage   model\n")
+            for k, d in f["biharmonic"].items():
+                fh.write(f"   {k:<13s} {d['median']:<9.3f} {d['min']:<9.3f} {d['p25']:<9.3f} {d['p75']:<9.3f} {d['max']:<9.3f} "
+                         f"{d['stage_delta_ms']:<+26.3f} {f['biharmonic_model_stage_delta_ms'][int(k.split('+')[0])]:+.3f}\n")
             for k, u in f["under_load"].items():
                 fh.write(f"   under load, {k}: sclk {u['sclk_mhz_mean']} MHz (min {u['sclk_mhz_min']}), power {u['power_w_mean']} W "
                          f"(max {u['power_w_max']}), {u['ms_per_call_sustained']:.3f} ms / step sustained\n")
