@@ -576,8 +576,8 @@ int  moka_state_del4_path(const moka_state *st);
  * (moka_state_rk4_streams: 16).  moka_state_optimize_placement neither times nor moves the tracer arrays.
  * Out of scope: upwind, FCT and higher-order edge values, a spatially varying kappa or kappa4 or a mesh scaling per edge, anisotropic
  * mixing, Forward Euler,
- * fp32 storage, partitioned meshes, reverse mode with respect to the flow, kappa or kappa4 (with respect to the tracers themselves
- * and to the sources: moka_tracer_tape_* below), time-dependent sources, point-source convenience calls, the 13-stream form, YAML keys and NetCDF I/O of tracers, and fusing the tracer sum into the dycore's stage
+ * fp32 storage, partitioned meshes, reverse mode with respect to the flow (with respect to the tracers themselves, to the sources and
+ * to kappa_j and kappa4_j: moka_tracer_tape_* below), time-dependent sources, point-source convenience calls, the 13-stream form, YAML keys and NetCDF I/O of tracers, and fusing the tracer sum into the dycore's stage
  * kernels. */
 int  moka_set_tracers(moka_state *st, int32_t nTracers);
 /* tracer j (0-based) at time_level 0 (previous) / 1 (current): (nVertLevels, nCells) doubles in the caller's cell numbering, like
@@ -659,8 +659,36 @@ int  moka_tracer_has_source(const moka_state *st, int32_t j, int *out);
  * phi (the tape records nothing new), so two runs that differ only in q give the same G and the same X bit for bit; asking for G
  * changes no bit of X; a zero seed gives G == 0 exactly; and the map is affine in q, so
  *   <X, phi_N(phi_0, q) - phi_N(phi_0, 0)> = <G, q>   up to round-off.
+ * Gradient with respect to the mixing coefficients (moka_tracer_adjoint_want_diffusivity_gradient).  The step is linear in phi and
+ * affine in (kappa_j, kappa4_j): stage s of tracer j forms T = A(P_s) pphi_s + kappa_j * D_s - kappa4_j * B_s (+ q) with
+ *   D_s[k,c] = sum over the slots of ((hE * (pphi_s[k,c'] - pphi_s[k,c])) * dvdc[c,i]) * invArea[c]
+ * and B_s the same sum with L_s = Lap(ph_s, pphi_s) in the place of pphi_s.  tau_s above is the adjoint of T, hence
+ *   d J / d kappa_j  =   sum over the recorded steps, s = 0..3 and (k, c) of tau_s[k,c] * D_s[k,c]
+ *   d J / d kappa4_j = - sum over the recorded steps, s = 0..3 and (k, c) of tau_s[k,c] * B_s[k,c]
+ * Two identities make both a dot product of fields the sweep holds: D_s = ph_s * L_s, and, Lap being self-adjoint under the weight
+ * areaCell[c] * ph_s[k,c], sum tau_s B_s = sum over (k, c) of areaCell[c] ph_s[k,c] L_s[k,c] M[k,c] with M = Lap(ph_s, y), y = tau_s * invA.
+ * A flagged tracer's pphi_0..pphi_3 (pphi_0 = phi_cur) are recorded beside P_s by copies behind the stage launches: 4 * nVertLevels *
+ * nCells doubles more per flagged tracer and step.  In the sweep, ahead of each reverse stage rs = 3, 2, 1, 0 (when y holds tau_rs * invA),
+ * for the flagged tracers only: L = Lap(ph_rs, pphi_rs) by the Laplacian pass above, M = Lap(ph_rs, y) also for a tracer whose d J / d
+ * kappa4 is wanted while its recorded kappa4 is zero (a derivative at zero is legitimate; the reverse stages never read that M), and
+ * per element, one rounding per operation, no contraction:
+ *   p = ph_rs[k,c] * L[k,c];     dk = p * y[k,c];     dk4 = p * M[k,c]
+ * colsum(d)[c], the sum over the column: with LPC the smallest power of two >= nVertLevels, at most 64, partial l = 0..LPC-1 starts
+ * at 0.0 and adds d[k,c] for k = l, l + LPC, l + 2 LPC, ... in ascending order; then for o = LPC/2, LPC/4, ..., 1 every partial l
+ * becomes partial[l] + partial[l xor o] (all at once); colsum = partial[0].  The order depends on nVertLevels alone.
+ * Two sensitivity densities per flagged tracer, nCells doubles each, take one addition per reverse stage, each with its own rounding:
+ *   Wk_j[c]  = Wk_j[c]  + areaCell[c] * colsum(dk)[c]
+ *   Wk4_j[c] = Wk4_j[c] - areaCell[c] * colsum(dk4)[c]
+ * They accumulate over the four stages and over every recorded step, as G does, and are zeroed where G is: at the first seed after a
+ * recorded step.  d J / d kappa_j = sum over c of Wk_j[c] and d J / d kappa4_j = sum over c of Wk4_j[c], taken on the host over the
+ * caller's cell numbering, ascending, in long double and rounded once: independent of the mesh's cell ordering.  The density shows
+ * where J feels the mixing.  The derivative is with respect to a coefficient that acts identically in every recorded step (the values
+ * the steps ran with may differ from step to step), the flow held as it ran.  Hence: asking for these changes no bit of X, of G, of the
+ * state or of the tracers (the new launches read ph, y and M and write arrays of their own); the tracer that is 1 everywhere stays exactly 1.0, so its L == 0
+ * and both its gradients are exactly 0.0; a zero seed gives densities that are exactly zero; an unflagged tracer is neither recorded, read nor written.
  * Usage: tracer_tape_create -> n x step_rk4_tracer_taped -> seed (per tracer) -> sweep -> download (per tracer).
- * Out of scope: sensitivities of the tracers to the flow (d phi_N / d (u, h)), to kappa and to kappa4, time-dependent sources and a per-step
+ * Out of scope: sensitivities of the tracers to the flow (d phi_N / d (u, h)), a spatially varying or time-dependent kappa and a
+ * per-step split of its gradient, second derivatives, time-dependent sources and a per-step
  * split of G, coupling to moka_tape, Forward Euler, partitioned meshes, fp32 storage. */
 typedef struct moka_tracer_tape moka_tracer_tape;
 /* MOKA_ERR_UNSUPPORTED on a state without tracers, MOKA_ERR_ARG for NULL arguments or a negative capacity.  The tape remembers the
@@ -689,6 +717,20 @@ int  moka_tracer_adjoint_path(const moka_tracer_tape *t);
 int  moka_tracer_adjoint_want_source_gradient(moka_tracer_tape *t, int32_t j, int on);
 /* G_j as it stands, in the caller's cell numbering; MOKA_ERR_ARG for j out of range, a NULL host, or a tracer that was never flagged */
 int  moka_tracer_adjoint_source_download(moka_tracer_tape *t, int32_t j, double *host);
+/* Gradient with respect to kappa_j and kappa4_j (algebra above).  what: a nonempty set of the two bits; on != 0 adds them to tracer
+ * j's set, 0 removes them.  Only while the tape holds no recorded step and is not between a seed and its sweep: MOKA_ERR_ARG there, for
+ * j out of range and for an empty or unknown `what`.  moka_tracer_tape_create sizes nothing for this: a call that changes the set of
+ * flagged tracers allocates the record of their provisional tracers (capacity * 4 * nVertLevels * nCells doubles each), one scratch
+ * field and two densities per flagged tracer -- MOKA_ERR_ALLOC, with nothing changed, when that fails -- and drops what earlier
+ * sweeps accumulated.  While any tracer is flagged moka_step_rk4_tracer_taped records more (state and tracers keep their bits) and the
+ * sweep has up to three more launches per reverse stage; a tape without a flag records, allocates and launches what it always did. */
+enum { MOKA_TRACER_GRAD_KAPPA = 1, MOKA_TRACER_GRAD_KAPPA4 = 2 };
+int  moka_tracer_adjoint_want_diffusivity_gradient(moka_tracer_tape *t, int32_t j, int what, int on);
+/* what: exactly one bit.  *out = d J / d kappa_j (d J / d kappa4_j) as the densities stand; host: the density itself, nCells doubles in
+ * the caller's cell numbering.  MOKA_ERR_ARG for j out of range, NULL arguments, a `what` that is not one bit, and a tracer or bit
+ * that is not flagged. */
+int  moka_tracer_adjoint_diffusivity_gradient(moka_tracer_tape *t, int32_t j, int what, double *out);
+int  moka_tracer_adjoint_diffusivity_density_download(moka_tracer_tape *t, int32_t j, int what, double *host);
 
 /* ---- reverse mode of the Forward-Euler loop ----------------------------------------------------------------
  * The reference gets d sum(ssh^2) / d (initial normalVelocity, layerThickness) from Enzyme over ocn_run_loop

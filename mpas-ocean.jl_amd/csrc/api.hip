@@ -1470,6 +1470,18 @@ struct moka_tracer_tape {
     std::vector<double *> G;
     std::vector<char> wantG;
     double **Gdev = nullptr;
+    // gradient with respect to kappa_j and kappa4_j (moka_tracer_adjoint_want_diffusivity_gradient): the bit set of every tracer and the
+    // nF flagged ones in ascending order.  All of the following is allocated by a flag, never by moka_tracer_tape_create, and replaced
+    // as a whole when the set of flagged tracers changes (only an empty tape may change it).
+    std::vector<int> wantK;                          // nT bit sets of MOKA_TRACER_GRAD_*
+    std::vector<int32_t> kgTracer;                   // nF
+    double *kgP = nullptr;                           // capacity x 4 x nF x (K, nC): pphi_s of the flagged tracers
+    double *kgL = nullptr;                           // nF x (K, nC): Lap(ph_rs, pphi_rs) of a reverse stage
+    double *kgW = nullptr;                           // 2 nF x nC: the densities Wk_f, Wk4_f (both rows exist; a row not wanted stays zero)
+    double *kgOnes = nullptr;                        // nF ones: launch_tracer_lap's filter for the pass over the flagged tracers
+    double *kgMOn = nullptr;                         // capacity x nT: the filter of the sweep's M pass (recorded kappa4, or 1 where M is wanted)
+    int32_t *kgTracerDev = nullptr;                  // nF
+    double **kgWdev = nullptr;                       // 2 nF
     bool seeded = false;
     bool pending = false;                            // seeded and not yet swept
     int path = 0;                                    // moka_tracer_adjoint_path
@@ -1509,6 +1521,12 @@ static int step_rk4(moka_state *st, double dt, moka_tracer_tape *rec)
             HIPCHK(c, hipMemcpyAsync(rec->pu + nEK * (4 * rec->n + s - 1), g.pu, nEK * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
             HIPCHK(c, hipMemcpyAsync(rec->ph + nCK * (4 * rec->n + s - 1), g.ph, nCK * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
             if (s == 4) HIPCHK(c, hipMemcpyAsync(rec->hn + nCK * rec->n, g.nh_out, nCK * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+            // pphi_{s-1} of the tracers flagged for a diffusivity gradient: what tracer_stage handed the stage's launches
+            const double *pphi = s == 1 ? st->trPhi[1] : st->trProv[s == 3 ? 1 : 0];
+            const size_t nF = rec->kgTracer.size();
+            for (size_t f = 0; f < nF; ++f)
+                HIPCHK(c, hipMemcpyAsync(rec->kgP + nCK * ((4 * rec->n + s - 1) * nF + f), pphi + nCK * rec->kgTracer[f], nCK * sizeof(double),
+                                         hipMemcpyDeviceToDevice, c->stream));
         }
     }
     if (timed) HIPCHK(c, stamp());
@@ -2022,6 +2040,7 @@ int moka_tracer_tape_create(moka_state *st, int64_t capacity_steps, moka_tracer_
     t->nT = st->nTracers;
     t->G.assign((size_t)t->nT, nullptr);
     t->wantG.assign((size_t)t->nT, 0);
+    t->wantK.assign((size_t)t->nT, 0);
     t->capacity = capacity_steps;
     const size_t nEK = (size_t)p.K * p.nE, nCK = (size_t)p.K * p.nC, cap = (size_t)capacity_steps;
     int rc = MOKA_OK;
@@ -2104,6 +2123,7 @@ int moka_tracer_adjoint_seed(moka_tracer_tape *t, int32_t j, const double *host)
         HIPCHK(t->ctx, hipMemsetAsync(t->X, 0, nCK * t->nT * sizeof(double), t->ctx->stream));
         for (double *G : t->G)
             if (G) HIPCHK(t->ctx, hipMemsetAsync(G, 0, nCK * sizeof(double), t->ctx->stream));
+        if (t->kgW) HIPCHK(t->ctx, hipMemsetAsync(t->kgW, 0, 2 * t->kgTracer.size() * (size_t)p.nC * sizeof(double), t->ctx->stream));
     }
     t->seeded = true;
     t->pending = true;
@@ -2127,8 +2147,19 @@ int moka_tracer_adjoint_sweep(moka_tracer_tape *t)
     for (double k : t->kappa4) bih = bih || k != 0.0;
     for (double k : t->kappa) diff = diff || k != 0.0;
     diff = diff || bih;                 // the BIH kernels exist only together with DIFF (a step without diffusivities recorded zeros)
-    if (diff && !mm->dvdc)
+    const int nF = (int)t->kgTracer.size();         // tracers flagged for d J / d kappa, d J / d kappa4: their passes need dvdc as well
+    if ((diff || nF > 0) && !mm->dvdc)
         if (int rc = upload_vec(mm, mm->plan.dvdc, &mm->dvdc)) return rc;
+    // M of a tracer whose d J / d kappa4 is wanted and whose recorded kappa4 is zero: the sweep's own pass skips it, so the pass takes a
+    // filter in which such a tracer counts -- its M lands in its own slot of t->M, which no reverse kernel reads for kappa4_j == 0
+    bool kgM = false;
+    for (int w : t->wantK) kgM = kgM || (w & MOKA_TRACER_GRAD_KAPPA4) != 0;
+    if (kgM && t->n > 0) {
+        std::vector<double> on(t->kappa4.begin(), t->kappa4.begin() + (size_t)t->n * t->nT);
+        for (size_t i = 0; i < on.size(); ++i)
+            if (on[i] == 0.0 && (t->wantK[i % t->nT] & MOKA_TRACER_GRAD_KAPPA4)) on[i] = 1.0;
+        if (int rc = h2d(t->ctx, t->kgMOn, on.data(), on.size() * sizeof(double))) return rc;
+    }
     const MeshDev dev = launch_bounds(mm);
     const bool generic = t->ctx->variant == 3;
     const size_t nEK = (size_t)p.K * p.nE, nCK = (size_t)p.K * p.nC;
@@ -2153,10 +2184,21 @@ int moka_tracer_adjoint_sweep(moka_tracer_tape *t)
             q.G = rs > 0 ? G : nullptr;         // reverse stage 0 does not touch G
             q.kappa4 = bih ? t->kap4 + (size_t)n * t->nT : nullptr;
             q.lapy = bih ? t->M : nullptr;
-            if (bih && std::any_of(t->kappa4.begin() + n * t->nT, t->kappa4.begin() + (n + 1) * t->nT, [](double k) { return k != 0.0; })) {
-                TracerLapArgs w{};          // M = Lap(ph_s, y) of the tracers whose recorded kappa4 is not zero
-                w.nT = q.nT; w.stride = q.stride; w.ph = q.ph; w.x = q.y; w.kappa4 = q.kappa4; w.dvdc = q.dvdc; w.out = t->M;
+            if (kgM || (bih && std::any_of(t->kappa4.begin() + n * t->nT, t->kappa4.begin() + (n + 1) * t->nT, [](double k) { return k != 0.0; }))) {
+                TracerLapArgs w{};          // M = Lap(ph_s, y) of the tracers whose recorded kappa4 is not zero (kgM: or whose d J / d kappa4 is wanted)
+                w.nT = q.nT; w.stride = q.stride; w.ph = q.ph; w.x = q.y; w.kappa4 = kgM ? t->kgMOn + (size_t)n * t->nT : q.kappa4;
+                w.dvdc = mm->dvdc; w.out = t->M;
                 HIPCHK(t->ctx, launch_tracer_lap(dev, w, mm->lpc, generic, s));
+            }
+            if (nF > 0) {                   // L = Lap(ph_rs, pphi_rs) of the flagged tracers, then the products against y and M
+                TracerLapArgs w{};
+                w.nT = nF; w.stride = q.stride; w.ph = q.ph; w.x = t->kgP + nCK * ((size_t)(4 * n + rs) * nF); w.kappa4 = t->kgOnes;
+                w.dvdc = mm->dvdc; w.out = t->kgL;
+                HIPCHK(t->ctx, launch_tracer_lap(dev, w, mm->lpc, generic, s));
+                TracerKgradArgs kg{};
+                kg.nF = nF; kg.stride = q.stride; kg.ph = q.ph; kg.L = t->kgL; kg.y = q.y; kg.M = t->M;
+                kg.tracer = t->kgTracerDev; kg.W = t->kgWdev;
+                HIPCHK(t->ctx, launch_tracer_kgrad(dev, kg, mm->lpc, s));
             }
             t->path = tracer_adjoint_kernel(dev, mm->lpc, q.nT, generic, diff, bih).form;
             HIPCHK(t->ctx, launch_tracer_adjoint(dev, q, mm->lpc, generic, s));
@@ -2209,6 +2251,111 @@ int moka_tracer_adjoint_source_download(moka_tracer_tape *t, int32_t j, double *
 }
 
 int moka_tracer_adjoint_path(const moka_tracer_tape *t) { return t ? t->path : 0; }
+
+// ---- d J / d kappa_j, d J / d kappa4_j (include/moka_hip.h: the algebra; k_tracer_kgrad) ----
+static void ttape_free(moka_tracer_tape *t, void *q)
+{
+    if (!q) return;
+    t->allocs.erase(std::remove(t->allocs.begin(), t->allocs.end(), q), t->allocs.end());
+    (void)hipFree(q);
+}
+
+int moka_tracer_adjoint_want_diffusivity_gradient(moka_tracer_tape *t, int32_t j, int what, int on)
+{
+    if (!t) return fail(nullptr, MOKA_ERR_ARG, "tracer tape is NULL");
+    if (j < 0 || j >= t->nT) return fail(t->ctx, MOKA_ERR_ARG, "tracer index out of range (moka_tracer_tape_create)");
+    if (what == 0 || (what & ~(MOKA_TRACER_GRAD_KAPPA | MOKA_TRACER_GRAD_KAPPA4)))
+        return fail(t->ctx, MOKA_ERR_ARG, "tracer tape: what must be a nonempty set of MOKA_TRACER_GRAD_KAPPA | MOKA_TRACER_GRAD_KAPPA4");
+    if (t->n > 0) return fail(t->ctx, MOKA_ERR_ARG, "tracer tape: the diffusivity gradients may be chosen only while the tape holds no recorded step");
+    if (t->pending) return fail(t->ctx, MOKA_ERR_ARG, "tracer tape: not between a seed and its sweep");
+    HIPCHK(t->ctx, hipSetDevice(t->ctx->device));
+    const Plan &p = t->st->mesh->plan;
+    std::vector<int> want = t->wantK;
+    want[j] = on ? (want[j] | what) : (want[j] & ~what);
+    std::vector<int32_t> tr;
+    for (int i = 0; i < t->nT; ++i)
+        if (want[i]) tr.push_back(i);
+    const size_t nF = tr.size(), nCK = (size_t)p.K * p.nC, cap = (size_t)t->capacity;
+    HIPCHK(t->ctx, hipStreamSynchronize(t->ctx->stream));        // no launch is reading what goes
+    if (nF > 0 && tr == t->kgTracer) {          // the same tracers, other bits: the arrays stay; the table of wanted densities changes
+        std::vector<double *> tab(2 * nF, nullptr);
+        for (size_t f = 0; f < nF; ++f) {
+            if (want[tr[f]] & MOKA_TRACER_GRAD_KAPPA) tab[2 * f] = t->kgW + (2 * f) * (size_t)p.nC;
+            if (want[tr[f]] & MOKA_TRACER_GRAD_KAPPA4) tab[2 * f + 1] = t->kgW + (2 * f + 1) * (size_t)p.nC;
+        }
+        HIPCHK(t->ctx, hipMemsetAsync(t->kgW, 0, 2 * nF * (size_t)p.nC * sizeof(double), t->ctx->stream));
+        if (int rc = h2d(t->ctx, t->kgWdev, tab.data(), tab.size() * sizeof(double *))) return rc;
+        t->wantK = want;
+        return MOKA_OK;
+    }
+    // the new arrays first (each zeroed): a failure leaves the tape as it was
+    double *P = nullptr, *Lk = nullptr, *W = nullptr, *ones = nullptr, *mOn = nullptr, *trDev = nullptr, *wDev = nullptr;
+    int rc = MOKA_OK;
+    if (nF > 0) {
+        auto A = [&](double **q, size_t n) { if (rc == MOKA_OK) rc = ttape_alloc(t, q, n); };
+        A(&P, nCK * 4 * nF * cap); A(&Lk, nCK * nF); A(&W, 2 * nF * (size_t)p.nC); A(&ones, nF); A(&mOn, cap * t->nT);
+        A(&trDev, (nF * sizeof(int32_t) + sizeof(double) - 1) / sizeof(double)); A(&wDev, 2 * nF * sizeof(double *) / sizeof(double));
+        if (rc == MOKA_OK) {
+            std::vector<double> one(nF, 1.0);
+            std::vector<double *> tab(2 * nF, nullptr);
+            for (size_t f = 0; f < nF; ++f) {
+                if (want[tr[f]] & MOKA_TRACER_GRAD_KAPPA) tab[2 * f] = W + (2 * f) * (size_t)p.nC;
+                if (want[tr[f]] & MOKA_TRACER_GRAD_KAPPA4) tab[2 * f + 1] = W + (2 * f + 1) * (size_t)p.nC;
+            }
+            rc = h2d(t->ctx, ones, one.data(), nF * sizeof(double));
+            if (rc == MOKA_OK) rc = h2d(t->ctx, trDev, tr.data(), nF * sizeof(int32_t));
+            if (rc == MOKA_OK) rc = h2d(t->ctx, wDev, tab.data(), tab.size() * sizeof(double *));
+        }
+        if (rc != MOKA_OK) {
+            (void)hipStreamSynchronize(t->ctx->stream);
+            for (double *q : {P, Lk, W, ones, mOn, trDev, wDev}) ttape_free(t, q);
+            return rc;
+        }
+    }
+    for (void *q : {(void *)t->kgP, (void *)t->kgL, (void *)t->kgW, (void *)t->kgOnes, (void *)t->kgMOn, (void *)t->kgTracerDev, (void *)t->kgWdev})
+        ttape_free(t, q);
+    t->kgP = P; t->kgL = Lk; t->kgW = W; t->kgOnes = ones; t->kgMOn = mOn;
+    t->kgTracerDev = reinterpret_cast<int32_t *>(trDev); t->kgWdev = reinterpret_cast<double **>(wDev);
+    t->wantK = want;
+    t->kgTracer = tr;
+    return MOKA_OK;
+}
+
+// the row of kgW that holds the density `what` of tracer j, or an error
+static int kgrad_row(moka_tracer_tape *t, int32_t j, int what, const void *out, const double **row)
+{
+    if (!t) return fail(nullptr, MOKA_ERR_ARG, "tracer tape is NULL");
+    if (j < 0 || j >= t->nT) return fail(t->ctx, MOKA_ERR_ARG, "tracer index out of range (moka_tracer_tape_create)");
+    if (!out) return fail(t->ctx, MOKA_ERR_ARG, "NULL argument");
+    if (what != MOKA_TRACER_GRAD_KAPPA && what != MOKA_TRACER_GRAD_KAPPA4)
+        return fail(t->ctx, MOKA_ERR_ARG, "tracer tape: what must be exactly one of MOKA_TRACER_GRAD_KAPPA, MOKA_TRACER_GRAD_KAPPA4");
+    if (!(t->wantK[j] & what))
+        return fail(t->ctx, MOKA_ERR_ARG, "tracer tape: this gradient was not asked for (moka_tracer_adjoint_want_diffusivity_gradient)");
+    const size_t f = std::lower_bound(t->kgTracer.begin(), t->kgTracer.end(), j) - t->kgTracer.begin();
+    *row = t->kgW + (2 * f + (what == MOKA_TRACER_GRAD_KAPPA4 ? 1 : 0)) * (size_t)t->st->mesh->plan.nC;
+    return MOKA_OK;
+}
+
+int moka_tracer_adjoint_diffusivity_density_download(moka_tracer_tape *t, int32_t j, int what, double *host)
+{
+    const double *row = nullptr;
+    if (int rc = kgrad_row(t, j, what, host, &row)) return rc;
+    HIPCHK(t->ctx, hipSetDevice(t->ctx->device));
+    return get_rows(t->st->mesh, host, row, MOKA_CELL, t->st->mesh->plan.nC, 1);
+}
+
+int moka_tracer_adjoint_diffusivity_gradient(moka_tracer_tape *t, int32_t j, int what, double *out)
+{
+    const double *row = nullptr;
+    if (int rc = kgrad_row(t, j, what, out, &row)) return rc;
+    HIPCHK(t->ctx, hipSetDevice(t->ctx->device));
+    std::vector<double> w((size_t)t->st->mesh->plan.nC);
+    if (int rc = get_rows(t->st->mesh, w.data(), row, MOKA_CELL, (int64_t)w.size(), 1)) return rc;
+    long double sum = 0.0L;            // the caller's cell numbering, ascending, one rounding at the end: independent of the plan's order
+    for (double v : w) sum += (long double)v;
+    *out = (double)sum;
+    return MOKA_OK;
+}
 
 // ---------------------------------------------------------------------------------------------
 // reverse mode of the Forward-Euler loop.  The reference differentiates

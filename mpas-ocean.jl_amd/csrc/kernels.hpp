@@ -273,6 +273,25 @@ hipError_t launch_tracer_adjoint(const MeshDev &m, const TracerAdjArgs &a, int l
 hipError_t launch_tracer_adj_seed(const MeshDev &m, const double *X, const double *hn, double *g, double *y, double b4, int nT,
                                   double *const *G, hipStream_t s);
 
+// ---- gradient of a tracer objective with respect to kappa_j and kappa4_j (moka_tracer_adjoint_want_diffusivity_gradient) ----
+// One launch ahead of a reverse stage, over the nF flagged tracers only.  With L_f = Lap(ph_rs, pphi_rs) of flagged tracer f (nF fields
+// `stride` apart, launch_tracer_lap on the same stream), y = tau_rs * invArea and M = Lap(ph_rs, y) of the sweep (nT fields `stride`
+// apart, indexed by the tracer tracer[f]), per element (k, c):
+//   p = ph[k,c] * L_f[k,c];   dk = p * y[k,c];   dk4 = p * M[k,c]
+// colsum: lane l of the LPC = lanes_per_column(K) lanes of a cell adds its levels k = l, l + LPC, ... in ascending order onto 0.0, then
+// the XOR butterfly of group_sum (offsets LPC/2, ..., 1) adds the lanes; lane 0 holds the sum.  Then, one read and one write per cell:
+//   Wk_f[c] = Wk_f[c] + areaCell[c] * colsum(dk);      Wk4_f[c] = Wk4_f[c] - areaCell[c] * colsum(dk4)
+// W holds 2 nF device pointers: W[2f] = Wk_f, W[2f+1] = Wk4_f, each nC doubles or nullptr where that derivative is not wanted (then
+// its factor -- y, or M -- is not read).  Reads ph, L, y, M; writes W only.
+struct TracerKgradArgs {
+    int nF;
+    int64_t stride;               // K * nC
+    const double *ph, *L, *y, *M;
+    const int32_t *tracer;        // nF: the tracer index of flagged tracer f
+    double *const *W;
+};
+hipError_t launch_tracer_kgrad(const MeshDev &m, const TracerKgradArgs &a, int lpc, hipStream_t s);
+
 // ---- reverse mode of one Forward-Euler step: gather form, the oracle's summation order ----
 struct AdjMesh {
     int32_t nC, nE, K, ME, W;          // W = width of the transposed Coriolis lists

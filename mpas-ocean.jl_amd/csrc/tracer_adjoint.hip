@@ -381,4 +381,80 @@ hipError_t launch_tracer_adjoint(const MeshDev &m, const TracerAdjArgs &a, int l
 #undef PICK
 }
 
+// ------------------------------------------------------------------------------------------------
+// d J / d kappa_j and d J / d kappa4_j (TracerKgradArgs, kernels.hpp: the algebra and the summation order).  An elementwise stream with a
+// column sum: no gather, so one form serves every K and every cell order -- k_tracer_adj_cell's lanes per cell, the strided loop for
+// K > 64.  ph of a lane's first level is read once and kept across the groups of TRA_TJ flagged tracers (for K <= 64 that is every
+// element); p = ph * L is formed once and serves both products.  No atomics, no LDS: the lanes meet in group_sum's shuffles.
+// ------------------------------------------------------------------------------------------------
+template <int LPC>
+__global__ __launch_bounds__(BLOCK) void k_tracer_kgrad(const MeshDev m, const TracerKgradArgs a)
+{
+    constexpr int NG = BLOCK / LPC;
+    const int grp = uniform_if_wave<LPC>(threadIdx.x / LPC), l = threadIdx.x % LPC;
+    const int K = m.K;
+    for (int c = blockIdx.x * NG + grp; c < m.nC; c += gridDim.x * NG) {
+        const double area = cptr(m.areaCell)[c];
+        const size_t row = (size_t)c * K;
+        const double h0 = l < K ? a.ph[row + l] : 0.0;
+        for (int f0 = 0; f0 < a.nF; f0 += TRA_TJ) {
+            const int nf = min(TRA_TJ, a.nF - f0);
+            double sk[TRA_TJ], s4[TRA_TJ], wk0[TRA_TJ], w40[TRA_TJ];
+            double *Wk[TRA_TJ], *W4[TRA_TJ];
+            size_t jo[TRA_TJ];
+#pragma unroll
+            for (int jj = 0; jj < TRA_TJ; ++jj) {
+                sk[jj] = 0.0;
+                s4[jj] = 0.0;
+                Wk[jj] = jj < nf ? cptr(a.W)[2 * (f0 + jj)] : nullptr;      // wave-uniform; the tables are kernel-invariant
+                W4[jj] = jj < nf ? cptr(a.W)[2 * (f0 + jj) + 1] : nullptr;
+                jo[jj] = jj < nf ? (size_t)cptr(a.tracer)[f0 + jj] * a.stride : 0;
+                // lane 0 fetches the densities' old values beside the streams, not behind the shuffles
+                wk0[jj] = l == 0 && Wk[jj] ? Wk[jj][c] : 0.0;
+                w40[jj] = l == 0 && W4[jj] ? W4[jj][c] : 0.0;
+            }
+            for (int k = l; k < K; k += LPC) {
+                const size_t off = row + k;
+                const double hc = k == l ? h0 : a.ph[off];
+#pragma unroll
+                for (int jj = 0; jj < TRA_TJ; ++jj)
+                    if (jj < nf) {
+                        const double p = hc * a.L[(size_t)(f0 + jj) * a.stride + off];
+                        if (Wk[jj]) sk[jj] += p * a.y[jo[jj] + off];
+                        if (W4[jj]) s4[jj] += p * a.M[jo[jj] + off];
+                    }
+            }
+#pragma unroll
+            for (int jj = 0; jj < TRA_TJ; ++jj)
+                if (jj < nf) {
+                    if (Wk[jj]) {
+                        const double t = group_sum<LPC>(sk[jj]);
+                        if (l == 0) Wk[jj][c] = wk0[jj] + area * t;
+                    }
+                    if (W4[jj]) {
+                        const double t = group_sum<LPC>(s4[jj]);
+                        if (l == 0) W4[jj][c] = w40[jj] - area * t;
+                    }
+                }
+        }
+    }
+}
+
+template <int LPC>
+static hipError_t launch_tracer_kgrad_lpc(const MeshDev &m, const TracerKgradArgs &a, hipStream_t s)
+{
+    const int ng = BLOCK / LPC;
+    const int grid = std::min(std::max((m.nC + ng - 1) / ng, 1), 65536);
+    hipLaunchKernelGGL((k_tracer_kgrad<LPC>), dim3(grid), dim3(BLOCK), 0, s, m, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_tracer_kgrad(const MeshDev &m, const TracerKgradArgs &a, int lpc, hipStream_t s)
+{
+    if (a.nF <= 0) return hipSuccess;
+#define CALL(L) launch_tracer_kgrad_lpc<L>(m, a, s)
+    DISPATCH_LPC(lpc, CALL)
+#undef CALL
+}
+
 }  // namespace moka

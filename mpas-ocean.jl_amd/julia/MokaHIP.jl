@@ -636,6 +636,27 @@ function source_gradient!(out::Matrix{Float64}, t::TracerTape, j::Integer)
     check(ccall((:moka_tracer_adjoint_source_download, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), t.handle, j - 1, out), t.state.backend.ctx)
     out
 end
+# d J / d kappa_j and d J / d kappa4_j (include/moka_hip.h states the algebra): tracer j's (1-based) set becomes exactly (kappa,
+# biharmonic).  Only while the tape holds no recorded step: the steps recorded from then on also keep the provisional fields of a flagged
+# tracer.  Changing the set of flagged tracers drops what earlier sweeps accumulated.
+const TRACER_GRAD_KAPPA = Cint(1)
+const TRACER_GRAD_KAPPA4 = Cint(2)
+function want_diffusivity_gradient!(t::TracerTape, j::Integer; kappa::Bool = true, biharmonic::Bool = false)
+    for (bit, on) in ((TRACER_GRAD_KAPPA, kappa), (TRACER_GRAD_KAPPA4, biharmonic))
+        check(ccall((:moka_tracer_adjoint_want_diffusivity_gradient, lib), Cint, (Ptr{Cvoid}, Int32, Cint, Cint), t.handle, j - 1, bit, on ? 1 : 0), t.state.backend.ctx)
+    end
+end
+function diffusivity_gradient(t::TracerTape, j::Integer; biharmonic::Bool = false)
+    out = Ref{Float64}(0.0)
+    check(ccall((:moka_tracer_adjoint_diffusivity_gradient, lib), Cint, (Ptr{Cvoid}, Int32, Cint, Ref{Float64}), t.handle, j - 1, biharmonic ? TRACER_GRAD_KAPPA4 : TRACER_GRAD_KAPPA, out), t.state.backend.ctx)
+    out[]
+end
+biharmonic_gradient(t::TracerTape, j::Integer) = diffusivity_gradient(t, j; biharmonic = true)
+# the per-cell sensitivity density (nCells values, the caller's numbering) whose sum over the cells is the scalar
+function diffusivity_density!(out::Vector{Float64}, t::TracerTape, j::Integer; biharmonic::Bool = false)
+    check(ccall((:moka_tracer_adjoint_diffusivity_density_download, lib), Cint, (Ptr{Cvoid}, Int32, Cint, Ptr{Float64}), t.handle, j - 1, biharmonic ? TRACER_GRAD_KAPPA4 : TRACER_GRAD_KAPPA, out), t.state.backend.ctx)
+    out
+end
 # 1 the patch form, 2 the generic form of the reverse tracer kernel served the last reverse stage, 0 none yet
 tracer_adjoint_path(t::TracerTape) = Int(ccall((:moka_tracer_adjoint_path, lib), Cint, (Ptr{Cvoid},), t.handle))
 

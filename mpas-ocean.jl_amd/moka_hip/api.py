@@ -771,13 +771,15 @@ class TracerAdjointTape:
     steps of a model with tracers, then turn d J / d (tracers after the last step) into d J / d (tracers before the first recorded
     step), the flow held as it ran.  The tracer step is linear in the tracers, so this is an exact transpose; it works over the
     linear, nonlinear, Del2 and Del4 dycores alike.  want_source_gradient(j) makes the sweep also return d J / d q_j for a source
-    q_j that acts identically in every recorded step.  Sensitivities to the flow or to the diffusivities are out of scope."""
+    q_j that acts identically in every recorded step, want_diffusivity_gradient(j) -- before the first recorded step -- the scalars
+    d J / d kappa_j and d J / d kappa4_j and their per-cell densities.  Sensitivities to the flow are out of scope."""
 
     def __init__(self, Prog: "PrognosticVars", capacity_steps: int):
         self._state = Prog._state
         self._ctx = self._state.mesh.backend._h
         self._shape = tuple(Prog.layerThickness[-1].shape)
         self._h = C.c_void_p()
+        self._kflags = {}
         L.check(L.lib().moka_tracer_tape_create(self._state._h, int(capacity_steps), C.byref(self._h)), self._ctx)
         _own(self, L.lib().moka_tracer_tape_destroy, self._h, self._state, self._state.mesh, self._state.mesh.backend)
         self._state._dependents.append(weakref.ref(self))
@@ -821,9 +823,41 @@ class TracerAdjointTape:
         L.check(L.lib().moka_tracer_adjoint_source_download(self._h, int(j), L.f64(out)), self._ctx)
         return out
 
-    def gradient(self, seeds, sources: bool = False):
+    def want_diffusivity_gradient(self, j: int, kappa: bool = True, biharmonic: bool = False):
+        """moka_tracer_adjoint_want_diffusivity_gradient: tracer j's set becomes exactly (kappa, biharmonic).  Only while the tape
+        holds no recorded step: the steps recorded from now on also keep the provisional fields of a flagged tracer, and the sweep
+        accumulates d J / d kappa_j and / or d J / d kappa4_j.  Changing the set of flagged tracers drops what earlier sweeps left."""
+        for bit, on in ((L.TRACER_GRAD_KAPPA, kappa), (L.TRACER_GRAD_KAPPA4, biharmonic)):
+            L.check(L.lib().moka_tracer_adjoint_want_diffusivity_gradient(self._h, int(j), bit, 1 if on else 0), self._ctx)
+        self._kflags[int(j)] = (bool(kappa), bool(biharmonic))
+
+    def _kgrad(self, j: int, what: int) -> float:
+        out = C.c_double()
+        L.check(L.lib().moka_tracer_adjoint_diffusivity_gradient(self._h, int(j), what, C.byref(out)), self._ctx)
+        return float(out.value)
+
+    def diffusivity_gradient(self, j: int) -> float:
+        """d J / d kappa_j as it stands (after a sweep: the derivative with respect to a diffusivity that acts identically in every
+        recorded step): the sum of diffusivity_density(j) over the cells."""
+        return self._kgrad(j, L.TRACER_GRAD_KAPPA)
+
+    def biharmonic_gradient(self, j: int) -> float:
+        """d J / d kappa4_j, likewise."""
+        return self._kgrad(j, L.TRACER_GRAD_KAPPA4)
+
+    def diffusivity_density(self, j: int, biharmonic: bool = False) -> np.ndarray:
+        """The per-cell sensitivity density of d J / d kappa_j (biharmonic: of d J / d kappa4_j), nCells values in the caller's
+        numbering: where J feels the mixing."""
+        out = np.empty(self._shape[0], dtype=np.float64)
+        what = L.TRACER_GRAD_KAPPA4 if biharmonic else L.TRACER_GRAD_KAPPA
+        L.check(L.lib().moka_tracer_adjoint_diffusivity_density_download(self._h, int(j), what, L.f64(out)), self._ctx)
+        return out
+
+    def gradient(self, seeds, sources: bool = False, diffusivity: bool = False):
         """seeds: one entry per tracer, None meaning zero.  Seeds, sweeps and returns the list of gradients d J / d phi_0; with
-        sources=True every tracer's source gradient is asked for and (dphi0, dq) is returned."""
+        sources=True every tracer's source gradient is asked for and (dphi0, dq) is returned.  diffusivity=True appends the two
+        vectors (d J / d kappa_j), (d J / d kappa4_j) over the tracers, NaN where want_diffusivity_gradient did not ask (that has to
+        happen before the steps are recorded, so this call cannot do it)."""
         seeds = list(seeds)
         if sources:
             for j in range(len(seeds)):
@@ -832,9 +866,18 @@ class TracerAdjointTape:
             self.seed(j, a)
         self.sweep()
         dphi0 = [self.download(j) for j in range(len(seeds))]
+        out = (dphi0,)
         if sources:
-            return dphi0, [self.source_gradient(j) for j in range(len(seeds))]
-        return dphi0
+            out += ([self.source_gradient(j) for j in range(len(seeds))],)
+        if diffusivity:
+            dk, dk4 = np.full(len(seeds), np.nan), np.full(len(seeds), np.nan)
+            for j, (k, k4) in self._kflags.items():
+                if k and j < len(seeds):
+                    dk[j] = self.diffusivity_gradient(j)
+                if k4 and j < len(seeds):
+                    dk4[j] = self.biharmonic_gradient(j)
+            out += (dk, dk4)
+        return out if len(out) > 1 else dphi0
 
     def path(self) -> int:
         """moka_tracer_adjoint_path: 1 the patch form, 2 the generic form of the reverse kernel, 0 before the first reverse stage."""
