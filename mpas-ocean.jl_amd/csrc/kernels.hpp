@@ -236,9 +236,8 @@ struct TracerLapArgs {
     const double *kappa4, *dvdc;  // nT coefficients (only their being zero or not matters here); the plan's (nC, ME) dvEdge / dcEdge
     double *out;
 };
-// the kernel that serves the pass: k_tracer_patch's layout without the harmonic extras (dvdc takes the place of sdv), so
+// The kernel that serves the pass: k_tracer_patch's layout without the harmonic extras (dvdc takes the place of sdv), so
 // tracer_kernel(m, lpc, nT, generic, false, false) decides.  form 1: k_tracer_lap_patch, form 2: k_tracer_lap_cell.
-TracerKernel tracer_lap_kernel(const MeshDev &m, int lpc, int nT, bool generic);
 hipError_t launch_tracer_lap(const MeshDev &m, const TracerLapArgs &a, int lpc, bool generic, hipStream_t s);
 
 // ---- reverse mode of the tracer step over a frozen flow (moka_tracer_tape_*; tracer_adjoint.hip): one launch per reverse stage ----
@@ -265,8 +264,13 @@ struct TracerAdjArgs {
     // dvdc, and M of a tracer with kappa4[j] == 0 is never read.
     const double *kappa4, *lapy;
 };
-// the kernel that serves a reverse stage, for the launcher and for moka_tracer_adjoint_path: the forward choice (same rows in LDS)
-TracerKernel tracer_adjoint_kernel(const MeshDev &m, int lpc, int nT, bool generic, bool diff, bool bih);
+// The kernel that serves a reverse stage, for the launcher and for moka_tracer_adjoint_path.  The reverse kernels stage what the forward
+// ones do (ph rows and one gathered row set per resident tracer, two with bih, the same records), so the form, the LDS size and the chunk
+// are tracer_kernel's: one decision for both directions.
+inline TracerKernel tracer_adjoint_kernel(const MeshDev &m, int lpc, int nT, bool generic, bool diff, bool bih)
+{
+    return tracer_kernel(m, lpc, nT, generic, diff, bih);
+}
 hipError_t launch_tracer_adjoint(const MeshDev &m, const TracerAdjArgs &a, int lpc, bool generic, hipStream_t s);
 // g = X / hn and y = (b4 * g) * invArea, elementwise over nT fields: the head of a reverse step
 // G: TracerAdjArgs::G (nullptr: no gradient wanted); the head adds tau_3 = b4 * g, the value y multiplies by invArea

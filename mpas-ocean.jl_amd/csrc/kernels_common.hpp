@@ -1,5 +1,6 @@
 // kernels_common.hpp -- device helpers and launch macros shared by the kernel translation units of libmoka_hip
-// (kernels.hip: stage / Forward-Euler / utility kernels; nonlinear.hip; adjoint.hip).
+// (kernels.hip: stage / Forward-Euler / utility kernels; nonlinear.hip; adjoint.hip; tracers.hip and tracer_adjoint.hip through
+// tracer_patch.hpp, the row cache their patch-form kernels share).
 #pragma once
 #include <atomic>
 #include <algorithm>

@@ -1,5 +1,5 @@
 // tracer_adjoint.hip -- reverse mode of the passive tracer transport over a frozen flow (gfx950; moka_tracer_tape_*, NOT in the reference).
-#include "kernels_common.hpp"
+#include "tracer_patch.hpp"
 
 namespace moka {
 
@@ -37,9 +37,6 @@ __device__ __forceinline__ void tracer_adj_update(const TracerAdjArgs &a, double
     out = tau * invA;
 }
 
-constexpr int TRA_NT = 256;   // threads of a k_tracer_adj_patch workgroup
-constexpr int TRA_TJ = 4;     // tracers whose sums a lane of k_tracer_adj_cell carries at once (the slot's factor is formed once per TRA_TJ)
-
 // g = X / hn and the first gathered field y = (b4 * g) * invArea of a reverse step: elementwise over (tracer, cell, level)
 template <bool SG>
 __global__ __launch_bounds__(BLOCK) void k_tracer_adj_seed(const double *X, const double *hn, const double *invArea, double *g, double *y,
@@ -68,11 +65,11 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_adj_cell(const MeshDev m, cons
         for (int k = l; k < K; k += LPC) {
             const size_t off = (size_t)c * K + k;
             const double hc = a.ph[off];
-            for (int j0 = 0; j0 < a.nT; j0 += TRA_TJ) {
-                const int nj = min(TRA_TJ, a.nT - j0);
-                double r[TRA_TJ], yc[TRA_TJ], kap[TRA_TJ], k4[BIH ? TRA_TJ : 1], mc[BIH ? TRA_TJ : 1];
+            for (int j0 = 0; j0 < a.nT; j0 += TR_TJ) {
+                const int nj = min(TR_TJ, a.nT - j0);
+                double r[TR_TJ], yc[TR_TJ], kap[TR_TJ], k4[BIH ? TR_TJ : 1], mc[BIH ? TR_TJ : 1];
 #pragma unroll
-                for (int jj = 0; jj < TRA_TJ; ++jj) {
+                for (int jj = 0; jj < TR_TJ; ++jj) {
                     r[jj] = 0.0;
                     yc[jj] = jj < nj ? a.y[(size_t)(j0 + jj) * a.stride + off] : 0.0;
                     kap[jj] = DIFF && jj < nj ? cptr(a.kappa)[j0 + jj] : 0.0;
@@ -90,7 +87,7 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_adj_cell(const MeshDev m, cons
                     const double w = (0.5 * F) * cptr(m.sdv)[(size_t)c * ME + i];
                     const double dd = DIFF ? cptr(a.dvdc)[(size_t)c * ME + i] : 0.0;
 #pragma unroll
-                    for (int jj = 0; jj < TRA_TJ; ++jj)
+                    for (int jj = 0; jj < TR_TJ; ++jj)
                         if (jj < nj) {
                             const double yn = a.y[(size_t)(j0 + jj) * a.stride + noff];
                             r[jj] += w * (yc[jj] - yn);
@@ -101,7 +98,7 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_adj_cell(const MeshDev m, cons
                         }
                 }
 #pragma unroll
-                for (int jj = 0; jj < TRA_TJ; ++jj)
+                for (int jj = 0; jj < TR_TJ; ++jj)
                     if (jj < nj) {
                         const size_t joff = (size_t)(j0 + jj) * a.stride + off;
                         double sOut, out, tau;
@@ -116,89 +113,30 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_adj_cell(const MeshDev m, cons
     }
 }
 
-// Patch form (even 34 <= K <= 64, hexagon-width byte-offset records): k_tracer_patch's shape -- one workgroup per patch, half a wave per
-// cell, a lane owns levels 2l and 2l + 1.  The patch's records and the ph rows and the y rows of `chunk` tracers of its own cells are
-// staged in LDS (the forward kernel's layout, hence its LDS formula and its chunking: tracer_kernel); a cell reads its neighbours'
-// cached rows in one burst and overwrites the lanes of foreign rows with masked global loads by byte offset.  The slot factors
+// Patch form (tracer_patch.hpp): k_tracer_patch's shape and LDS layout, hence its LDS formula and its chunking (tracer_kernel) -- the
+// patch's records and the ph rows and the y rows of `chunk` tracers of its own cells are staged in LDS.  The slot factors
 // (0.5 * F) * sdv are formed once per cell and pass and reused by the tracer loop; v = r / ph_s and ph_0 * (g + S) use the staged own row.
-// BIH: a resident tracer takes a second row set, for M (row type 1 + chunk + jj), as in k_tracer_patch.
+// BIH: a resident tracer takes a second row set, for M (row set 1 + chunk + jj), as in k_tracer_patch.
 template <int ME_, bool DIFF, bool SG, bool BIH>
-__global__ __launch_bounds__(TRA_NT, 2) void k_tracer_adj_patch(const MeshDev m, const TracerAdjArgs a, const int chunk)
+__global__ __launch_bounds__(TR_NT, 2) void k_tracer_adj_patch(const MeshDev m, const TracerAdjArgs a, const int chunk)
 {
-    constexpr int NG = TRA_NT / 32;
     static_assert(ME_ == 6, "burst width");
     static_assert(DIFF || !BIH, "BIH instantiates only together with DIFF");
     extern __shared__ __align__(16) unsigned char tra_smem[];
-    const int tid = threadIdx.x, grp = tid >> 5, l = tid & 31, K = m.K, CI = m.CI, mC = m.maxOwnC;
-    const bool act = 2 * l < K;
-    const unsigned rowB = (unsigned)K * 8u, lo = (unsigned)l * 16u;
-    double *sRows = reinterpret_cast<double *>(tra_smem);                   // [1 + chunk][maxOwnC][K]  ph rows, then y rows per tracer
-    double *sSd = sRows + (size_t)(1 + (BIH ? 2 : 1) * chunk) * mC * K;     // (BIH: then M rows per tracer)  [maxOwnC][ME]  sdv
-    double *sDd = sSd + (size_t)mC * ME_;                                   // [maxOwnC][ME]  dvdc (DIFF only)
-    double *sIa = sDd + (DIFF ? (size_t)mC * ME_ : 0);                      // [maxOwnC]      invArea
-    uint32_t *sRec = reinterpret_cast<uint32_t *>(sIa + mC);                // [maxOwnC][CI]  cRec
-    int *sMl = reinterpret_cast<int *>(sRec + (size_t)mC * CI);             // [maxOwnC][ME]  maxLevelEdgeTop of the slot's edge
     const int pl_ = patch_of_block(m.nPatches);
     if (pl_ >= m.nPatches) return;
-    const int p = pl_ + m.patchBegin;
-    const int c0 = m.patchCellStart[p], nc = m.patchCellStart[p + 1] - c0;
-    const unsigned ownB = (unsigned)c0 * rowB, ownN = (unsigned)nc * rowB;
-    const glb_bytes_t uG = (glb_bytes_t)a.pu, hG = (glb_bytes_t)a.ph;
-    const uint32_t ldsH = (uint32_t)(size_t)sRows + lo;
+    const TracerPatch P = tracer_patch_open<ME_>(m, tra_smem, pl_, 1 + (BIH ? 2 : 1) * chunk, true, DIFF);
+    const glb_bytes_t uG = (glb_bytes_t)a.pu;
 
-    // rows [rb * nc, (1 + cj) * nc) of the cache from global memory: row type 0 = ph, 1 + jj = y of tracer j0 + jj; eight in flight per half-wave
+    // the rows of a pass: ph (rb == 0) and y of its cj tracers, then the M rows of those with kappa4 != 0
     auto stage_rows = [&](int rb, int j0, int cj) {
-        if (!act) return;
-        const int nrows = (1 + cj) * nc;
-        for (int q0 = rb * nc + grp; q0 < nrows; q0 += 8 * NG) {
-            double2 v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int q = q0 + j * NG;
-                v[j] = make_double2(0.0, 0.0);
-                if (q < nrows) {
-                    const int ty = q / nc, ci = q - ty * nc;
-                    const double *src = ty == 0 ? a.ph : a.y + (size_t)(j0 + ty - 1) * a.stride;
-                    v[j] = *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(src) + (ownB + (unsigned)ci * rowB + lo));
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int q = q0 + j * NG;
-                if (q < nrows) {
-                    const int ty = q / nc, ci = q - ty * nc;
-                    reinterpret_cast<double2 *>(sRows + ((size_t)ty * mC + ci) * K)[l] = v[j];
-                }
-            }
-        }
-        if (BIH)      // the M rows of the pass's tracers with kappa4 != 0: row type 1 + chunk + jj
-            for (int jj = 0; jj < cj; ++jj) {
-                if (a.kappa4[j0 + jj] == 0.0) continue;
-                const char *src = reinterpret_cast<const char *>(a.lapy + (size_t)(j0 + jj) * a.stride);
-                double *dst = sRows + (size_t)(1 + chunk + jj) * mC * K;
-                for (int ci = grp; ci < nc; ci += NG)
-                    reinterpret_cast<double2 *>(dst + (size_t)ci * K)[l] = *reinterpret_cast<const double2 *>(src + (ownB + (unsigned)ci * rowB + lo));
-            }
+        tracer_stage_rows(P, rb, cj, a.ph, a.y + (size_t)j0 * a.stride, a.stride);
+        if constexpr (BIH)
+            for (int jj = 0; jj < cj; ++jj)
+                if (a.kappa4[j0 + jj] != 0.0) tracer_stage_set(P, 1 + chunk + jj, a.lapy + (size_t)(j0 + jj) * a.stride);
     };
 
-    {   // records: as in k_tracer_patch, the first TRA_NT entries of each list go through registers ahead of the first LDS write
-        const int nRec = nc * CI, nSd = nc * ME_;
-        const uint32_t r0 = tid < nRec ? m.cRec[(size_t)c0 * CI + tid] : 0u;
-        const double sd0 = tid < nSd ? m.sdv[(size_t)c0 * ME_ + tid] : 0.0;
-        const double dd0 = DIFF && tid < nSd ? a.dvdc[(size_t)c0 * ME_ + tid] : 0.0;
-        const int ml0 = tid < nSd ? m.mltc[(size_t)c0 * ME_ + tid] : 0;
-        const double ia0 = tid < nc ? m.invArea[c0 + tid] : 0.0;
-        stage_rows(0, 0, min(chunk, a.nT));
-        if (tid < nRec) sRec[tid] = r0;
-        if (tid < nSd) { sSd[tid] = sd0; sMl[tid] = ml0; }
-        if (DIFF && tid < nSd) sDd[tid] = dd0;
-        if (tid < nc) sIa[tid] = ia0;
-        for (int i = tid + TRA_NT; i < nRec; i += TRA_NT) sRec[i] = m.cRec[(size_t)c0 * CI + i];
-        for (int i = tid + TRA_NT; i < nSd; i += TRA_NT) { sSd[i] = m.sdv[(size_t)c0 * ME_ + i]; sMl[i] = m.mltc[(size_t)c0 * ME_ + i]; }
-        if (DIFF)
-            for (int i = tid + TRA_NT; i < nSd; i += TRA_NT) sDd[i] = a.dvdc[(size_t)c0 * ME_ + i];
-        for (int i = tid + TRA_NT; i < nc; i += TRA_NT) sIa[i] = m.invArea[c0 + i];
-    }
+    tracer_stage_records<ME_, DIFF>(P, m, a.dvdc, [&] { stage_rows(0, 0, min(chunk, a.nT)); });
     for (int j0 = 0; j0 < a.nT; j0 += chunk) {
         const int cj = min(chunk, a.nT - j0);
         if (j0 > 0) {
@@ -206,95 +144,55 @@ __global__ __launch_bounds__(TRA_NT, 2) void k_tracer_adj_patch(const MeshDev m,
             stage_rows(1, j0, cj);
         }
         __syncthreads();
-        if (!act) continue;
-        for (int ci = grp; ci < nc; ci += NG) {
-            const uint32_t *rec = sRec + (size_t)ci * CI;
-            const unsigned mask = rec[2 * ME_];
+        if (!P.act) continue;
+        for (int ci = P.grp; ci < P.nc; ci += TR_NG) {
+            const uint32_t *rec = P.rec + (size_t)ci * P.CI;
             double2 w[ME_], hE[DIFF ? ME_ : 1];
             bool ch[ME_], okx[ME_], oky[ME_];
             uint32_t aoff[ME_], gh[ME_];
-            const double *sd = sSd + ci * ME_, *dd = sDd + ci * ME_;
-            const double2 hc = reinterpret_cast<const double2 *>(sRows + (size_t)ci * K)[l];
-            {
-                double2 uu[ME_];
-                uint32_t ah[ME_];
-                v4u_t rh[ME_];
+            const double *sd = P.sd + ci * ME_, *dd = P.dd + ci * ME_;
+            const double2 hc = tracer_own_row(P, 0, ci);
+            double2 uu[ME_], hh[ME_];
 #pragma unroll
-                for (int i = 0; i < ME_; ++i) uu[i] = glb_row2(uG + (rec[i] + lo));
+            for (int i = 0; i < ME_; ++i) uu[i] = glb_row2(uG + (rec[i] + P.lo));
+            tracer_slots<ME_>(P, rec, ch, aoff, gh);
+            tracer_gather<ME_>(P, 0, a.ph, ch, aoff, gh, hh);
+            tracer_level_masks<ME_>(P, ci, rec[2 * ME_], okx, oky);
 #pragma unroll
-                for (int i = 0; i < ME_; ++i) {        // cached row or row 0 of the cache (then overwritten by the masked global load)
-                    const unsigned ho = rec[ME_ + i], loc = ho - ownB;
-                    ch[i] = loc < ownN;
-                    aoff[i] = ch[i] ? loc : 0u;
-                    gh[i] = ho + lo;
-                    asm("" : "+v"(gh[i]));             // the offset stays in a VGPR (see k_nl_prep5)
-                    ah[i] = ldsH + aoff[i];
-                }
-                lds_burst<ME_>(rh, ah);
-#pragma unroll
-                for (int i = 0; i < ME_; ++i) {
-                    double2 hh = __builtin_bit_cast(double2, rh[i]);
-                    if (!ch[i]) hh = glb_row2(hG + gh[i]);
-                    const double2 he = make_double2(0.5 * (hc.x + hh.x), 0.5 * (hc.y + hh.y));
-                    const double2 F = make_double2(uu[i].x * he.x, uu[i].y * he.y);
-                    w[i] = make_double2((0.5 * F.x) * sd[i], (0.5 * F.y) * sd[i]);
-                    if (DIFF) hE[i] = he;
-                    const int ml = sMl[ci * ME_ + i];
-                    const bool valid = (mask >> i) & 1u;
-                    okx[i] = valid && 2 * l < ml;
-                    oky[i] = valid && 2 * l + 1 < ml;
-                }
+            for (int i = 0; i < ME_; ++i) {
+                const double2 he = make_double2(0.5 * (hc.x + hh[i].x), 0.5 * (hc.y + hh[i].y));
+                const double2 F = make_double2(uu[i].x * he.x, uu[i].y * he.y);
+                w[i] = make_double2((0.5 * F.x) * sd[i], (0.5 * F.y) * sd[i]);
+                if constexpr (DIFF) hE[i] = he;
             }
-            const double invA = sIa[ci];
-            const unsigned orow = ownB + (unsigned)ci * rowB + lo;       // the cell's own row in every (K, nC) array
+            const double invA = P.ia[ci];
+            const unsigned orow = P.ownB + (unsigned)ci * P.rowB + P.lo;       // the cell's own row in every (K, nC) array
             for (int jj = 0; jj < cj; ++jj) {
                 const size_t jo = (size_t)(j0 + jj) * a.stride;
                 const double kap = DIFF ? a.kappa[j0 + jj] : 0.0;
-                const glb_bytes_t yG = (glb_bytes_t)(a.y + jo);
-                const uint32_t ldsY = ldsH + (uint32_t)(1 + jj) * (uint32_t)mC * rowB;
-                uint32_t ap[ME_];
-                v4u_t rp[ME_];
-#pragma unroll
-                for (int i = 0; i < ME_; ++i) ap[i] = ldsY + aoff[i];
-                lds_burst<ME_>(rp, ap);
-                const double2 yc = reinterpret_cast<const double2 *>(sRows + ((size_t)(1 + jj) * mC + ci) * K)[l];
-                double2 r = make_double2(0.0, 0.0);
                 double2 yy[ME_];
-#pragma unroll
-                for (int i = 0; i < ME_; ++i) {
-                    yy[i] = __builtin_bit_cast(double2, rp[i]);
-                    if (!ch[i]) yy[i] = glb_row2(yG + gh[i]);
-                }
+                tracer_gather<ME_>(P, 1 + jj, a.y + jo, ch, aoff, gh, yy);
+                const double2 yc = tracer_own_row(P, 1 + jj, ci);
+                double2 r = make_double2(0.0, 0.0);
                 const double kap4 = BIH ? a.kappa4[j0 + jj] : 0.0;
                 const bool b4 = BIH && kap4 != 0.0;             // wave-uniform
                 double2 mm[BIH ? ME_ : 1], mc = make_double2(0.0, 0.0);
-                if (BIH) {
+                if constexpr (BIH) {
 #pragma unroll
                     for (int i = 0; i < ME_; ++i) mm[i] = make_double2(0.0, 0.0);
                     if (b4) {                                   // M gathered as y is, from its own row set
-                        const glb_bytes_t mG = (glb_bytes_t)(a.lapy + jo);
-                        const uint32_t ldsM = ldsH + (uint32_t)(1 + chunk + jj) * (uint32_t)mC * rowB;
-                        uint32_t al[ME_];
-                        v4u_t rl[ME_];
-#pragma unroll
-                        for (int i = 0; i < ME_; ++i) al[i] = ldsM + aoff[i];
-                        lds_burst<ME_>(rl, al);
-                        mc = reinterpret_cast<const double2 *>(sRows + ((size_t)(1 + chunk + jj) * mC + ci) * K)[l];
-#pragma unroll
-                        for (int i = 0; i < ME_; ++i) {
-                            mm[i] = __builtin_bit_cast(double2, rl[i]);
-                            if (!ch[i]) mm[i] = glb_row2(mG + gh[i]);
-                        }
+                        tracer_gather<ME_>(P, 1 + chunk + jj, a.lapy + jo, ch, aoff, gh, mm);
+                        mc = tracer_own_row(P, 1 + chunk + jj, ci);
                     }
                 }
 #pragma unroll
                 for (int i = 0; i < ME_; ++i) {
                     double rx = r.x + w[i].x * (yc.x - yy[i].x), ry = r.y + w[i].y * (yc.y - yy[i].y);
-                    if (DIFF) {
+                    if constexpr (DIFF) {
                         rx += ((kap * hE[i].x) * dd[i]) * (yy[i].x - yc.x);
                         ry += ((kap * hE[i].y) * dd[i]) * (yy[i].y - yc.y);
                     }
-                    if (BIH)
+                    if constexpr (BIH)
                         if (b4) {
                             rx -= ((kap4 * hE[i].x) * dd[i]) * (mm[i].x - mc.x);
                             ry -= ((kap4 * hE[i].y) * dd[i]) * (mm[i].y - mc.y);
@@ -319,12 +217,7 @@ __global__ __launch_bounds__(TRA_NT, 2) void k_tracer_adj_patch(const MeshDev m,
     }
 }
 
-// The reverse kernels stage what the forward ones do (ph rows and one gathered row set per resident tracer, two with bih, the same
-// records), so the form, the LDS size and the chunk are tracer_kernel's: one decision for both directions.
-TracerKernel tracer_adjoint_kernel(const MeshDev &m, int lpc, int nT, bool generic, bool diff, bool bih)
-{
-    return tracer_kernel(m, lpc, nT, generic, diff, bih);
-}
+
 
 hipError_t launch_tracer_adj_seed(const MeshDev &m, const double *X, const double *hn, double *g, double *y, double b4, int nT,
                                   double *const *G, hipStream_t s)
@@ -337,29 +230,10 @@ hipError_t launch_tracer_adj_seed(const MeshDev &m, const double *X, const doubl
     return hipGetLastError();
 }
 
-template <int LPC, bool DIFF, bool SG, bool BIH>
-static hipError_t launch_tracer_adj_cell(const MeshDev &m, const TracerAdjArgs &a, hipStream_t s)
-{
-    const int ng = BLOCK / LPC;
-    const int grid = std::min(std::max((m.nC + ng - 1) / ng, 1), 65536);
-    hipLaunchKernelGGL((k_tracer_adj_cell<LPC, DIFF, SG, BIH>), dim3(grid), dim3(BLOCK), 0, s, m, a);
-    return hipGetLastError();
-}
-
-template <bool DIFF, bool SG, bool BIH>
-static hipError_t launch_tracer_adj_patch(const MeshDev &m, const TracerAdjArgs &a, const TracerKernel &k, hipStream_t s)
-{
-    if (k.lds > 64 * 1024)
-        if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_tracer_adj_patch<6, DIFF, SG, BIH>)}, 80 * 1024); e != hipSuccess)
-            return e;
-    hipLaunchKernelGGL((k_tracer_adj_patch<6, DIFF, SG, BIH>), dim3(patch_grid(m)), dim3(TRA_NT), k.lds, s, m, a, k.chunk);
-    return hipGetLastError();
-}
-
 template <bool DIFF, bool SG, bool BIH>
 static hipError_t launch_tracer_adj_generic(const MeshDev &m, const TracerAdjArgs &a, int lpc, hipStream_t s)
 {
-#define CALL(L) launch_tracer_adj_cell<L, DIFF, SG, BIH>(m, a, s)
+#define CALL(L) launch_tracer_cell_form(k_tracer_adj_cell<L, DIFF, SG, BIH>, L, m, a, s)
     DISPATCH_LPC(lpc, CALL)
 #undef CALL
 }
@@ -370,21 +244,17 @@ hipError_t launch_tracer_adjoint(const MeshDev &m, const TracerAdjArgs &a, int l
     const bool diff = a.kappa != nullptr;       // (then a.dvdc is set too: moka_tracer_adjoint_sweep)
     const bool sg = a.G != nullptr;             // (some tracer's source gradient is wanted: moka_tracer_adjoint_sweep)
     const bool bih = a.kappa4 != nullptr;       // (then a.lapy, a.kappa and a.dvdc are set too: moka_tracer_adjoint_sweep)
-    if (bih && !diff) return hipErrorInvalidValue;      // BIH instantiates only together with DIFF
     const TracerKernel k = tracer_adjoint_kernel(m, lpc, a.nT, generic, diff, bih);
-#define PICK(F, ...)                                                                                          \
-    (bih    ? (sg ? F<true, true, true>(__VA_ARGS__) : F<true, false, true>(__VA_ARGS__))                       \
-     : diff ? (sg ? F<true, true, false>(__VA_ARGS__) : F<true, false, false>(__VA_ARGS__))                     \
-            : (sg ? F<false, true, false>(__VA_ARGS__) : F<false, false, false>(__VA_ARGS__)))
-    if (k.form == 1) return PICK(launch_tracer_adj_patch, m, a, k, s);
-    return PICK(launch_tracer_adj_generic, m, a, lpc, s);
-#undef PICK
+    return pick_tracer_instance(diff, sg, bih, [&](auto D, auto S, auto B) {
+        if (k.form == 1) return launch_tracer_patch_form(k_tracer_adj_patch<6, D.value, S.value, B.value>, m, a, k, s);
+        return launch_tracer_adj_generic<D.value, S.value, B.value>(m, a, lpc, s);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
 // d J / d kappa_j and d J / d kappa4_j (TracerKgradArgs, kernels.hpp: the algebra and the summation order).  An elementwise stream with a
 // column sum: no gather, so one form serves every K and every cell order -- k_tracer_adj_cell's lanes per cell, the strided loop for
-// K > 64.  ph of a lane's first level is read once and kept across the groups of TRA_TJ flagged tracers (for K <= 64 that is every
+// K > 64.  ph of a lane's first level is read once and kept across the groups of TR_TJ flagged tracers (for K <= 64 that is every
 // element); p = ph * L is formed once and serves both products.  No atomics, no LDS: the lanes meet in group_sum's shuffles.
 // ------------------------------------------------------------------------------------------------
 template <int LPC>
@@ -397,13 +267,13 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_kgrad(const MeshDev m, const T
         const double area = cptr(m.areaCell)[c];
         const size_t row = (size_t)c * K;
         const double h0 = l < K ? a.ph[row + l] : 0.0;
-        for (int f0 = 0; f0 < a.nF; f0 += TRA_TJ) {
-            const int nf = min(TRA_TJ, a.nF - f0);
-            double sk[TRA_TJ], s4[TRA_TJ], wk0[TRA_TJ], w40[TRA_TJ];
-            double *Wk[TRA_TJ], *W4[TRA_TJ];
-            size_t jo[TRA_TJ];
+        for (int f0 = 0; f0 < a.nF; f0 += TR_TJ) {
+            const int nf = min(TR_TJ, a.nF - f0);
+            double sk[TR_TJ], s4[TR_TJ], wk0[TR_TJ], w40[TR_TJ];
+            double *Wk[TR_TJ], *W4[TR_TJ];
+            size_t jo[TR_TJ];
 #pragma unroll
-            for (int jj = 0; jj < TRA_TJ; ++jj) {
+            for (int jj = 0; jj < TR_TJ; ++jj) {
                 sk[jj] = 0.0;
                 s4[jj] = 0.0;
                 Wk[jj] = jj < nf ? cptr(a.W)[2 * (f0 + jj)] : nullptr;      // wave-uniform; the tables are kernel-invariant
@@ -417,7 +287,7 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_kgrad(const MeshDev m, const T
                 const size_t off = row + k;
                 const double hc = k == l ? h0 : a.ph[off];
 #pragma unroll
-                for (int jj = 0; jj < TRA_TJ; ++jj)
+                for (int jj = 0; jj < TR_TJ; ++jj)
                     if (jj < nf) {
                         const double p = hc * a.L[(size_t)(f0 + jj) * a.stride + off];
                         if (Wk[jj]) sk[jj] += p * a.y[jo[jj] + off];
@@ -425,7 +295,7 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_kgrad(const MeshDev m, const T
                     }
             }
 #pragma unroll
-            for (int jj = 0; jj < TRA_TJ; ++jj)
+            for (int jj = 0; jj < TR_TJ; ++jj)
                 if (jj < nf) {
                     if (Wk[jj]) {
                         const double t = group_sum<LPC>(sk[jj]);
@@ -440,19 +310,10 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_kgrad(const MeshDev m, const T
     }
 }
 
-template <int LPC>
-static hipError_t launch_tracer_kgrad_lpc(const MeshDev &m, const TracerKgradArgs &a, hipStream_t s)
-{
-    const int ng = BLOCK / LPC;
-    const int grid = std::min(std::max((m.nC + ng - 1) / ng, 1), 65536);
-    hipLaunchKernelGGL((k_tracer_kgrad<LPC>), dim3(grid), dim3(BLOCK), 0, s, m, a);
-    return hipGetLastError();
-}
-
 hipError_t launch_tracer_kgrad(const MeshDev &m, const TracerKgradArgs &a, int lpc, hipStream_t s)
 {
     if (a.nF <= 0) return hipSuccess;
-#define CALL(L) launch_tracer_kgrad_lpc<L>(m, a, s)
+#define CALL(L) launch_tracer_cell_form(k_tracer_kgrad<L>, L, m, a, s)
     DISPATCH_LPC(lpc, CALL)
 #undef CALL
 }

@@ -1,5 +1,5 @@
 // tracers.hip -- passive tracer transport beside the RK4 stages of libmoka_hip (gfx950; moka_set_tracers, NOT in the reference).
-#include "kernels_common.hpp"
+#include "tracer_patch.hpp"
 
 namespace moka {
 
@@ -35,8 +35,6 @@ __device__ __forceinline__ void tracer_update(const TracerArgs &a, double t, dou
     const double qn = (a.stage == 1 ? qc : qnIn) + a.b * t;
     qOut = a.stage == 4 ? qn / hnext : qn;
 }
-
-constexpr int TR_TJ = 4;      // tracers whose sums a lane of k_tracer_cell carries at once (F is formed once per TR_TJ tracers)
 
 // Generic form: LPC lanes span a column, one cell per lane group, index records; any K, any maxEdges (the shape of k_nl_cell).
 template <int LPC, bool DIFF, bool SRC, bool BIH>
@@ -101,95 +99,33 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_cell(const MeshDev m, const Tr
     }
 }
 
-// Patch form (even 34 <= K <= 64, hexagon-width byte-offset records): one workgroup per patch, half a wave per cell, a lane owns levels
-// 2l and 2l + 1 (16 bytes).  The patch's cRec records, sdv, invArea and maxLevelEdgeTop entries and the ph and pphi rows of its own cells
-// are staged in LDS in one phase; a cell then reads its neighbours' cached rows in one burst of ds_read_b128 and overwrites the lanes
-// of foreign rows with exec-masked global loads by 32-bit byte offset (k_nl_prep5's row cache).  `chunk` tracers' rows are resident
-// at a time: a state with more takes further passes over the patch (the pphi rows re-staged, F re-formed once per pass).
+// Patch form (tracer_patch.hpp: the workgroup shape, the LDS layout, the row cache): the patch's records and the ph and pphi rows of its
+// own cells are staged in LDS in one phase.  `chunk` tracers' rows are resident at a time: a state with more takes further passes over the
+// patch (the pphi rows re-staged, F re-formed once per pass).
 // DIFF: the patch's dvdc entries are staged beside sdv, and a cell keeps hE of its slots beside F.  SRC: one more own-row load per
 // sourced tracer, not staged (the LDS layout and the chunking do not know about sources).  BIH: a resident tracer takes a second row
-// set, for L (row type 1 + chunk + jj), staged and gathered as pphi is -- for the tracers with kappa4 != 0 only.
-constexpr int TR_NT = 256;
-
+// set, for L (row set 1 + chunk + jj), staged and gathered as pphi is -- for the tracers with kappa4 != 0 only.
 template <int ME_, bool DIFF, bool SRC, bool BIH>
 __global__ __launch_bounds__(TR_NT, 2) void k_tracer_patch(const MeshDev m, const TracerArgs a, const int chunk)
 {
-    constexpr int NG = TR_NT / 32;
     static_assert(ME_ == 6, "burst width");
     static_assert(DIFF || !BIH, "BIH instantiates only together with DIFF");
     extern __shared__ __align__(16) unsigned char tr_smem[];
-    const int tid = threadIdx.x, grp = tid >> 5, l = tid & 31, K = m.K, CI = m.CI, mC = m.maxOwnC;
-    const bool act = 2 * l < K;
-    const unsigned rowB = (unsigned)K * 8u, lo = (unsigned)l * 16u;
-    double *sRows = reinterpret_cast<double *>(tr_smem);                    // [1 + chunk][maxOwnC][K]  ph rows, then pphi rows per tracer
-    double *sSd = sRows + (size_t)(1 + (BIH ? 2 : 1) * chunk) * mC * K;     // (BIH: then L rows per tracer)  [maxOwnC][ME]  sdv
-    double *sDd = sSd + (size_t)mC * ME_;                                   // [maxOwnC][ME]  dvdc (DIFF only)
-    double *sIa = sDd + (DIFF ? (size_t)mC * ME_ : 0);                      // [maxOwnC]      invArea
-    uint32_t *sRec = reinterpret_cast<uint32_t *>(sIa + mC);                // [maxOwnC][CI]  cRec
-    int *sMl = reinterpret_cast<int *>(sRec + (size_t)mC * CI);             // [maxOwnC][ME]  maxLevelEdgeTop of the slot's edge
     const int pl_ = patch_of_block(m.nPatches);
     if (pl_ >= m.nPatches) return;
-    const int p = pl_ + m.patchBegin;
-    const int c0 = m.patchCellStart[p], nc = m.patchCellStart[p + 1] - c0;
+    const TracerPatch P = tracer_patch_open<ME_>(m, tr_smem, pl_, 1 + (BIH ? 2 : 1) * chunk, true, DIFF);
     const bool s1 = a.stage == 1, s4 = a.stage == 4;
-    const unsigned ownB = (unsigned)c0 * rowB, ownN = (unsigned)nc * rowB;
-    const glb_bytes_t uG = (glb_bytes_t)a.pu, hG = (glb_bytes_t)a.ph;
-    const uint32_t ldsH = (uint32_t)(size_t)sRows + lo;
+    const glb_bytes_t uG = (glb_bytes_t)a.pu;
 
-    // rows [rb * nc, (1 + cj) * nc) of the cache from global memory: row type 0 = ph, 1 + jj = tracer j0 + jj; eight in flight per half-wave
+    // the rows of a pass: ph (rb == 0) and pphi of its cj tracers, then the L rows of those with kappa4 != 0
     auto stage_rows = [&](int rb, int j0, int cj) {
-        if (!act) return;
-        const int nrows = (1 + cj) * nc;
-        for (int q0 = rb * nc + grp; q0 < nrows; q0 += 8 * NG) {
-            double2 v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int q = q0 + j * NG;
-                v[j] = make_double2(0.0, 0.0);
-                if (q < nrows) {
-                    const int ty = q / nc, ci = q - ty * nc;
-                    const double *src = ty == 0 ? a.ph : a.pphi + (size_t)(j0 + ty - 1) * a.stride;
-                    v[j] = *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(src) + (ownB + (unsigned)ci * rowB + lo));
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int q = q0 + j * NG;
-                if (q < nrows) {
-                    const int ty = q / nc, ci = q - ty * nc;
-                    reinterpret_cast<double2 *>(sRows + ((size_t)ty * mC + ci) * K)[l] = v[j];
-                }
-            }
-        }
-        if (BIH)      // the L rows of the pass's tracers with kappa4 != 0: row type 1 + chunk + jj
-            for (int jj = 0; jj < cj; ++jj) {
-                if (a.kappa4[j0 + jj] == 0.0) continue;
-                const char *src = reinterpret_cast<const char *>(a.lap + (size_t)(j0 + jj) * a.stride);
-                double *dst = sRows + (size_t)(1 + chunk + jj) * mC * K;
-                for (int ci = grp; ci < nc; ci += NG)
-                    reinterpret_cast<double2 *>(dst + (size_t)ci * K)[l] = *reinterpret_cast<const double2 *>(src + (ownB + (unsigned)ci * rowB + lo));
-            }
+        tracer_stage_rows(P, rb, cj, a.ph, a.pphi + (size_t)j0 * a.stride, a.stride);
+        if constexpr (BIH)
+            for (int jj = 0; jj < cj; ++jj)
+                if (a.kappa4[j0 + jj] != 0.0) tracer_stage_set(P, 1 + chunk + jj, a.lap + (size_t)(j0 + jj) * a.stride);
     };
 
-    {   // records: the first TR_NT entries of each list go through registers, so that every global load of the phase (rows included)
-        // is issued before the first LDS write; lists longer than that (large patch_cells) finish in plain loops
-        const int nRec = nc * CI, nSd = nc * ME_;
-        const uint32_t r0 = tid < nRec ? m.cRec[(size_t)c0 * CI + tid] : 0u;
-        const double sd0 = tid < nSd ? m.sdv[(size_t)c0 * ME_ + tid] : 0.0;
-        const double dd0 = DIFF && tid < nSd ? a.dvdc[(size_t)c0 * ME_ + tid] : 0.0;
-        const int ml0 = tid < nSd ? m.mltc[(size_t)c0 * ME_ + tid] : 0;
-        const double ia0 = tid < nc ? m.invArea[c0 + tid] : 0.0;
-        stage_rows(0, 0, min(chunk, a.nT));
-        if (tid < nRec) sRec[tid] = r0;
-        if (tid < nSd) { sSd[tid] = sd0; sMl[tid] = ml0; }
-        if (DIFF && tid < nSd) sDd[tid] = dd0;
-        if (tid < nc) sIa[tid] = ia0;
-        for (int i = tid + TR_NT; i < nRec; i += TR_NT) sRec[i] = m.cRec[(size_t)c0 * CI + i];
-        for (int i = tid + TR_NT; i < nSd; i += TR_NT) { sSd[i] = m.sdv[(size_t)c0 * ME_ + i]; sMl[i] = m.mltc[(size_t)c0 * ME_ + i]; }
-        if (DIFF)
-            for (int i = tid + TR_NT; i < nSd; i += TR_NT) sDd[i] = a.dvdc[(size_t)c0 * ME_ + i];
-        for (int i = tid + TR_NT; i < nc; i += TR_NT) sIa[i] = m.invArea[c0 + i];
-    }
+    tracer_stage_records<ME_, DIFF>(P, m, a.dvdc, [&] { stage_rows(0, 0, min(chunk, a.nT)); });
     for (int j0 = 0; j0 < a.nT; j0 += chunk) {
         const int cj = min(chunk, a.nT - j0);
         if (j0 > 0) {
@@ -197,98 +133,57 @@ __global__ __launch_bounds__(TR_NT, 2) void k_tracer_patch(const MeshDev m, cons
             stage_rows(1, j0, cj);
         }
         __syncthreads();
-        if (!act) continue;
-        for (int ci = grp; ci < nc; ci += NG) {
-            const uint32_t *rec = sRec + (size_t)ci * CI;
-            const unsigned mask = rec[2 * ME_];
+        if (!P.act) continue;
+        for (int ci = P.grp; ci < P.nc; ci += TR_NG) {
+            const uint32_t *rec = P.rec + (size_t)ci * P.CI;
             double2 F[ME_], hE[DIFF ? ME_ : 1];
             bool ch[ME_], okx[ME_], oky[ME_];
             uint32_t aoff[ME_], gh[ME_];
-            {
-                double2 uu[ME_];
-                uint32_t ah[ME_];
-                v4u_t rh[ME_];
+            double2 uu[ME_], hh[ME_];
 #pragma unroll
-                for (int i = 0; i < ME_; ++i) uu[i] = glb_row2(uG + (rec[i] + lo));
+            for (int i = 0; i < ME_; ++i) uu[i] = glb_row2(uG + (rec[i] + P.lo));
+            tracer_slots<ME_>(P, rec, ch, aoff, gh);
+            tracer_gather<ME_>(P, 0, a.ph, ch, aoff, gh, hh);
+            tracer_level_masks<ME_>(P, ci, rec[2 * ME_], okx, oky);
+            const double2 hc = tracer_own_row(P, 0, ci);
 #pragma unroll
-                for (int i = 0; i < ME_; ++i) {        // cached row or row 0 of the cache (then overwritten by the masked global load)
-                    const unsigned ho = rec[ME_ + i], loc = ho - ownB;
-                    ch[i] = loc < ownN;
-                    aoff[i] = ch[i] ? loc : 0u;
-                    gh[i] = ho + lo;
-                    asm("" : "+v"(gh[i]));             // the offset stays in a VGPR (see k_nl_prep5)
-                    ah[i] = ldsH + aoff[i];
-                }
-                lds_burst<ME_>(rh, ah);
-                const double2 hc = reinterpret_cast<const double2 *>(sRows + (size_t)ci * K)[l];
-#pragma unroll
-                for (int i = 0; i < ME_; ++i) {
-                    double2 hh = __builtin_bit_cast(double2, rh[i]);
-                    if (!ch[i]) hh = glb_row2(hG + gh[i]);
-                    const double2 he = make_double2(0.5 * (hc.x + hh.x), 0.5 * (hc.y + hh.y));
-                    F[i] = make_double2(uu[i].x * he.x, uu[i].y * he.y);   // Operators.jl:217, DiagnosticVars.jl:165
-                    if (DIFF) hE[i] = he;
-                    const int ml = sMl[ci * ME_ + i];
-                    const bool valid = (mask >> i) & 1u;
-                    okx[i] = valid && 2 * l < ml;
-                    oky[i] = valid && 2 * l + 1 < ml;
-                }
+            for (int i = 0; i < ME_; ++i) {
+                const double2 he = make_double2(0.5 * (hc.x + hh[i].x), 0.5 * (hc.y + hh[i].y));
+                F[i] = make_double2(uu[i].x * he.x, uu[i].y * he.y);   // Operators.jl:217, DiagnosticVars.jl:165
+                if constexpr (DIFF) hE[i] = he;
             }
-            const double *sd = sSd + ci * ME_, *dd = sDd + ci * ME_;
-            const double invA = sIa[ci];
-            const unsigned orow = ownB + (unsigned)ci * rowB + lo;       // the cell's own row in every (K, nC) array
-            const double2 hcO = reinterpret_cast<const double2 *>(sRows + (size_t)ci * K)[l];
+            const double *sd = P.sd + ci * ME_, *dd = P.dd + ci * ME_;
+            const double invA = P.ia[ci];
+            const unsigned orow = P.ownB + (unsigned)ci * P.rowB + P.lo;       // the cell's own row in every (K, nC) array
             const double2 hnext = gload2(a.hnext, orow);
-            const double2 hcur = s1 ? hcO : s4 ? make_double2(0.0, 0.0) : gload2(a.hcur, orow);
+            const double2 hcur = s1 ? hc : s4 ? make_double2(0.0, 0.0) : gload2(a.hcur, orow);
             for (int jj = 0; jj < cj; ++jj) {
                 const size_t jo = (size_t)(j0 + jj) * a.stride;
                 const double kap = DIFF ? a.kappa[j0 + jj] : 0.0;
-                const glb_bytes_t pG = (glb_bytes_t)(a.pphi + jo);
-                const uint32_t ldsP = ldsH + (uint32_t)(1 + jj) * (uint32_t)mC * rowB;
-                uint32_t ap[ME_];
-                v4u_t rp[ME_];
-#pragma unroll
-                for (int i = 0; i < ME_; ++i) ap[i] = ldsP + aoff[i];
-                lds_burst<ME_>(rp, ap);
-                const double2 pc = reinterpret_cast<const double2 *>(sRows + ((size_t)(1 + jj) * mC + ci) * K)[l];
-                double2 t = make_double2(0.0, 0.0);
                 double2 pp[ME_];
-#pragma unroll
-                for (int i = 0; i < ME_; ++i) {
-                    pp[i] = __builtin_bit_cast(double2, rp[i]);
-                    if (!ch[i]) pp[i] = glb_row2(pG + gh[i]);
-                }
+                tracer_gather<ME_>(P, 1 + jj, a.pphi + jo, ch, aoff, gh, pp);
+                const double2 pc = tracer_own_row(P, 1 + jj, ci);
+                double2 t = make_double2(0.0, 0.0);
                 const double kap4 = BIH ? a.kappa4[j0 + jj] : 0.0;
                 const bool b4 = BIH && kap4 != 0.0;             // wave-uniform
                 double2 ll[BIH ? ME_ : 1], lc = make_double2(0.0, 0.0);
-                if (BIH) {
+                if constexpr (BIH) {
 #pragma unroll
                     for (int i = 0; i < ME_; ++i) ll[i] = make_double2(0.0, 0.0);
                     if (b4) {                                   // L gathered as pphi is, from its own row set
-                        const glb_bytes_t lG = (glb_bytes_t)(a.lap + jo);
-                        const uint32_t ldsL = ldsH + (uint32_t)(1 + chunk + jj) * (uint32_t)mC * rowB;
-                        uint32_t al[ME_];
-                        v4u_t rl[ME_];
-#pragma unroll
-                        for (int i = 0; i < ME_; ++i) al[i] = ldsL + aoff[i];
-                        lds_burst<ME_>(rl, al);
-                        lc = reinterpret_cast<const double2 *>(sRows + ((size_t)(1 + chunk + jj) * mC + ci) * K)[l];
-#pragma unroll
-                        for (int i = 0; i < ME_; ++i) {
-                            ll[i] = __builtin_bit_cast(double2, rl[i]);
-                            if (!ch[i]) ll[i] = glb_row2(lG + gh[i]);
-                        }
+                        tracer_gather<ME_>(P, 1 + chunk + jj, a.lap + jo, ch, aoff, gh, ll);
+                        lc = tracer_own_row(P, 1 + chunk + jj, ci);
                     }
                 }
 #pragma unroll
                 for (int i = 0; i < ME_; ++i) {
                     const double ex = 0.5 * (pc.x + pp[i].x), ey = 0.5 * (pc.y + pp[i].y);
                     double tx = t.x + ((F[i].x * ex) * sd[i]) * invA, ty = t.y + ((F[i].y * ey) * sd[i]) * invA;
-                    if (DIFF) {
+                    if constexpr (DIFF) {
                         tx += (((kap * hE[i].x) * (pp[i].x - pc.x)) * dd[i]) * invA;
                         ty += (((kap * hE[i].y) * (pp[i].y - pc.y)) * dd[i]) * invA;
                     }
-                    if (BIH)
+                    if constexpr (BIH)
                         if (b4) {
                             tx -= (((kap4 * hE[i].x) * (ll[i].x - lc.x)) * dd[i]) * invA;
                             ty -= (((kap4 * hE[i].y) * (ll[i].y - lc.y)) * dd[i]) * invA;
@@ -314,12 +209,6 @@ __global__ __launch_bounds__(TR_NT, 2) void k_tracer_patch(const MeshDev m, cons
     }
 }
 
-static inline size_t tracer_patch_lds(const MeshDev &m, int chunk, bool diff, bool bih)
-{
-    return (size_t)(1 + (bih ? 2 : 1) * chunk) * m.maxOwnC * m.K * 8 + (size_t)m.maxOwnC * (m.ME + 1) * 8 +
-           (size_t)m.maxOwnC * (m.CI + m.ME) * 4 + (diff ? (size_t)m.maxOwnC * m.ME * 8 : 0);
-}
-
 TracerKernel tracer_kernel(const MeshDev &m, int lpc, int nT, bool generic, bool diff, bool bih)
 {
     if (!generic && lpc == 64 && m.K >= 34 && m.K <= 64 && !(m.K & 1) && m.ME == 6 && m.cRec && m.maxOwnC > 0) {
@@ -334,29 +223,10 @@ TracerKernel tracer_kernel(const MeshDev &m, int lpc, int nT, bool generic, bool
     return {2, 0, 0};
 }
 
-template <int LPC, bool DIFF, bool SRC, bool BIH>
-static hipError_t launch_tracer_cell(const MeshDev &m, const TracerArgs &a, hipStream_t s)
-{
-    const int ng = BLOCK / LPC;
-    const int grid = std::min(std::max((m.nC + ng - 1) / ng, 1), 65536);
-    hipLaunchKernelGGL((k_tracer_cell<LPC, DIFF, SRC, BIH>), dim3(grid), dim3(BLOCK), 0, s, m, a);
-    return hipGetLastError();
-}
-
-template <bool DIFF, bool SRC, bool BIH>
-static hipError_t launch_tracer_patch(const MeshDev &m, const TracerArgs &a, const TracerKernel &k, hipStream_t s)
-{
-    if (k.lds > 64 * 1024)
-        if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_tracer_patch<6, DIFF, SRC, BIH>)}, 80 * 1024); e != hipSuccess)
-            return e;
-    hipLaunchKernelGGL((k_tracer_patch<6, DIFF, SRC, BIH>), dim3(patch_grid(m)), dim3(TR_NT), k.lds, s, m, a, k.chunk);
-    return hipGetLastError();
-}
-
 template <bool DIFF, bool SRC, bool BIH>
 static hipError_t launch_tracer_generic(const MeshDev &m, const TracerArgs &a, int lpc, hipStream_t s)
 {
-#define CALL(L) launch_tracer_cell<L, DIFF, SRC, BIH>(m, a, s)
+#define CALL(L) launch_tracer_cell_form(k_tracer_cell<L, DIFF, SRC, BIH>, L, m, a, s)
     DISPATCH_LPC(lpc, CALL)
 #undef CALL
 }
@@ -367,15 +237,11 @@ hipError_t launch_tracers(const MeshDev &m, const TracerArgs &a, int lpc, bool g
     const bool diff = a.kappa != nullptr;       // (then a.dvdc is set too: tracer_stage)
     const bool src = a.src != nullptr;          // (some tracer of the state has a source: tracer_stage)
     const bool bih = a.kappa4 != nullptr;       // (then a.lap, a.kappa and a.dvdc are set too: tracer_stage)
-    if (bih && !diff) return hipErrorInvalidValue;      // BIH instantiates only together with DIFF
     const TracerKernel k = tracer_kernel(m, lpc, a.nT, generic, diff, bih);
-#define PICK(F, ...)                                                                                          \
-    (bih    ? (src ? F<true, true, true>(__VA_ARGS__) : F<true, false, true>(__VA_ARGS__))                      \
-     : diff ? (src ? F<true, true, false>(__VA_ARGS__) : F<true, false, false>(__VA_ARGS__))                    \
-            : (src ? F<false, true, false>(__VA_ARGS__) : F<false, false, false>(__VA_ARGS__)))
-    if (k.form == 1) return PICK(launch_tracer_patch, m, a, k, s);
-    return PICK(launch_tracer_generic, m, a, lpc, s);
-#undef PICK
+    return pick_tracer_instance(diff, src, bih, [&](auto D, auto S, auto B) {
+        if (k.form == 1) return launch_tracer_patch_form(k_tracer_patch<6, D.value, S.value, B.value>, m, a, k, s);
+        return launch_tracer_generic<D.value, S.value, B.value>(m, a, lpc, s);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -425,51 +291,31 @@ __global__ __launch_bounds__(BLOCK) void k_tracer_lap_cell(const MeshDev m, cons
     }
 }
 
-// Patch form: k_tracer_patch's shape and LDS layout with dvdc where that one keeps sdv -- the patch's cRec records, dvdc, invArea and
-// maxLevelEdgeTop entries, the ph rows and the x rows of `chunk` fields of its own cells in LDS; neighbours' rows in one burst, foreign
-// rows by masked global loads at 32-bit byte offsets.  Fields with kappa4 == 0 are not staged, not gathered, not written.
+// Patch form: k_tracer_patch's shape and LDS layout (tracer_patch.hpp) with dvdc where that one keeps sdv -- the patch's cRec records, dvdc,
+// invArea and maxLevelEdgeTop entries, the ph rows and the x rows of `chunk` fields of its own cells in LDS; neighbours' rows in one burst,
+// foreign rows by masked global loads at 32-bit byte offsets.  Fields with kappa4 == 0 are not staged, not gathered, not written.
 template <int ME_>
 __global__ __launch_bounds__(TR_NT, 2) void k_tracer_lap_patch(const MeshDev m, const TracerLapArgs a, const int chunk)
 {
-    constexpr int NG = TR_NT / 32;
     static_assert(ME_ == 6, "burst width");
     extern __shared__ __align__(16) unsigned char trl_smem[];
-    const int tid = threadIdx.x, grp = tid >> 5, l = tid & 31, K = m.K, CI = m.CI, mC = m.maxOwnC;
-    const bool act = 2 * l < K;
-    const unsigned rowB = (unsigned)K * 8u, lo = (unsigned)l * 16u;
-    double *sRows = reinterpret_cast<double *>(trl_smem);                   // [1 + chunk][maxOwnC][K]  ph rows, then x rows per field
-    double *sDd = sRows + (size_t)(1 + chunk) * mC * K;                     // [maxOwnC][ME]  dvdc
-    double *sIa = sDd + (size_t)mC * ME_;                                   // [maxOwnC]      invArea
-    uint32_t *sRec = reinterpret_cast<uint32_t *>(sIa + mC);                // [maxOwnC][CI]  cRec
-    int *sMl = reinterpret_cast<int *>(sRec + (size_t)mC * CI);             // [maxOwnC][ME]  maxLevelEdgeTop of the slot's edge
     const int pl_ = patch_of_block(m.nPatches);
     if (pl_ >= m.nPatches) return;
-    const int p = pl_ + m.patchBegin;
-    const int c0 = m.patchCellStart[p], nc = m.patchCellStart[p + 1] - c0;
-    const unsigned ownB = (unsigned)c0 * rowB, ownN = (unsigned)nc * rowB;
-    const glb_bytes_t hG = (glb_bytes_t)a.ph;
-    const uint32_t ldsH = (uint32_t)(size_t)sRows + lo;
+    const TracerPatch P = tracer_patch_open<ME_>(m, trl_smem, pl_, 1 + chunk, false, true);
+    const int tid = P.tid, c0 = P.c0, nc = P.nc;
 
-    // row set ty of the cache (0 = ph, 1 + jj = field j0 + jj) from global memory, the patch's own cells
-    auto stage_set = [&](int ty, const double *base) {
-        if (!act) return;
-        const char *src = reinterpret_cast<const char *>(base);
-        double *dst = sRows + (size_t)ty * mC * K;
-        for (int ci = grp; ci < nc; ci += NG)
-            reinterpret_cast<double2 *>(dst + (size_t)ci * K)[l] = *reinterpret_cast<const double2 *>(src + (ownB + (unsigned)ci * rowB + lo));
-    };
     auto stage_fields = [&](int j0, int cj) {
         for (int jj = 0; jj < cj; ++jj)
-            if (a.kappa4[j0 + jj] != 0.0) stage_set(1 + jj, a.x + (size_t)(j0 + jj) * a.stride);
+            if (a.kappa4[j0 + jj] != 0.0) tracer_stage_set(P, 1 + jj, a.x + (size_t)(j0 + jj) * a.stride);
     };
 
     {
-        const int nRec = nc * CI, nSd = nc * ME_;
-        stage_set(0, a.ph);
+        const int nRec = nc * P.CI, nSd = nc * ME_;
+        tracer_stage_set(P, 0, a.ph);
         stage_fields(0, min(chunk, a.nT));
-        for (int i = tid; i < nRec; i += TR_NT) sRec[i] = m.cRec[(size_t)c0 * CI + i];
-        for (int i = tid; i < nSd; i += TR_NT) { sDd[i] = a.dvdc[(size_t)c0 * ME_ + i]; sMl[i] = m.mltc[(size_t)c0 * ME_ + i]; }
-        for (int i = tid; i < nc; i += TR_NT) sIa[i] = m.invArea[c0 + i];
+        for (int i = tid; i < nRec; i += TR_NT) P.rec[i] = m.cRec[(size_t)c0 * P.CI + i];
+        for (int i = tid; i < nSd; i += TR_NT) { P.dd[i] = a.dvdc[(size_t)c0 * ME_ + i]; P.ml[i] = m.mltc[(size_t)c0 * ME_ + i]; }
+        for (int i = tid; i < nc; i += TR_NT) P.ia[i] = m.invArea[c0 + i];
     }
     for (int j0 = 0; j0 < a.nT; j0 += chunk) {
         const int cj = min(chunk, a.nT - j0);
@@ -478,59 +324,31 @@ __global__ __launch_bounds__(TR_NT, 2) void k_tracer_lap_patch(const MeshDev m, 
             stage_fields(j0, cj);
         }
         __syncthreads();
-        if (!act) continue;
-        for (int ci = grp; ci < nc; ci += NG) {
-            const uint32_t *rec = sRec + (size_t)ci * CI;
-            const unsigned mask = rec[2 * ME_];
+        if (!P.act) continue;
+        for (int ci = P.grp; ci < nc; ci += TR_NG) {
+            const uint32_t *rec = P.rec + (size_t)ci * P.CI;
             double2 hE[ME_];
             bool ch[ME_], okx[ME_], oky[ME_];
             uint32_t aoff[ME_], gh[ME_];
-            const double2 hc = reinterpret_cast<const double2 *>(sRows + (size_t)ci * K)[l];
+            const double2 hc = tracer_own_row(P, 0, ci);
             {
-                uint32_t ah[ME_];
-                v4u_t rh[ME_];
+                double2 hh[ME_];
+                tracer_slots<ME_>(P, rec, ch, aoff, gh);
+                tracer_gather<ME_>(P, 0, a.ph, ch, aoff, gh, hh);
+                tracer_level_masks<ME_>(P, ci, rec[2 * ME_], okx, oky);
 #pragma unroll
-                for (int i = 0; i < ME_; ++i) {        // cached row or row 0 of the cache (then overwritten by the masked global load)
-                    const unsigned ho = rec[ME_ + i], loc = ho - ownB;
-                    ch[i] = loc < ownN;
-                    aoff[i] = ch[i] ? loc : 0u;
-                    gh[i] = ho + lo;
-                    asm("" : "+v"(gh[i]));             // the offset stays in a VGPR (see k_nl_prep5)
-                    ah[i] = ldsH + aoff[i];
-                }
-                lds_burst<ME_>(rh, ah);
-#pragma unroll
-                for (int i = 0; i < ME_; ++i) {
-                    double2 hh = __builtin_bit_cast(double2, rh[i]);
-                    if (!ch[i]) hh = glb_row2(hG + gh[i]);
-                    hE[i] = make_double2(0.5 * (hc.x + hh.x), 0.5 * (hc.y + hh.y));
-                    const int ml = sMl[ci * ME_ + i];
-                    const bool valid = (mask >> i) & 1u;
-                    okx[i] = valid && 2 * l < ml;
-                    oky[i] = valid && 2 * l + 1 < ml;
-                }
+                for (int i = 0; i < ME_; ++i) hE[i] = make_double2(0.5 * (hc.x + hh[i].x), 0.5 * (hc.y + hh[i].y));
             }
-            const double *dd = sDd + ci * ME_;
-            const double invA = sIa[ci];
-            const unsigned orow = ownB + (unsigned)ci * rowB + lo;       // the cell's own row in every (K, nC) array
+            const double *dd = P.dd + ci * ME_;
+            const double invA = P.ia[ci];
+            const unsigned orow = P.ownB + (unsigned)ci * P.rowB + P.lo;       // the cell's own row in every (K, nC) array
             for (int jj = 0; jj < cj; ++jj) {
                 if (a.kappa4[j0 + jj] == 0.0) continue;                  // wave-uniform
                 const size_t jo = (size_t)(j0 + jj) * a.stride;
-                const glb_bytes_t xG = (glb_bytes_t)(a.x + jo);
-                const uint32_t ldsX = ldsH + (uint32_t)(1 + jj) * (uint32_t)mC * rowB;
-                uint32_t ap[ME_];
-                v4u_t rp[ME_];
-#pragma unroll
-                for (int i = 0; i < ME_; ++i) ap[i] = ldsX + aoff[i];
-                lds_burst<ME_>(rp, ap);
-                const double2 xc = reinterpret_cast<const double2 *>(sRows + ((size_t)(1 + jj) * mC + ci) * K)[l];
-                double2 s = make_double2(0.0, 0.0);
                 double2 xx[ME_];
-#pragma unroll
-                for (int i = 0; i < ME_; ++i) {
-                    xx[i] = __builtin_bit_cast(double2, rp[i]);
-                    if (!ch[i]) xx[i] = glb_row2(xG + gh[i]);
-                }
+                tracer_gather<ME_>(P, 1 + jj, a.x + jo, ch, aoff, gh, xx);
+                const double2 xc = tracer_own_row(P, 1 + jj, ci);
+                double2 s = make_double2(0.0, 0.0);
 #pragma unroll
                 for (int i = 0; i < ME_; ++i) {
                     const double sx = s.x + (hE[i].x * (xx[i].x - xc.x)) * dd[i], sy = s.y + (hE[i].y * (xx[i].y - xc.y)) * dd[i];
@@ -543,31 +361,13 @@ __global__ __launch_bounds__(TR_NT, 2) void k_tracer_lap_patch(const MeshDev m, 
     }
 }
 
-TracerKernel tracer_lap_kernel(const MeshDev &m, int lpc, int nT, bool generic)
-{
-    return tracer_kernel(m, lpc, nT, generic, false, false);
-}
-
-template <int LPC>
-static hipError_t launch_tracer_lap_cell(const MeshDev &m, const TracerLapArgs &a, hipStream_t s)
-{
-    const int ng = BLOCK / LPC;
-    const int grid = std::min(std::max((m.nC + ng - 1) / ng, 1), 65536);
-    hipLaunchKernelGGL((k_tracer_lap_cell<LPC>), dim3(grid), dim3(BLOCK), 0, s, m, a);
-    return hipGetLastError();
-}
-
 hipError_t launch_tracer_lap(const MeshDev &m, const TracerLapArgs &a, int lpc, bool generic, hipStream_t s)
 {
     if (a.nT <= 0) return hipSuccess;
-    const TracerKernel k = tracer_lap_kernel(m, lpc, a.nT, generic);
-    if (k.form == 1) {
-        if (k.lds > 64 * 1024)
-            if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_tracer_lap_patch<6>)}, 80 * 1024); e != hipSuccess) return e;
-        hipLaunchKernelGGL((k_tracer_lap_patch<6>), dim3(patch_grid(m)), dim3(TR_NT), k.lds, s, m, a, k.chunk);
-        return hipGetLastError();
-    }
-#define CALL(L) launch_tracer_lap_cell<L>(m, a, s)
+    // k_tracer_patch's layout without the harmonic extras (dvdc takes the place of sdv): the size and the chunk of the plain tracer kernel
+    const TracerKernel k = tracer_kernel(m, lpc, a.nT, generic, false, false);
+    if (k.form == 1) return launch_tracer_patch_form(k_tracer_lap_patch<6>, m, a, k, s);
+#define CALL(L) launch_tracer_cell_form(k_tracer_lap_cell<L>, L, m, a, s)
     DISPATCH_LPC(lpc, CALL)
 #undef CALL
 }

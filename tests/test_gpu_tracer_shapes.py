@@ -6,18 +6,20 @@ Every case gives its tracers pairwise distinct fields and, with diffusion on, pa
 (a tracer taken for its neighbour three or four places on cannot pass), compares both time levels of every tracer after an eager
 step and after mk.run_steps, and asserts Tracers.path() plus whatever else proves that the lines named below ran:
 
-  k_tracer_cell, j0 > 0: second and third tracer group, partial tail, (j0 + jj) * stride (lines 44-79)   test_generic_form_tracer_groups
-  k_tracer_cell<2>, <16>, <32>; K = 33 (64 lanes, generic); K = 130 (three levels a lane) (lines 36-41)  test_generic_form_lane_widths
-  k_tracer_patch's tail loops after the register-staged records, the LDS carve for maxOwnC != 16,
-      chunk == 1 and 2 with three tracers (lines 102-107, 157-160, 163-168)                              test_patch_form_patch_sizes
-  tracer_kernel at its 80 KB boundary, both ways (lines 262-270)                                         test_form_flips_with_diffusion_at_the_lds_boundary,
+  k_tracer_cell's j0 loop, j0 > 0: second and third tracer group, partial tail, (j0 + jj) * stride       test_generic_form_tracer_groups
+  k_tracer_cell<2>, <16>, <32>; K = 33 (64 lanes, generic); K = 130 (three levels a lane of its k loop)  test_generic_form_lane_widths
+  the tail loops of tracer_stage_records (tracer_patch.hpp) after the register-staged records, the LDS
+      carve of tracer_patch_open for maxOwnC != 16, k_tracer_patch's pass loop with chunk == 1 and 2
+      and three tracers                                                                                  test_patch_form_patch_sizes
+  tracer_kernel at its 80 KB boundary, both ways                                                         test_form_flips_with_diffusion_at_the_lds_boundary,
                                                                                                          test_patches_too_large_for_the_patch_form
   moka_tracer_upload / _download through put_rows / get_rows in other cell orders                        test_tracers_in_other_cell_orders
-  every ch[i] a cache hit, one neighbour through several slots (lines 184-191, 227-230)                  test_tiny_periodic_meshes
+  every ch[i] of tracer_slots a cache hit (tracer_gather takes no masked load), one neighbour through
+      several slots                                                                                      test_tiny_periodic_meshes
   moka_set_tracers on a state that has stepped; 3 -> 9 -> 1 tracers (api.hip)                            test_late_and_changing_tracers
   the stage weights, on the device                                                                       test_plane_wave_on_the_device
 
-Left alone: the invArea tail loop (line 161) needs more than 256 cells in a patch, and 257 * (16 * 34 + 144) bytes are above the 80 KB
+Left alone: the invArea tail loop of tracer_stage_records needs more than 256 cells in a patch, and 257 * (16 * 34 + 144) bytes are above the 80 KB
 the patch form may take, so no mesh reaches it."""
 import numpy as np
 import pytest
@@ -61,7 +63,7 @@ def step_and_check(md, tr, ref, nsteps, n=None, first=0):
 @pytest.mark.parametrize("meshname,K,partial,variant,nsteps", [("ico12f", 5, False, 0, 7), ("ico16", 66, False, 0, 3),
                                                                  ("ico16", 60, True, 3, 3)])
 def test_generic_form_tracer_groups(backend, meshname, K, partial, variant, nsteps, nT, diff):
-    """More tracers than the TR_TJ = 4 a lane of k_tracer_cell carries at once: the j0 loop (tracers.hip 44-79) takes a second group
+    """More tracers than the TR_TJ = 4 a lane of k_tracer_cell carries at once: the j0 loop of k_tracer_cell takes a second group
     (nT = 5: a tail of one; 8: a full one) and a third (9: a tail of one behind two full groups), so `(j0 + jj) * stride` addresses
     rows beyond the first group and `jj < nj` masks a tail with j0 > 0 -- with and without DIFF, with 8 (heptagons), 64 lanes and
     with a partial edge mask under variant 3.  Nine distinct fields and diffusivities; the twin of the nine serves every nT.  The
@@ -83,7 +85,7 @@ def test_generic_form_tracer_groups(backend, meshname, K, partial, variant, nste
 def test_generic_form_lane_widths(backend, meshname, K, lpc, partial, diff):
     """The instantiations of k_tracer_cell no other test launches: 2, 16 and 32 lanes per column (NG = 128, 16, 8 cells a block;
     K = 12 and 17 leave lanes of the group idle, K = 32 none), K = 33 -- the first K with 64 lanes, odd and below 34, so the generic
-    form although lpc == 64 -- and K = 130, where `k += LPC` (line 41) gives a lane a third level.  Five tracers (two groups), one
+    form although lpc == 64 -- and K = 130, where the level loop's `k += LPC` gives a lane a third level.  Five tracers (two groups), one
     case with the partial edge mask; 7 steps."""
     ref = tc.reference(meshname, K, "linear", partial, ((7, (5, 21, False), diff),))
     md = tc.Model(backend, meshname, K, partial=partial)
@@ -103,10 +105,10 @@ def test_generic_form_lane_widths(backend, meshname, K, lpc, partial, diff):
 @pytest.mark.parametrize("meshname,K", [("planar", 64), ("ico16", 60)])
 def test_patch_form_patch_sizes(backend, meshname, K, patch_cells, partial, mode, diff):
     """k_tracer_patch with patches of 12, 24 and 48 cells instead of the default 16, where nRec = 256 = TR_NT exactly and every tail
-    loop behind the register-staged record phase is empty.  24 cells: nRec = 384, the sRec tail (line 157) runs; 48 cells: nSd = 288,
-    the sSd / sMl (158) and sDd (160) tails run too; 12 cells: nRec < TR_NT, the guards `tid < nRec` cut.  sSd, sDd, sIa, sRec and
-    sMl (102-107) all move with maxOwnC, and the last patch is short (360 and 2562 cells).  Three tracers: at 48 cells the 80 KB
-    hold one (diffused) or two (plain) tracers' rows beside the thickness rows, so the pass loop (163-168) re-stages rows once or
+    loop behind the register-staged record phase is empty.  24 cells: nRec = 384, the cRec tail loop of tracer_stage_records runs; 48 cells: nSd = 288,
+    its sdv / maxLevelEdgeTop and dvdc tail loops run too; 12 cells: nRec < TR_NT, the guards `tid < nRec` cut.  the sd, dd, ia, rec and
+    ml arrays (the carve of tracer_patch_open) all move with maxOwnC, and the last patch is short (360 and 2562 cells).  Three tracers: at 48 cells the 80 KB
+    hold one (diffused) or two (plain) tracers' rows beside the thickness rows, so k_tracer_patch's pass loop re-stages rows once or
     twice, where the only multi-pass case so far was 8 + 1.  Full masks over the linear dycore and partial masks under Del2 + Del4.
     7 steps over the linear dycore, 3 under Del2 + Del4 on the sphere (that twin's cost).  ico32 at K = 34 is left out: its twin alone
     takes longer than this whole file."""
@@ -134,7 +136,7 @@ def test_patch_form_patch_sizes(backend, meshname, K, patch_cells, partial, mode
 
 
 def test_form_flips_with_diffusion_at_the_lds_boundary(backend):
-    """tracer_kernel (262-270) refuses the patch form when maxOwnC * (16 K + 144 + 48 diff) exceeds 80 KB.  At K = 64 patches of 70
+    """tracer_kernel refuses the patch form when maxOwnC * (16 K + 144 + 48 diff) exceeds 80 KB.  At K = 64 patches of 70
     cells take 70 * 1168 = 81 760 <= 81 920 bytes without diffusion (the largest dynamic LDS the kernel is ever launched with) and
     70 * 1216 = 85 120 with it: the default variant runs the patch form, the generic form once a diffusivity is set, and the patch
     form again after set_diffusivity(0).  Three segments of an eager step and a run of one, each bitwise against the twin's."""
@@ -206,7 +208,7 @@ def test_tracers_in_other_cell_orders(backend, meshname, K, order, diff):
 @pytest.mark.parametrize("nx,ny,K", tc.TINY)
 def test_tiny_periodic_meshes(backend, nx, ny, K):
     """The doubly periodic meshes of test_gpu_parity.py's test_tiny_periodic_meshes_bitwise: a cell meets the same neighbour through
-    several slots, and one patch holds the whole mesh (4 x 4, 2 x 4 at K = 60: 16 and 8 cells), so every ch[i] (186) is a cache hit
+    several slots, and one patch holds the whole mesh (4 x 4, 2 x 4 at K = 60: 16 and 8 cells), so every ch[i] of tracer_slots is a cache hit
     and `loc` ranges over all of ownN; 6 x 4 at K = 34 has a short second patch.  K = 1 and 8: the generic form.  Three diffused
     tracers, the first one 1 everywhere: it stays exactly 1.0.  (The twins' tendencies on these meshes: the CPU tests.)"""
     name = f"tiny-{nx}-{ny}"
