@@ -82,7 +82,11 @@ typedef struct moka_mesh_desc {
     const int32_t *edgeSignOnVertex;                 /* (edgeSignOnVertexLD, nVertices) :313    */
     const double  *areaTriangle;                     /* (nVertices)                             */
     /* VerticalMesh */
-    const int32_t *maxLevelEdgeTop;                  /* (opt) (nEdges); NULL -> all ones (VertMesh.jl:32) */
+    const int32_t *maxLevelEdgeTop;                  /* (opt) (nEdges); NULL -> all ones (VertMesh.jl:32).  Skipped means
+                                                      * never read: normalVelocity, tracers and adjoint seeds at levels no active
+                                                      * element reads may hold anything (NaN, infinities: fill values below the
+                                                      * sea floor) and never reach an active element (tests/test_gpu_poison.py);
+                                                      * layerThickness must be finite on every level (ssh sums all of them) */
     const double  *restingThicknessSum;              /* (nCells) (VertMesh.jl:73,100)           */
     /* layout controls */
     int32_t ordering;                                /* moka_ordering                            */

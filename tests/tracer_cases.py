@@ -91,15 +91,18 @@ def viscosities(mesh, dtv):
     return 0.01 * dcmin ** 2 / dtv, 0.002 * dcmin ** 4 / dtv
 
 
-def oracle_mesh(meshname, K, partial):
+def oracle_mesh(meshname, K, partial, mlt=None):
+    """mlt: a maxLevelEdgeTop array of the caller's (it replaces both `partial` and the full columns)."""
     mesh = get_mesh(meshname)
     rest = state_of(meshname, K)[3]
-    return orc.OracleMesh(mesh, K, resting_thickness_sum=rest.sum(1), max_level_edge_top=partial_mlt(mesh, K) if partial else K)
+    if mlt is None:
+        mlt = partial_mlt(mesh, K) if partial else K
+    return orc.OracleMesh(mesh, K, resting_thickness_sum=rest.sum(1), max_level_edge_top=mlt)
 
 
-def twin_of(meshname, K, mode="linear", partial=False):
+def twin_of(meshname, K, mode="linear", partial=False, mlt=None):
     """A TracerDiffusionTwin (kappa = 0 is TracerTwin bit for bit: test_tracer_diffusion_twin.py) over the dycore base `mode`."""
-    mesh, om = get_mesh(meshname), oracle_mesh(meshname, K, partial)
+    mesh, om = get_mesh(meshname), oracle_mesh(meshname, K, partial, mlt)
     base = om
     if mode == "del2+del4":
         v2, v4 = viscosities(mesh, dt_of(meshname))
@@ -138,10 +141,11 @@ def reference(meshname, K, mode, partial, schedule):
 
 class Model:
     """A model on the device through the C ABI's mesh descriptor, so that every option of it can be set: a partial edge mask, the
-    cell ordering, patch_cells, a cell class per cell; `state` = (ssh, u, h, rest) replaces the random state of the case."""
+    cell ordering, patch_cells, a cell class per cell; `state` = (ssh, u, h, rest) replaces the random state of the case; `mlt` = a
+    maxLevelEdgeTop array of the caller's (it replaces `partial`); state_bytes = 4: the fp32-storage state."""
 
     def __init__(self, backend, meshname, K, mode="linear", partial=False, variant=0, ordering=L.ORDER_DEFAULT, patch_cells=0,
-                 cell_class=None, state=None):
+                 cell_class=None, state=None, mlt=None, state_bytes=8):
         import moka_hip as mk
         from moka_hip import api
         self.mk, self.backend = mk, backend
@@ -151,12 +155,14 @@ class Model:
         backend.set_kernel_variant(variant)
         hm = mk.HorzMesh(mesh)
         vm = mk.VerticalMesh(hm, nVertLevels=K, restingThickness=self.rest, multilayer=True)
-        if partial:
+        if mlt is not None:
+            vm.maxLevelEdge.Top[:] = mlt
+        elif partial:
             vm.maxLevelEdge.Top[:] = partial_mlt(mesh, K)
         self.M = M = mk.Mesh(hm, vm)                       # no backend yet: the descriptor below takes the options Mesh() lacks
-        M.backend = backend
+        M.backend, M.state_bytes = backend, int(state_bytes)
         desc, self._keep = L.make_desc(mesh, K, vm.restingThicknessSum, vm.maxLevelEdge.Top, ordering, patch_cells,
-                                       cell_class=cell_class)
+                                       cell_class=cell_class, state_bytes=state_bytes)
         L.check(L.lib().moka_mesh_create(backend._h, C.byref(desc), C.byref(M._h)), backend._h)
         api._own(M, L.lib().moka_mesh_destroy, M._h, backend)
         self.info = M.info()
