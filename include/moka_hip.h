@@ -214,7 +214,8 @@ int moka_curl_on_vertex_jvp(moka_mesh *mesh, const double *dVecEdge, double *dCu
 /* A mesh created with stateBytes = 4 yields an fp32-STORAGE state: host arrays stay double (upload rounds to fp32,
  * download widens); moka_tendencies / moka_step_rk4 / moka_step_fe / moka_run / moka_sum_sq / the halo API work on it.
  * moka_step_fe steps all levels of a whole mesh (no MOKA_FE_LEVEL1_ONLY; on a partitioned mesh: moka_fe_dist_step).  DiagnosticVars come out of
- * Forward-Euler steps only: after an RK4 step they are unavailable (MOKA_ERR_UNSUPPORTED on download), and the next
+ * Forward-Euler steps only: after an RK4 step they are unavailable (MOKA_ERR_UNSUPPORTED on download, moka_sum_sq and upload of a
+ * DiagnosticVars field; the state is unchanged), and the next
  * Forward-Euler step must carry none over (flags 0).  The piecewise calls (moka_diagnostic_compute, moka_compute_*_tendency,
  * moka_advance_time_levels with level-1-only flags) stay Float64-only.  Needs nVertLevels % 4 == 0 and <= 128. */
 int  moka_state_create(moka_ctx *ctx, moka_mesh *mesh, moka_state **out);
@@ -494,7 +495,11 @@ int moka_fe_lazy_pending(const moka_state *st);
  * SURVEY.md N4).  on = 1 switches moka_tendencies / moka_step_rk4 / moka_run(RK4) of this state to the
  * vector-invariant TRiSK form (Ringler et al. 2010):  q = (fVertex + zeta)/h_vertex at vertices, averaged to edges;
  *   tendU = sum_i w[i,e] F[eoe_i] (q_e + q_eoe_i)/2 - g grad(ssh) - grad(KE),  KE = sum_e dc dv u^2 / (4 areaCell).
- * Default off.  Needs the optional mesh arrays above; Float64 states on whole meshes; no Forward Euler, no tape. */
+ * Default off.  Needs the optional mesh arrays above; Float64 states on whole meshes; no Forward Euler, no tape: on = 1 is
+ * MOKA_ERR_UNSUPPORTED while a moka_tape of the state exists, as moka_tape_create is on a nonlinear state.
+ * Order of calls: the toggles below and this one take effect with the next tendency evaluation.  What a finished step left in
+ * TendencyVars (also where it is produced on the first read) was computed with the terms and coefficients in force during that
+ * step, whatever is switched afterwards. */
 int  moka_set_nonlinear(moka_state *st, int on);
 /* Del2 momentum mixing on top of the nonlinear terms -- the reference's sketch (never called there, and not runnable:
  * src/ocn/Tendencies/normalVelocity/horizontal_momentum_mixing.jl:53-80, with viscDel2 hard-wired to 1.0 at :30):

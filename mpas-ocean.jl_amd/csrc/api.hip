@@ -1663,9 +1663,18 @@ int moka_last_fe_path(const moka_state *st) { return st ? st->feFast : -1; }
 int moka_set_nonlinear(moka_state *st, int on)
 {
     if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
-    if (!on) { st->nonlinear = false; return MOKA_OK; }
+    if (!on) {
+        if (st->nonlinear) {           // the stage-4 tendencies an RK4 step left pending belong to the terms they were computed with
+            HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+            if (int rc = flush_lazy(st, false, true)) return rc;
+        }
+        st->nonlinear = false;
+        return MOKA_OK;
+    }
     const Plan &p = st->mesh->plan;
     if (st->f32) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "nonlinear terms: Float64 states only");
+    if (st->dycoreTapes > 0)
+        return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "nonlinear terms: not while a moka_tape of this state exists (reverse mode covers the linear terms only)");
     if (!p.nlOk)
         return fail(st->ctx, MOKA_ERR_UNSUPPORTED,
                     "nonlinear terms need kiteAreasOnVertex, fVertex, verticesOnEdge and cellsOnVertex in the mesh descriptor");
@@ -1689,10 +1698,12 @@ int moka_set_viscosity_del2(moka_state *st, double viscDel2)
     if (!(viscDel2 >= 0.0)) return fail(st->ctx, MOKA_ERR_ARG, "viscDel2 must be >= 0");
     if (viscDel2 != 0.0 && !st->nonlinear)
         return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "Del2 mixing rides on the nonlinear tendencies: call moka_set_nonlinear first");
+    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    int rc;
+    // pending stage-4 tendencies belong to the coefficient they were computed with (as in moka_set_viscosity_del4)
+    if (viscDel2 != st->viscDel2 && (rc = flush_lazy(st, false, true))) return rc;
     if (viscDel2 != 0.0 && !st->nlZv) {
         const Plan &p = st->mesh->plan;
-        HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
-        int rc;
         if ((rc = alloc_field(st, &st->nlZv, (size_t)p.K * p.nV))) return rc;
         if ((rc = alloc_field(st, &st->nlDiv, (size_t)p.K * p.nC))) return rc;
     }
@@ -2486,6 +2497,7 @@ int moka_tape_create(moka_state *st, int64_t capacity_steps, moka_tape **out)
     HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));
     state_attach(st);
     t->counted = true;
+    ++st->dycoreTapes;
     *out = t;
     return MOKA_OK;
 }
@@ -2493,7 +2505,7 @@ int moka_tape_create(moka_state *st, int64_t capacity_steps, moka_tape **out)
 void moka_tape_destroy(moka_tape *t)
 {
     if (!t) return;
-    if (t->counted) state_detach(t->st);
+    if (t->counted) { state_detach(t->st); --t->st->dycoreTapes; }
     (void)hipSetDevice(t->st->ctx->device);
     if (t->st->lazyOwner == t) {        // the stage-4 tendencies of the last taped step would be produced from a slot of this tape
         if (t->st->tendDirty) (void)flush_lazy(t->st, false, true);

@@ -136,6 +136,7 @@ struct moka_state {
     // objects that hold or have exported the addresses of this state's arrays (halos, tapes): while any exists the arrays stay
     // where they are (moka_state_optimize_placement refuses)
     int attached = 0;
+    int dycoreTapes = 0;              // live moka_tape objects on this state (moka_set_nonlinear refuses while one exists)
     std::vector<moka_placement_trial> placementLog;   // what the last moka_state_optimize_placement tried
     int64_t placementLaunches = 0;                    // ... and how many stage launches it issued (measurement bookkeeping)
 };

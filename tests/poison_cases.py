@@ -29,6 +29,7 @@ import tracer_cases as tc
 import tracer_kgrad_twin as tk
 import tracer_source_twin as ts
 from del4_twin import Del4Twin, TwinState
+from masks import basin  # noqa: F401  (the mask of the docstring; tests name it poison_cases.basin)
 
 VALUES = {None: None, "nan": np.nan, "-inf": -np.inf}
 RINGS = {"linear": 1, "nonlinear": 2, "nonlinear+del2": 2, "del2+del4": 3}
@@ -42,15 +43,6 @@ def _cached(key, make):
 
 
 # ---- the mask and the sets ------------------------------------------------------------------------------------------------------------
-def basin(mesh, K):
-    if getattr(mesh, "on_sphere", False):
-        s = (1.0 + np.asarray(mesh.zEdge) / mesh.sphere_radius) / 2.0
-    else:
-        x = np.asarray(mesh.xEdge, dtype=np.float64)
-        s = (x - x.min()) / (x.max() - x.min())
-    return np.clip(np.rint(K * (1.3 * s - 0.15)), 0, K).astype(np.int32)
-
-
 def mask_of(meshname, K):
     return _cached(("mlt", meshname, K), lambda: basin(tc.get_mesh(meshname), K))
 
