@@ -174,7 +174,8 @@ enum {
     MOKA_PA_EOC = 0, MOKA_PA_COC, MOKA_PA_MLTC, MOKA_PA_SDV, MOKA_PA_INVAREA, MOKA_PA_AREACELL, MOKA_PA_RSUM,
     MOKA_PA_EHDR, MOKA_PA_EOE, MOKA_PA_WOE, MOKA_PA_GINVDC, MOKA_PA_DCEDGE, MOKA_PA_DVEDGE, MOKA_PA_FEDGE,
     MOKA_PA_EOV, MOKA_PA_CV, MOKA_PA_HALO_START, MOKA_PA_HALO_EDGE, MOKA_PA_LEOC, MOKA_PA_LEOE,
-    MOKA_PA_CREC, MOKA_PA_EREC, MOKA_PA_FEOE, MOKA_PA_PVSTART, MOKA_PA_PVLIST, MOKA_PA_LVOE
+    MOKA_PA_CREC, MOKA_PA_EREC, MOKA_PA_FEOE, MOKA_PA_PVSTART, MOKA_PA_PVLIST, MOKA_PA_LVOE,
+    MOKA_PA_NLEV     /* (nCells) int32: active depth of a cell, see moka_set_tracer_vertical_diffusion */
 };
 int  moka_plan_array(const moka_plan *plan, int which, const void **data, int64_t *count);
 
@@ -626,6 +627,50 @@ int  moka_tracer_source_upload(moka_state *st, int32_t j, const double *host);
 int  moka_tracer_source_download(moka_state *st, int32_t j, double *host);
 /* *out = 1 when tracer j has a source, else 0; MOKA_ERR_ARG for j out of range or a NULL out */
 int  moka_tracer_has_source(const moka_state *st, int32_t j, int *out);
+/* Implicit vertical diffusion (moka_set_tracer_vertical_diffusion; default off).  One coefficient kappaV_j >= 0 (m^2/s) per tracer.  After the
+ * RK4 step above has formed phi* = Qn / h_new (stage 4, unchanged), the step is split:
+ *   (h_new phi_new)[k] - dt d/dz(kappaV_j d/dz phi_new)[k] = (h_new phi*)[k]
+ * -- backward Euler in the vertical, unconditionally stable: layers are metres thick where cells are kilometres wide, and an explicit
+ * term would cap dt by h^2 / kappaV.
+ * Active depth.  nLev[c] = the maximum of maxLevelEdgeTop[e] over the non-empty slots of edgesOnCell, at most nVertLevels: exactly the
+ * levels at which some active element reads the cell (moka_plan_array: MOKA_PA_NLEV).  Levels k >= nLev[c] are neither read into
+ * arithmetic nor changed; a column with nLev[c] < 2 is left alone.
+ * Arithmetic.  For tracer j with kappaV_j != 0 and a column with n = nLev[c] >= 2, every operation below rounded once, nothing
+ * contracted; x[k] = phi*[k,c], h[k] = h_new[k,c], s = dt * kappaV_j:
+ *   w[k]  = s / (0.5 * (h[k] + h[k+1]))                         k = 0 .. n-2
+ *   d[0]  = h[0] + w[0];   d[k] = (h[k] + w[k-1]) + w[k];   d[n-1] = h[n-1] + w[n-2]
+ *   Lv(v)[0] = w[0]*(v[1]-v[0]);   Lv(v)[n-1] = w[n-2]*(v[n-2]-v[n-1])
+ *   Lv(v)[k] = w[k-1]*(v[k-1]-v[k]) + w[k]*(v[k+1]-v[k])        0 < k < n-1
+ *   Solve(r):  beta = d[0];  y[0] = r[0]/beta
+ *              k = 1..n-1:  g[k-1] = w[k-1]/beta;  beta = d[k] - w[k-1]*g[k-1];  y[k] = (r[k] + w[k-1]*y[k-1])/beta
+ *              z[n-1] = y[n-1];   k = n-2..0:  z[k] = y[k] + g[k]*z[k+1]
+ *   forward:   phi_new = x + Solve(Lv(x))
+ *   reverse:   X      <- X + Lv(Solve(X))
+ * This is the increment form of A phi_new = h o phi* with A = diag(h) + s W, W the interface-flux matrix of weights 1 / hm.  A is
+ * symmetric and strictly diagonally dominant for h > 0: no pivoting.  h > 0 on active levels is required and, like the explicit limits,
+ * not checked.  The reverse line is S^T = diag(h) A^-1 = I - s W A^-1, applied to X_j at the head of a reversed step, ahead of
+ * g = X / hn, with the recorded hn, dt and kappaV_j of that step; tau_s, G, Wk and Wk4 keep their definitions (sources and horizontal
+ * mixing act inside the RK stages, before the solve).  The reverse mode uses the factorisation of the forward pass and stays an exact
+ * transpose; the tape records nTracers doubles more per step.
+ * Hence: a tracer that is constant over a column has Lv(x) == 0 exactly, so the unit tracer stays exactly 1.0; a tracer with
+ * kappaV_j == 0 is skipped by a wave-uniform branch (nothing is added to it) and keeps every bit, also beside mixed tracers, forwards
+ * and backwards; the column content sum_k h phi is conserved to round-off; A^-1 diag(h) is row-stochastic and non-negative, so every
+ * active value of a column stays inside that column's former range up to round-off (the limiter-free centred horizontal scheme has no
+ * such property).  The launch is skipped when nVertLevels < 2, when dt == 0.0 and while every kappaV is zero.
+ * moka_step_rk4, moka_run and moka_step_rk4_tracer_taped return MOKA_ERR_ARG before any launch when dt < 0 and some kappaV != 0.
+ * kappaV: nTracers values, NULL = all zero; they take effect with the next RK4 step or moka_run.  MOKA_ERR_ARG, with nothing changed,
+ * for a negative, NaN or infinite value and for a non-NULL kappaV on a state without tracers.  The first nonzero value allocates the
+ * coefficient array and the scratch of the column form (2 * nVertLevels * nCells doubles); while every value is zero a step launches,
+ * allocates and records what a state that never set one does.  moka_set_tracers (any count, 0 included) resets every value to zero.
+ * Not built yet: d J / d kappaV_j = -dt sum over columns and k of (z[k] - z[k+1]) (phi_new[k] - phi_new[k+1]) / hm[k] with z = A^-1 X
+ * and hm[k] = 0.5 (h[k] + h[k+1]) -- it needs phi_new recorded.  Also out of scope: a kappaV that varies in space or time, vertical
+ * advection, vertical mixing of momentum, Forward Euler, fp32 storage, partitioned meshes, YAML keys and NetCDF I/O, the 13-stream form. */
+int  moka_set_tracer_vertical_diffusion(moka_state *st, const double *kappaV);
+/* the vertical diffusivity of tracer j (0-based) into *out; MOKA_ERR_ARG for j out of range */
+int  moka_tracer_vertical_diffusion(const moka_state *st, int32_t j, double *out);
+/* which kernel served the last vertical pass of this state: 1 the tile form (column tiles staged in LDS, a lane per column; nVertLevels
+ * <= 105), 2 the column form (a lane per column from global memory: deeper columns, and kernel variant 3), 0 no vertical pass yet */
+int  moka_state_tracer_vmix_path(const moka_state *st);
 
 /* ---- reverse mode of passive tracer transport over a frozen flow (extension) ---------------------------------------
  * Once the flow is given the tracer step above is linear in phi, so d J(phi_N) / d phi_0 is the exact transpose of a linear map.  It
@@ -702,8 +747,8 @@ int  moka_tracer_has_source(const moka_state *st, int32_t j, int *out);
 typedef struct moka_tracer_tape moka_tracer_tape;
 /* MOKA_ERR_UNSUPPORTED on a state without tracers, MOKA_ERR_ARG for NULL arguments or a negative capacity.  The tape remembers the
  * state's tracer count and counts as a tape of the state: while it lives, moka_state_optimize_placement and moka_set_tracers(st, n > 0)
- * refuse.  K * (4 nEdges + 5 nCells) doubles per step of capacity (the four P_s and hn), nTracers more for the diffusivities and nTracers
- * for the biharmonic coefficients, and six work arrays of nTracers * K * nCells doubles (the sixth holds M).  State and tape may be destroyed in either order. */
+ * refuse.  K * (4 nEdges + 5 nCells) doubles per step of capacity (the four P_s and hn), nTracers more for the diffusivities, nTracers
+ * for the biharmonic coefficients and nTracers for the vertical diffusivities, and six work arrays of nTracers * K * nCells doubles (the sixth holds M).  State and tape may be destroyed in either order. */
 int  moka_tracer_tape_create(moka_state *st, int64_t capacity_steps, moka_tracer_tape **out);
 void moka_tracer_tape_destroy(moka_tracer_tape *t);
 /* exactly moka_step_rk4 on the tape's state -- state and tracers end up bit for bit as after the untaped call -- with P_0..P_3, hn and
@@ -719,6 +764,9 @@ int  moka_tracer_adjoint_sweep(moka_tracer_tape *t);
 int  moka_tracer_adjoint_download(moka_tracer_tape *t, int32_t j, double *host);    /* X_j as it stands */
 /* which kernel served the last reverse stage: 1 the patch form, 2 the generic form (the conditions of moka_state_tracer_path), 0 none yet */
 int  moka_tracer_adjoint_path(const moka_tracer_tape *t);
+/* which kernel served the vertical pass of the last reverse step that had one: as moka_state_tracer_vmix_path; 0 none yet.  A sweep whose
+ * recorded steps all have every kappaV == 0 launches what it launches without the term. */
+int  moka_tracer_adjoint_vmix_path(const moka_tracer_tape *t);
 /* on != 0: the next sweeps also accumulate G_j (algebra above); 0: they no longer do (the accumulator stays readable).  May be called
  * whenever the tape is not between a seed and its sweep (MOKA_ERR_ARG there, and for j out of range); the first call for a tracer
  * allocates its (nVertLevels, nCells) accumulator.  The first seed after a recorded step zeroes every G, as it zeroes X.  A sweep in

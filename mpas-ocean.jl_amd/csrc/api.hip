@@ -1452,6 +1452,24 @@ static hipError_t tracer_stage(moka_state *st, int s, const StageArgs &g)
     return launch_tracers(dev, t, mm->lpc, generic, st->ctx->stream);
 }
 
+// The vertical pass (implicit vertical diffusion, include/moka_hip.h): forwards behind the stage-4 tracer launch on the new tracers with
+// the new thickness, backwards at the head of a reversed step on X with the recorded hn.  The callers skip it when K < 2, when dt == 0.0
+// and while every kappaV is zero.  *path takes the form that served it.
+static int tracer_vmix(moka_mesh *mm, moka_ctx *ctx, int nT, const double *h, double *x, const double *kv, double dt, double *scratch,
+                       bool reverse, int *path)
+{
+    const Plan &p = mm->plan;
+    if (!mm->nLev)
+        if (int rc = upload_vec(mm, p.nLev, &mm->nLev)) return rc;
+    VmixArgs a{};
+    a.nT = nT; a.nC = p.nC; a.K = p.K; a.stride = (int64_t)p.K * p.nC;
+    a.h = h; a.x = x; a.kv = kv; a.dt = dt; a.nLev = mm->nLev; a.scratch = scratch;
+    const bool generic = ctx->variant == 3;
+    *path = vmix_kernel(p.K, generic).form;
+    HIPCHK(ctx, launch_tracer_vmix(a, reverse, generic, ctx->stream));
+    return MOKA_OK;
+}
+
 // Tape of the tracer reverse mode (moka_tracer_tape_*, further down).  Per recorded step: the four provisional states the stage launches
 // read, the new level's thickness and the diffusivities in force -- K * (4 nEdges + 5 nCells) doubles and nTracers more.
 struct moka_tracer_tape {
@@ -1463,6 +1481,11 @@ struct moka_tracer_tape {
     double *hn = nullptr;                            // capacity x (K, nC): layerThickness of the new level
     double *kap = nullptr, *kap4 = nullptr;          // capacity x nT each: the diffusivities and the biharmonic coefficients on the device
     std::vector<double> kappa, kappa4, dts;          // ... and on the host (n * nT values each); dt of each step
+    double *kv = nullptr;                            // capacity x nT: the vertical diffusivities on the device ...
+    std::vector<double> kappaV;                      // ... and on the host
+    bool kvUsed = false;                             // some recorded step had a nonzero kappaV: slots of kv may hold old values
+    double *vmScratch = nullptr;                     // 2 x (K, nC): the column form's g and y, allocated by the first sweep that has a vertical pass
+    int vmixPath = 0;                                // moka_tracer_adjoint_vmix_path
     double *M = nullptr;                             // nT x (K, nC): Lap(ph_s, y) of a reverse stage (biharmonic term)
     double *X = nullptr, *g = nullptr, *S = nullptr, *y[2] = {nullptr, nullptr};   // nT x (K, nC) each: the adjoint state and the sweep's work arrays
     // gradient with respect to the sources (moka_tracer_adjoint_want_source_gradient): the (K, nC) accumulator of every tracer that was
@@ -1494,6 +1517,8 @@ struct moka_tracer_tape {
 static int step_rk4(moka_state *st, double dt, moka_tracer_tape *rec)
 {
     HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    const bool vmix = st->nTracers > 0 && st->trKappaVDev != nullptr;      // (non-null exactly while some kappaV != 0)
+    if (vmix && dt < 0.0) return fail(st->ctx, MOKA_ERR_ARG, "vertical tracer diffusion: dt must be >= 0 (the implicit solve is not reversible in time)");
     const double *ssh0 = nullptr;
     int rc = rk4_begin(st, &ssh0);
     if (rc) return rc;
@@ -1515,6 +1540,8 @@ static int step_rk4(moka_state *st, double dt, moka_tracer_tape *rec)
         const StageArgs g = s13 ? rk13_stage_args(st, s, dt, ssh0) : rk4_stage_args(st, s, dt, ssh0);
         HIPCHK(c, run_stage(st, g));
         if (st->nTracers > 0) HIPCHK(c, tracer_stage(st, s, g));
+        if (s == 4 && vmix && st->mesh->plan.K >= 2 && dt != 0.0)       // the split step: the new tracers (still in the previous level's array) over the new thickness
+            if ((rc = tracer_vmix(st->mesh, c, st->nTracers, g.nh_out, st->trPhi[0], st->trKappaVDev, dt, st->trVmixScratch, false, &st->vmixPath))) return rc;
         if (rec) {
             const Plan &p = st->mesh->plan;
             const size_t nEK = (size_t)p.K * p.nE, nCK = (size_t)p.K * p.nC;
@@ -1579,6 +1606,8 @@ int moka_run(moka_state *st, int integrator, double dt, int64_t nsteps, int flag
     if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
     if (nsteps < 0) return fail(st->ctx, MOKA_ERR_ARG, "nsteps must be >= 0");
     if (integrator != MOKA_FORWARD_EULER && integrator != MOKA_RUNGE_KUTTA_4) return fail(st->ctx, MOKA_ERR_ARG, "unknown integrator");
+    if (integrator == MOKA_RUNGE_KUTTA_4 && dt < 0.0 && st->nTracers > 0 && st->trKappaVDev)
+        return fail(st->ctx, MOKA_ERR_ARG, "vertical tracer diffusion: dt must be >= 0 (the implicit solve is not reversible in time)");
     auto one = [&]() { return integrator == MOKA_FORWARD_EULER ? moka_step_fe(st, dt, flags) : moka_step_rk4(st, dt); };
     int64_t done = 0;
     int rc;
@@ -1876,7 +1905,8 @@ int moka_set_tracers(moka_state *st, int32_t nTracers)
     }
     HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
     HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));
-    double **arr[7] = {&st->trPhi[0], &st->trPhi[1], &st->trProv[0], &st->trProv[1], &st->trKappaDev, &st->trKappa4Dev, &st->trLap};
+    double **arr[9] = {&st->trPhi[0], &st->trPhi[1], &st->trProv[0], &st->trProv[1], &st->trKappaDev, &st->trKappa4Dev, &st->trLap,
+                       &st->trKappaVDev, &st->trVmixScratch};
     auto release = [&]() {
         drop_sources(st);                // every source goes with the tracers
         for (double **q : arr) {
@@ -1889,11 +1919,13 @@ int moka_set_tracers(moka_state *st, int32_t nTracers)
         st->tracerPath = 0;
         st->trKappa.clear();             // every diffusivity back to zero
         st->trKappa4.clear();            // ... and every biharmonic coefficient
+        st->trKappaV.clear();            // ... and every vertical diffusivity
+        st->vmixPath = 0;
     };
     release();
     if (nTracers == 0) return MOKA_OK;
     for (double **q : arr)
-        if (q == &st->trKappaDev || q == &st->trKappa4Dev || q == &st->trLap) continue;      // allocated by their setters
+        if (q == &st->trKappaDev || q == &st->trKappa4Dev || q == &st->trLap || q == &st->trKappaVDev || q == &st->trVmixScratch) continue;      // allocated by their setters
         else if (int rc = alloc_field(st, q, (size_t)nTracers * p.K * p.nC)) {
             (void)hipStreamSynchronize(st->ctx->stream);
             release();
@@ -2021,6 +2053,58 @@ int moka_tracer_biharmonic(const moka_state *st, int32_t j, double *out)
     return MOKA_OK;
 }
 
+int moka_set_tracer_vertical_diffusion(moka_state *st, const double *kappaV)
+{
+    if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
+    const int nT = st->nTracers;
+    if (kappaV && nT == 0) return fail(st->ctx, MOKA_ERR_ARG, "vertical tracer diffusion: the state has no tracers (moka_set_tracers)");
+    bool any = false;
+    for (int j = 0; kappaV && j < nT; ++j) {
+        if (!(kappaV[j] >= 0.0) || !std::isfinite(kappaV[j]))
+            return fail(st->ctx, MOKA_ERR_ARG, "vertical tracer diffusion: every diffusivity must be finite and >= 0");
+        any = any || kappaV[j] != 0.0;
+    }
+    moka_mesh *mm = st->mesh;
+    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));      // no launch is reading the old values
+    auto drop = [&](double **q) {
+        if (!*q) return;
+        st->allocs.erase(std::remove(st->allocs.begin(), st->allocs.end(), (void *)*q), st->allocs.end());
+        (void)hipFree(*q);
+        *q = nullptr;
+    };
+    if (!any) {
+        drop(&st->trKappaVDev);
+        drop(&st->trVmixScratch);
+        st->trKappaV.clear();
+        return MOKA_OK;
+    }
+    const Plan &p = mm->plan;
+    if (!mm->nLev)
+        if (int rc = upload_vec(mm, p.nLev, &mm->nLev)) return rc;
+    if (!st->trVmixScratch)
+        if (int rc = alloc_field(st, &st->trVmixScratch, 2 * (size_t)p.K * p.nC)) return rc;
+    if (!st->trKappaVDev)
+        if (int rc = alloc_field(st, &st->trKappaVDev, (size_t)nT)) {
+            (void)hipStreamSynchronize(st->ctx->stream);
+            drop(&st->trVmixScratch);
+            return rc;
+        }
+    if (int rc = h2d(st->ctx, st->trKappaVDev, kappaV, (size_t)nT * sizeof(double))) return rc;
+    st->trKappaV.assign(kappaV, kappaV + nT);
+    return MOKA_OK;
+}
+
+int moka_tracer_vertical_diffusion(const moka_state *st, int32_t j, double *out)
+{
+    if (!st || !out) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    if (j < 0 || j >= st->nTracers) return fail(st->ctx, MOKA_ERR_ARG, "tracer index out of range (moka_set_tracers)");
+    *out = st->trKappaV.empty() ? 0.0 : st->trKappaV[j];
+    return MOKA_OK;
+}
+
+int moka_state_tracer_vmix_path(const moka_state *st) { return st ? st->vmixPath : 0; }
+
 // ---------------------------------------------------------------------------------------------
 // reverse mode of the tracer transport over a frozen flow (include/moka_hip.h: the algebra; tracer_adjoint.hip: the kernels).  A handle of
 // its own, separate from moka_tape: the tracer step is linear in phi, so its transpose needs the recorded provisional states only.
@@ -2056,7 +2140,7 @@ int moka_tracer_tape_create(moka_state *st, int64_t capacity_steps, moka_tracer_
     const size_t nEK = (size_t)p.K * p.nE, nCK = (size_t)p.K * p.nC, cap = (size_t)capacity_steps;
     int rc = MOKA_OK;
     auto A = [&](double **q, size_t n) { if (rc == MOKA_OK) rc = ttape_alloc(t, q, n); };
-    A(&t->pu, nEK * 4 * cap); A(&t->ph, nCK * 4 * cap); A(&t->hn, nCK * cap); A(&t->kap, (size_t)t->nT * cap); A(&t->kap4, (size_t)t->nT * cap);
+    A(&t->pu, nEK * 4 * cap); A(&t->ph, nCK * 4 * cap); A(&t->hn, nCK * cap); A(&t->kap, (size_t)t->nT * cap); A(&t->kap4, (size_t)t->nT * cap); A(&t->kv, (size_t)t->nT * cap);
     A(&t->X, nCK * t->nT); A(&t->g, nCK * t->nT); A(&t->S, nCK * t->nT); A(&t->y[0], nCK * t->nT); A(&t->y[1], nCK * t->nT); A(&t->M, nCK * t->nT);
     if (rc != MOKA_OK) { moka_tracer_tape_destroy(t); return rc; }
     HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));
@@ -2100,6 +2184,13 @@ int moka_step_rk4_tracer_taped(moka_tracer_tape *t, double dt)
     if (st->trKappa4Dev) HIPCHK(t->ctx, hipMemcpyAsync(k4d, st->trKappa4Dev, (size_t)t->nT * sizeof(double), hipMemcpyDeviceToDevice, t->ctx->stream));
     else HIPCHK(t->ctx, hipMemsetAsync(k4d, 0, (size_t)t->nT * sizeof(double), t->ctx->stream));
     for (int j = 0; j < t->nT; ++j) t->kappa4.push_back(st->trKappa4.empty() ? 0.0 : st->trKappa4[j]);
+    double *kvd = t->kv + (size_t)t->n * t->nT;
+    if (st->trKappaVDev) {
+        HIPCHK(t->ctx, hipMemcpyAsync(kvd, st->trKappaVDev, (size_t)t->nT * sizeof(double), hipMemcpyDeviceToDevice, t->ctx->stream));
+        t->kvUsed = true;
+    } else if (t->kvUsed)            // (the array is created zeroed: a tape that never saw a kappaV issues nothing here)
+        HIPCHK(t->ctx, hipMemsetAsync(kvd, 0, (size_t)t->nT * sizeof(double), t->ctx->stream));
+    for (int j = 0; j < t->nT; ++j) t->kappaV.push_back(st->trKappaV.empty() ? 0.0 : st->trKappaV[j]);
     t->dts.push_back(dt);
     ++t->n;
     t->seeded = false;
@@ -2174,6 +2265,14 @@ int moka_tracer_adjoint_sweep(moka_tracer_tape *t)
     const MeshDev dev = launch_bounds(mm);
     const bool generic = t->ctx->variant == 3;
     const size_t nEK = (size_t)p.K * p.nE, nCK = (size_t)p.K * p.nC;
+    // the vertical pass of a recorded step (its kappaV, its dt): skipped as in the forward step
+    auto vmix_of = [&](int64_t n) {
+        return p.K >= 2 && t->dts[n] != 0.0 &&
+               std::any_of(t->kappaV.begin() + n * t->nT, t->kappaV.begin() + (n + 1) * t->nT, [](double k) { return k != 0.0; });
+    };
+    for (int64_t n = 0; n < t->n && !t->vmScratch; ++n)
+        if (vmix_of(n))
+            if (int rc = ttape_alloc(t, &t->vmScratch, 2 * nCK)) return rc;
     double *const *G = std::any_of(t->wantG.begin(), t->wantG.end(), [](char w) { return w != 0; }) ? t->Gdev : nullptr;
     t->pending = false;
     while (t->n > 0) {
@@ -2182,6 +2281,8 @@ int moka_tracer_adjoint_sweep(moka_tracer_tape *t)
         const double a[3] = {dt / 2., dt / 2., dt};
         const double b[4] = {dt / 6., dt / 3., dt / 3., dt / 6.};
         int cur = 0;
+        if (vmix_of(n))             // S^T = diag(h) A^-1 on X, ahead of g = X / hn
+            if (int rc = tracer_vmix(mm, t->ctx, t->nT, t->hn + nCK * n, t->X, t->kv + (size_t)n * t->nT, dt, t->vmScratch, true, &t->vmixPath)) return rc;
         HIPCHK(t->ctx, launch_tracer_adj_seed(dev, t->X, t->hn + nCK * n, t->g, t->y[cur], b[3], t->nT, G, s));
         for (int rs = 3; rs >= 0; --rs) {
             TracerAdjArgs q{};
@@ -2219,6 +2320,7 @@ int moka_tracer_adjoint_sweep(moka_tracer_tape *t)
         t->dts.pop_back();
         t->kappa.resize((size_t)n * t->nT);
         t->kappa4.resize((size_t)n * t->nT);
+        t->kappaV.resize((size_t)n * t->nT);
     }
     return MOKA_OK;
 }
@@ -2262,6 +2364,7 @@ int moka_tracer_adjoint_source_download(moka_tracer_tape *t, int32_t j, double *
 }
 
 int moka_tracer_adjoint_path(const moka_tracer_tape *t) { return t ? t->path : 0; }
+int moka_tracer_adjoint_vmix_path(const moka_tracer_tape *t) { return t ? t->vmixPath : 0; }
 
 // ---- d J / d kappa_j, d J / d kappa4_j (include/moka_hip.h: the algebra; k_tracer_kgrad) ----
 static void ttape_free(moka_tracer_tape *t, void *q)

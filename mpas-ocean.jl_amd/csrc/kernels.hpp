@@ -296,6 +296,31 @@ struct TracerKgradArgs {
 };
 hipError_t launch_tracer_kgrad(const MeshDev &m, const TracerKgradArgs &a, int lpc, hipStream_t s);
 
+// ---- implicit vertical diffusion of the tracers (moka_set_tracer_vertical_diffusion; tracer_vmix.hip) ----
+// One launch over every column and every field j with kv[j] != 0 (the others are neither read nor written): forward behind the stage-4
+// tracer launch, x = the new tracers and h the new thickness; reverse at the head of a reversed step, x = X and h the recorded hn.
+// Per column c with n = nLev[c] >= 2 and s = dt * kv[j] (the recipe of include/moka_hip.h):
+//   forward:  x = x + Solve(Lv(x))        reverse:  x = x + Lv(Solve(x))
+struct VmixArgs {
+    int nT, nC, K;
+    int64_t stride;               // K * nC: the fields of x lie this far apart
+    const double *h;              // (K, nC) thickness
+    double *x;                    // nT fields, updated in place
+    const double *kv;             // nT coefficients kappaV
+    double dt;
+    const int32_t *nLev;          // (nC) active depth of a cell (Plan.nLev)
+    double *scratch;              // 2 * K * nC doubles: g and y of the column form (the tile form keeps them in LDS)
+};
+// The kernel that serves the pass (tracer_vmix.hip holds the LDS formula): form 1 = k_vmix_tile over tiles of `tc` columns with `lds`
+// bytes of dynamic LDS, form 2 = k_vmix_column.  generic: the caller asks for form 2 (kernel variant 3).
+struct VmixKernel {
+    int form;
+    size_t lds;
+    int tc;
+};
+VmixKernel vmix_kernel(int K, bool generic);
+hipError_t launch_tracer_vmix(const VmixArgs &a, bool reverse, bool generic, hipStream_t s);
+
 // ---- reverse mode of one Forward-Euler step: gather form, the oracle's summation order ----
 struct AdjMesh {
     int32_t nC, nE, K, ME, W;          // W = width of the transposed Coriolis lists

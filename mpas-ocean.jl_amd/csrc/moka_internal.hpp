@@ -38,6 +38,7 @@ struct Plan {
     std::vector<int32_t> mltc;     // nC*ME  maxLevelEdgeTop of that edge (0 for padding)
     std::vector<double>  sdv;      // nC*ME  dvEdge[e]*edgeSignOnCell[i,c] (exact: sign = +-1)
     std::vector<double>  dvdc;     // nC*ME  dvEdge[e]/dcEdge[e] of slot i (one division; tracer diffusion, uploaded at its first use)
+    std::vector<int32_t> nLev;     // nC     active depth: max of mltc over the cell's slots, at most K (vertical tracer diffusion)
     std::vector<double>  invArea;  // nC     1/areaCell      (horizontal_advection.jl:53)
     std::vector<double>  areaCell; // nC                    (Operators.jl:41 divides by it)
     std::vector<double>  rsum;     // nC     restingThicknessSum

@@ -403,6 +403,7 @@ int build_plan(const moka_mesh_desc *d, Plan &p)
     p.mltc.assign((size_t)nC * ME, 0);
     p.sdv.assign((size_t)nC * ME, 0.0);
     p.dvdc.assign((size_t)nC * ME, 0.0);
+    p.nLev.assign(nC, 0);
     p.invArea.resize(nC); p.areaCell.resize(nC); p.rsum.resize(nC);
     p.cellBandwidth = 0;
     for (int cn = 0; cn < nC; ++cn) {
@@ -418,6 +419,7 @@ int build_plan(const moka_mesh_desc *d, Plan &p)
             p.mltc[IX(i, cn, ME)] = d->maxLevelEdgeTop ? d->maxLevelEdgeTop[eo] : 1;
             p.sdv[IX(i, cn, ME)] = d->dvEdge[eo] * (double)d->edgeSignOnCell[IX(i, co, d->maxEdges)];
             p.dvdc[IX(i, cn, ME)] = d->dvEdge[eo] / d->dcEdge[eo];
+            p.nLev[cn] = std::max(p.nLev[cn], std::min(p.mltc[IX(i, cn, ME)], p.K));     // the levels at which some active element reads the cell
             p.cellBandwidth = std::max<int64_t>(p.cellBandwidth, std::abs((int64_t)p.cellO2N[other] - cn));
         }
         p.invArea[cn] = 1. / d->areaCell[co];
@@ -758,6 +760,7 @@ int moka_plan_array(const moka_plan *plan, int which, const void **data, int64_t
         VEC(MOKA_PA_HALO_START, haloStart) VEC(MOKA_PA_HALO_EDGE, haloEdge) VEC(MOKA_PA_LEOC, leoc) VEC(MOKA_PA_LEOE, leoe)
         VEC(MOKA_PA_CREC, cRec) VEC(MOKA_PA_EREC, eRec) VEC(MOKA_PA_FEOE, feoe)
         VEC(MOKA_PA_PVSTART, pvStart) VEC(MOKA_PA_PVLIST, pvList) VEC(MOKA_PA_LVOE, lvoe)
+        VEC(MOKA_PA_NLEV, nLev)
         default: moka::set_error("unknown plan array id"); return MOKA_ERR_ARG;
     }
 #undef VEC

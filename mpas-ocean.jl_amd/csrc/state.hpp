@@ -50,7 +50,8 @@ struct moka_mesh {
     // and are never launched, so the LDS carve of a boundary / interior launch is sized by the patches it covers
     std::map<std::pair<int, int>, std::pair<int, int>> rangeMax;
     const double *dvdc = nullptr;         // plan.dvdc on the device, uploaded by the first moka_set_tracer_diffusion with a nonzero value
-    moka::D4Rows d4{};        // Del4 mixing: per-patch edge rows of k_d4_patch, built at the first moka_set_viscosity_del4 (start == nullptr: not yet)
+    const int32_t *nLev = nullptr;        // plan.nLev on the device, uploaded when the vertical tracer diffusion first needs it
+    moka::D4Rows d4{};      // Del4 mixing: per-patch edge rows of k_d4_patch, built at the first moka_set_viscosity_del4 (start == nullptr: not yet)
 };
 
 struct LevelBufs {
@@ -126,6 +127,12 @@ struct moka_state {
     // nonzero value is first set, never inside a step, and nullptr while every value is zero.
     std::vector<double> trKappa4;
     double *trKappa4Dev = nullptr, *trLap = nullptr;
+    // implicit vertical tracer diffusion (moka_set_tracer_vertical_diffusion): the host copy (empty = all zero), the device array the
+    // vertical pass reads and the scratch of its column form (2 * K * nC doubles).  Both are allocated when a nonzero value is first set
+    // and nullptr while every value is zero: a step then launches what a state that never set one launches.
+    std::vector<double> trKappaV;
+    double *trKappaVDev = nullptr, *trVmixScratch = nullptr;
+    int vmixPath = 0;                 // moka_state_tracer_vmix_path
     // tracer sources (moka_tracer_source_upload): only a sourced tracer owns a (K, nC) device array.  trSrc holds nTracers pointers
     // (nullptr = no source) and is empty while no tracer has a source; trSrcDev is its copy on the device, the table the tracer
     // launches read -- nullptr while trSrc is empty: the launches are then those of a state that never had a source.  Sources do

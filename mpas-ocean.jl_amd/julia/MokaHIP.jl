@@ -478,6 +478,30 @@ function set_tracers!(Prog::MProg, fields::Vector{Matrix{Float64}}; diffusivity 
         check(ccall((:moka_set_tracer_biharmonic, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), s.handle, kappa4), s.backend.ctx)
     end
 end
+# ... and with implicit vertical diffusion, a backward-Euler solve per column behind the RK4 step (include/moka_hip.h states the
+# recipe): `vertical` is one diffusivity (m^2/s, >= 0) for all tracers or one per tracer.  Unconditionally stable; dt must not be
+# negative while it is on.  A method of its own: the keyword list above is pinned.
+function set_tracers!(Prog::MProg, fields::Vector{Matrix{Float64}}, vertical; diffusivity = nothing, biharmonic = nothing)
+    set_tracers!(Prog, fields; diffusivity = diffusivity, biharmonic = biharmonic)
+    s = Prog.ssh[end].state
+    kappaV = vertical isa Number ? fill(Float64(vertical), length(fields)) : Vector{Float64}(vertical)
+    length(kappaV) == length(fields) || error("MokaHIP: $(length(kappaV)) vertical diffusivities for $(length(fields)) tracers")
+    check(ccall((:moka_set_tracer_vertical_diffusion, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), s.handle, kappaV), s.backend.ctx)
+end
+# the vertical diffusivity of tracer j (1-based), 0.0 unless one was set
+function tracer_vertical_diffusivity(Prog::MProg, j::Integer)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    out = Ref{Float64}(0.0)
+    check(ccall((:moka_tracer_vertical_diffusion, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), s.handle, j - 1, out), s.backend.ctx)
+    out[]
+end
+# 1 the tile form, 2 the column form of the vertical pass served the last step, 0 none yet
+function tracer_vmix_path(Prog::MProg)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    Int(ccall((:moka_state_tracer_vmix_path, lib), Cint, (Ptr{Cvoid},), s.handle))
+end
 # the biharmonic coefficient of tracer j (1-based), 0.0 unless set_tracers! was given one
 function tracer_biharmonic(Prog::MProg, j::Integer)
     s = Prog.ssh[end].state
@@ -659,5 +683,7 @@ function diffusivity_density!(out::Vector{Float64}, t::TracerTape, j::Integer; b
 end
 # 1 the patch form, 2 the generic form of the reverse tracer kernel served the last reverse stage, 0 none yet
 tracer_adjoint_path(t::TracerTape) = Int(ccall((:moka_tracer_adjoint_path, lib), Cint, (Ptr{Cvoid},), t.handle))
+# the same for the vertical pass of the last reverse step: 1 the tile form, 2 the column form, 0 none yet
+tracer_adjoint_vmix_path(t::TracerTape) = Int(ccall((:moka_tracer_adjoint_vmix_path, lib), Cint, (Ptr{Cvoid},), t.handle))
 
 end # module

@@ -663,6 +663,33 @@ class Tracers:
             out[j] = v.value
         return out
 
+    def set_vertical_diffusivity(self, values):
+        """moka_set_tracer_vertical_diffusion: implicit vertical diffusion, a backward-Euler solve per column behind the RK4 step
+        (include/moka_hip.h states the recipe).  `values`: one diffusivity (m^2/s, finite, >= 0) for every tracer or one per tracer;
+        None or 0 switches it off.  Takes effect with the next RK4 step or run; unconditionally stable, but dt must not be negative."""
+        k = None
+        if values is not None:
+            k = np.asarray(values, dtype=np.float64)
+            k = np.full(self.n, float(k)) if k.ndim == 0 else np.ascontiguousarray(k.ravel())
+            if k.size != self.n:
+                raise ValueError(f"vertical: {k.size} values for {self.n} tracers")
+        if k is not None and self.n == 0 and not k.size:
+            k = None
+        L.check(L.lib().moka_set_tracer_vertical_diffusion(self._s._h, None if k is None else k.ctypes.data), self._s.mesh.backend._h)
+
+    def vertical_diffusivity(self) -> np.ndarray:
+        """moka_tracer_vertical_diffusion: the vertical diffusivity of every tracer (zeros unless set_vertical_diffusivity was called)."""
+        out = np.zeros(self.n, dtype=np.float64)
+        v = C.c_double()
+        for j in range(self.n):
+            L.check(L.lib().moka_tracer_vertical_diffusion(self._s._h, j, C.byref(v)), self._s.mesh.backend._h)
+            out[j] = v.value
+        return out
+
+    def vmix_path(self) -> int:
+        """moka_state_tracer_vmix_path: 1 the tile form, 2 the column form of the vertical pass, 0 before the first one."""
+        return int(L.lib().moka_state_tracer_vmix_path(self._s._h))
+
     def set_source(self, j: int, a):
         """moka_tracer_source_upload: the source q_j of tracer j, an (nCells, K) field in tracer * m/s (the rate of change of the
         content h phi), constant in time until changed; None removes it.  Takes effect with the next RK4 step or run.  Every value
@@ -685,13 +712,18 @@ class Tracers:
         return bool(v.value)
 
 
-def set_tracers(Prog: "PrognosticVars", arrays, diffusivity=None, sources=None, biharmonic=None) -> Tracers:
+def set_tracers(Prog: "PrognosticVars", arrays, *positional, vertical=None, diffusivity=None, sources=None, biharmonic=None) -> Tracers:
     """Give this model passive tracers (moka_set_tracers): `arrays` is a list of (nCells, K) fields, uploaded into both time levels;
     an empty list removes the tracers again.  An extension (the reference has none): centred flux-form transport by the thickness
     flux inside RK4 steps (include/moka_hip.h states the algebra); Forward Euler, tapes and halos refuse a state with tracers.
     diffusivity: a scalar or one value per tracer (Tracers.set_diffusivity); None leaves the tracers undiffused.
     sources: one entry per tracer, an (nCells, K) field or None for a tracer without a source (Tracers.set_source).
-    biharmonic: a scalar or one coefficient per tracer (Tracers.set_biharmonic); None leaves the term off."""
+    biharmonic: a scalar or one coefficient per tracer (Tracers.set_biharmonic); None leaves the term off.
+    vertical (keyword only): a scalar or one vertical diffusivity per tracer (Tracers.set_vertical_diffusivity); None leaves the term
+    off.  Arguments given by position beyond `arrays` are diffusivity, sources, biharmonic, as they always were."""
+    if len(positional) > 3:
+        raise TypeError("set_tracers: at most diffusivity, sources, biharmonic by position")
+    diffusivity, sources, biharmonic = (list(positional) + [diffusivity, sources, biharmonic][len(positional):])
     s = Prog._state
     arrays = list(arrays)
     L.check(L.lib().moka_set_tracers(s._h, len(arrays)), s.mesh.backend._h)
@@ -703,6 +735,8 @@ def set_tracers(Prog: "PrognosticVars", arrays, diffusivity=None, sources=None, 
         tr.set_diffusivity(diffusivity)
     if biharmonic is not None:
         tr.set_biharmonic(biharmonic)
+    if vertical is not None:
+        tr.set_vertical_diffusivity(vertical)
     if sources is not None:
         sources = list(sources)
         if len(sources) != len(arrays):
@@ -882,6 +916,10 @@ class TracerAdjointTape:
     def path(self) -> int:
         """moka_tracer_adjoint_path: 1 the patch form, 2 the generic form of the reverse kernel, 0 before the first reverse stage."""
         return int(L.lib().moka_tracer_adjoint_path(self._h))
+
+    def vmix_path(self) -> int:
+        """moka_tracer_adjoint_vmix_path: 1 the tile form, 2 the column form of the last reverse step's vertical pass, 0 none yet."""
+        return int(L.lib().moka_tracer_adjoint_vmix_path(self._h))
 
     def close(self):
         if self._h:

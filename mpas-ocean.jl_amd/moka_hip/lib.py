@@ -104,6 +104,7 @@ EXPORTS = [
     "moka_set_tracers", "moka_tracer_upload", "moka_tracer_download", "moka_state_tracer_path",
     "moka_set_tracer_diffusion", "moka_tracer_diffusion",
     "moka_set_tracer_biharmonic", "moka_tracer_biharmonic",
+    "moka_set_tracer_vertical_diffusion", "moka_tracer_vertical_diffusion", "moka_state_tracer_vmix_path", "moka_tracer_adjoint_vmix_path",
     "moka_tracer_source_upload", "moka_tracer_source_download", "moka_tracer_has_source",
     "moka_tracer_adjoint_want_source_gradient", "moka_tracer_adjoint_source_download",
     "moka_tracer_adjoint_want_diffusivity_gradient", "moka_tracer_adjoint_diffusivity_gradient",
@@ -253,6 +254,10 @@ def lib():
     L.moka_tracer_diffusion.argtypes = [vp, C.c_int32, C.POINTER(C.c_double)]
     L.moka_set_tracer_biharmonic.argtypes = [vp, vp]
     L.moka_tracer_biharmonic.argtypes = [vp, C.c_int32, C.POINTER(C.c_double)]
+    L.moka_set_tracer_vertical_diffusion.argtypes = [vp, vp]
+    L.moka_tracer_vertical_diffusion.argtypes = [vp, C.c_int32, C.POINTER(C.c_double)]
+    L.moka_state_tracer_vmix_path.argtypes = [vp]
+    L.moka_tracer_adjoint_vmix_path.argtypes = [vp]
     L.moka_tracer_tape_create.argtypes = [vp, C.c_int64, C.POINTER(vp)]
     L.moka_tracer_tape_destroy.argtypes = [vp]
     L.moka_tracer_tape_destroy.restype = None
@@ -360,6 +365,7 @@ PLAN_ARRAYS = {  # name -> (id, dtype)
     "haloStart": (16, np.int32), "haloEdge": (17, np.int32), "leoc": (18, np.uint8), "leoe": (19, np.uint8),
     "cRec": (20, np.uint32), "eRec": (21, np.uint32), "feoe": (22, np.float64),
     "pvStart": (23, np.int32), "pvList": (24, np.int32), "lvoe": (25, np.uint16),
+    "nLev": (26, np.int32),
 }
 
 
