@@ -662,9 +662,32 @@ int  moka_tracer_has_source(const moka_state *st, int32_t j, int *out);
  * for a negative, NaN or infinite value and for a non-NULL kappaV on a state without tracers.  The first nonzero value allocates the
  * coefficient array and the scratch of the column form (2 * nVertLevels * nCells doubles); while every value is zero a step launches,
  * allocates and records what a state that never set one does.  moka_set_tracers (any count, 0 included) resets every value to zero.
- * Not built yet: d J / d kappaV_j = -dt sum over columns and k of (z[k] - z[k+1]) (phi_new[k] - phi_new[k+1]) / hm[k] with z = A^-1 X
- * and hm[k] = 0.5 (h[k] + h[k+1]) -- it needs phi_new recorded.  Also out of scope: a kappaV that varies in space or time, vertical
- * advection, vertical mixing of momentum, Forward Euler, fp32 storage, partitioned meshes, YAML keys and NetCDF I/O, the 13-stream form. */
+ * Gradient with respect to kappaV_j (moka_tracer_adjoint_want_vertical_gradient, with the tracer tape below).  d J / d kappaV_j =
+ * -dt sum over columns and k of (z[k] - z[k+1]) (phi_new[k] - phi_new[k+1]) / hm[k] with z = A^-1 X and hm[k] = 0.5 (h[k] + h[k+1]);
+ * the unsummed term is, per interface and cell, d J / d kappaV(k+1/2, c): the sensitivity to a depth-dependent diffusivity, evaluated
+ * at the uniform value the run used.  The product keeps that density.  Consider a recorded step with its own dt, hn (h below) and
+ * kappaV_j; X_j the adjoint of phi_new as it stands at the head of the reversed step, BEFORE S^T is applied; p = phi_new,j, tracer j at
+ * the new level as the step left it (after the vertical pass where one ran, otherwise what stage 4 formed), recorded behind the step by
+ * a copy.  For a flagged tracer j and a column with n = nLev[c] >= 2, every operation rounded once, nothing contracted:
+ *   z = Solve(X)            the bits the reverse pass forms (y, g downwards; z upwards), when kappaV_j != 0 in that step
+ *   z[k] = X[k] / h[k]      when kappaV_j == 0 in that step (A = diag(h); a derivative at zero is legitimate, as for kappa4)
+ *   k = 0 .. n-2:   q = dt / (0.5 * (h[k] + h[k+1]));   c = (p[k] - p[k+1]) * q;   e = (z[k] - z[k+1]) * c;   D_j[k,c] = D_j[k,c] - e
+ * D_j is (nVertLevels, nCells) doubles; row k belongs to the interface between levels k and k+1; rows k >= nLev[c] - 1, row
+ * nVertLevels - 1 included, are never written and stay 0.0.  Like G and Wk, D_j accumulates over every recorded step and is zeroed
+ * where they are, at the first seed after a recorded step.  A recorded step with dt == 0.0, or a mesh with nVertLevels < 2, contributes
+ * nothing and launches nothing; flagging is still allowed there and every view is zeros.  No column reduction happens on the device, so
+ * the device leaves no summation order to pin.  Host views, over the caller's numbering in ascending order, in long double, rounded once:
+ *   cell:     Wv_j[c] = sum_k D_j[k,c]        profile:  Pv_j[k] = sum_c D_j[k,c]        scalar:  d J / d kappaV_j = sum_c sum_k D_j[k,c]
+ * (the scalar cell-major); independent of the mesh's cell ordering because D is elementwise per column.
+ * Hence: asking for the gradient changes no bit of X, G, Wk, Wk4, the state or the tracers; a flagged tracer with kappaV_j == 0 keeps
+ * every bit of its X (only z is formed, nothing is added to X); an unflagged tracer is neither recorded, read nor written; a tracer
+ * that is constant over a column has c == 0 exactly, so the unit tracer's density is exactly 0.0; a zero seed gives exactly zero; the
+ * map is linear in the seed; values at levels >= nLev[c] of p and X (NaN fill under the sea floor) never reach D.  The derivative is
+ * with respect to a coefficient acting identically in every recorded step (the values the steps ran with may differ from step to
+ * step), the flow held as it ran.
+ * Out of scope: a forward model with a kappaV that varies in space or time (only the derivative at the uniform point is delivered), a
+ * per-step split of D, second derivatives, vertical advection, vertical mixing of momentum, Forward Euler, fp32 storage, partitioned
+ * meshes, YAML keys and NetCDF I/O, the 13-stream form. */
 int  moka_set_tracer_vertical_diffusion(moka_state *st, const double *kappaV);
 /* the vertical diffusivity of tracer j (0-based) into *out; MOKA_ERR_ARG for j out of range */
 int  moka_tracer_vertical_diffusion(const moka_state *st, int32_t j, double *out);
@@ -741,18 +764,20 @@ int  moka_state_tracer_vmix_path(const moka_state *st);
  * state or of the tracers (the new launches read ph, y and M and write arrays of their own); the tracer that is 1 everywhere stays exactly 1.0, so its L == 0
  * and both its gradients are exactly 0.0; a zero seed gives densities that are exactly zero; an unflagged tracer is neither recorded, read nor written.
  * Usage: tracer_tape_create -> n x step_rk4_tracer_taped -> seed (per tracer) -> sweep -> download (per tracer).
- * Out of scope: sensitivities of the tracers to the flow (d phi_N / d (u, h)), a spatially varying or time-dependent kappa and a
+ * Out of scope: sensitivities of the tracers to the flow (d phi_N / d (u, h)), a spatially varying or time-dependent kappa or kappaV and a
  * per-step split of its gradient, second derivatives, time-dependent sources and a per-step
  * split of G, coupling to moka_tape, Forward Euler, partitioned meshes, fp32 storage. */
 typedef struct moka_tracer_tape moka_tracer_tape;
 /* MOKA_ERR_UNSUPPORTED on a state without tracers, MOKA_ERR_ARG for NULL arguments or a negative capacity.  The tape remembers the
  * state's tracer count and counts as a tape of the state: while it lives, moka_state_optimize_placement and moka_set_tracers(st, n > 0)
  * refuse.  K * (4 nEdges + 5 nCells) doubles per step of capacity (the four P_s and hn), nTracers more for the diffusivities, nTracers
- * for the biharmonic coefficients and nTracers for the vertical diffusivities, and six work arrays of nTracers * K * nCells doubles (the sixth holds M).  State and tape may be destroyed in either order. */
+ * for the biharmonic coefficients and nTracers for the vertical diffusivities, and six work arrays of nTracers * K * nCells doubles (the sixth holds M).
+ * A tracer flagged by moka_tracer_adjoint_want_vertical_gradient adds K * nCells doubles per step of capacity (its phi_new) and one
+ * K * nCells density; that call allocates them, not this one.  State and tape may be destroyed in either order. */
 int  moka_tracer_tape_create(moka_state *st, int64_t capacity_steps, moka_tracer_tape **out);
 void moka_tracer_tape_destroy(moka_tracer_tape *t);
 /* exactly moka_step_rk4 on the tape's state -- state and tracers end up bit for bit as after the untaped call -- with P_0..P_3, hn and
- * the diffusivities and biharmonic coefficients recorded by copies behind the stage launches.  MOKA_ERR_ARG when the tape is full or the state's tracer count is no
+ * the diffusivities and biharmonic coefficients recorded by copies behind the stage launches (and phi_new of the tracers flagged for the vertical gradient).  MOKA_ERR_ARG when the tape is full or the state's tracer count is no
  * longer the tape's.  A recorded step un-seeds the tape. */
 int  moka_step_rk4_tracer_taped(moka_tracer_tape *t, double dt);
 int  moka_tracer_tape_steps(const moka_tracer_tape *t, int64_t *n);                /* recorded and not yet reversed */
@@ -765,7 +790,9 @@ int  moka_tracer_adjoint_download(moka_tracer_tape *t, int32_t j, double *host);
 /* which kernel served the last reverse stage: 1 the patch form, 2 the generic form (the conditions of moka_state_tracer_path), 0 none yet */
 int  moka_tracer_adjoint_path(const moka_tracer_tape *t);
 /* which kernel served the vertical pass of the last reverse step that had one: as moka_state_tracer_vmix_path; 0 none yet.  A sweep whose
- * recorded steps all have every kappaV == 0 launches what it launches without the term. */
+ * recorded steps all have every kappaV == 0 launches what it launches without the term.  While a tracer is flagged for the vertical
+ * gradient the pass runs in every reversed step with nVertLevels >= 2 and dt != 0.0, also one whose kappaV are all zero, and its
+ * gradient instances keep four column sets in LDS: the tile form then serves nVertLevels <= 79, the column form deeper columns. */
 int  moka_tracer_adjoint_vmix_path(const moka_tracer_tape *t);
 /* on != 0: the next sweeps also accumulate G_j (algebra above); 0: they no longer do (the accumulator stays readable).  May be called
  * whenever the tape is not between a seed and its sweep (MOKA_ERR_ARG there, and for j out of range); the first call for a tracer
@@ -788,6 +815,22 @@ int  moka_tracer_adjoint_want_diffusivity_gradient(moka_tracer_tape *t, int32_t 
  * that is not flagged. */
 int  moka_tracer_adjoint_diffusivity_gradient(moka_tracer_tape *t, int32_t j, int what, double *out);
 int  moka_tracer_adjoint_diffusivity_density_download(moka_tracer_tape *t, int32_t j, int what, double *host);
+/* Gradient with respect to kappaV_j (algebra at moka_set_tracer_vertical_diffusion).  on != 0 flags tracer j, 0 unflags it.  Only while
+ * the tape holds no recorded step and is not between a seed and its sweep: MOKA_ERR_ARG there and for j out of range.  A call that
+ * changes the flagged set allocates each flagged tracer's record of phi_new (capacity * nVertLevels * nCells doubles) and its D --
+ * MOKA_ERR_ALLOC, with nothing changed, when that fails -- and drops what earlier sweeps accumulated.  While any tracer is flagged
+ * moka_step_rk4_tracer_taped copies each flagged tracer's new-level field behind the step (state and tracers keep their bits), and a
+ * reversed step runs the gradient instances of the vertical pass for all its tracers: an unflagged tracer with kappaV != 0 takes the
+ * plain reverse column, a flagged one with kappaV == 0 the gradient alone, an unflagged one with kappaV == 0 is skipped.  A tape
+ * without a flag records, allocates and launches what it always did. */
+int  moka_tracer_adjoint_want_vertical_gradient(moka_tracer_tape *t, int32_t j, int on);
+/* *out = d J / d kappaV_j as D_j stands (the scalar view).  MOKA_ERR_ARG for NULL arguments, j out of range or a tracer that is not
+ * flagged; a flagged tracer that has not been swept reads zero. */
+int  moka_tracer_adjoint_vertical_gradient(moka_tracer_tape *t, int32_t j, double *out);
+/* host: D_j itself, (nVertLevels, nCells) doubles (MOKA_VGRAD_INTERFACE), Wv_j, nCells doubles (MOKA_VGRAD_CELL), or Pv_j, nVertLevels
+ * doubles (MOKA_VGRAD_PROFILE), in the caller's cell numbering.  MOKA_ERR_ARG as above and for an unknown view. */
+enum { MOKA_VGRAD_INTERFACE = 0, MOKA_VGRAD_CELL = 1, MOKA_VGRAD_PROFILE = 2 };
+int  moka_tracer_adjoint_vertical_density_download(moka_tracer_tape *t, int32_t j, int view, double *host);
 
 /* ---- reverse mode of the Forward-Euler loop ----------------------------------------------------------------
  * The reference gets d sum(ssh^2) / d (initial normalVelocity, layerThickness) from Enzyme over ocn_run_loop

@@ -1454,9 +1454,10 @@ static hipError_t tracer_stage(moka_state *st, int s, const StageArgs &g)
 
 // The vertical pass (implicit vertical diffusion, include/moka_hip.h): forwards behind the stage-4 tracer launch on the new tracers with
 // the new thickness, backwards at the head of a reversed step on X with the recorded hn.  The callers skip it when K < 2, when dt == 0.0
-// and while every kappaV is zero.  *path takes the form that served it.
+// and while every kappaV is zero.  *path takes the form that served it.  gslot (reverse only): the gradient instances, with the step's
+// recorded phi_new in p and the densities in D (moka_tracer_adjoint_want_vertical_gradient).
 static int tracer_vmix(moka_mesh *mm, moka_ctx *ctx, int nT, const double *h, double *x, const double *kv, double dt, double *scratch,
-                       bool reverse, int *path)
+                       bool reverse, int *path, const int32_t *gslot = nullptr, const double *p_new = nullptr, double *D = nullptr)
 {
     const Plan &p = mm->plan;
     if (!mm->nLev)
@@ -1464,8 +1465,9 @@ static int tracer_vmix(moka_mesh *mm, moka_ctx *ctx, int nT, const double *h, do
     VmixArgs a{};
     a.nT = nT; a.nC = p.nC; a.K = p.K; a.stride = (int64_t)p.K * p.nC;
     a.h = h; a.x = x; a.kv = kv; a.dt = dt; a.nLev = mm->nLev; a.scratch = scratch;
+    a.gslot = gslot; a.p = p_new; a.D = D;
     const bool generic = ctx->variant == 3;
-    *path = vmix_kernel(p.K, generic).form;
+    *path = vmix_kernel(p.K, generic, gslot ? 4 : 3).form;
     HIPCHK(ctx, launch_tracer_vmix(a, reverse, generic, ctx->stream));
     return MOKA_OK;
 }
@@ -1505,6 +1507,13 @@ struct moka_tracer_tape {
     double *kgMOn = nullptr;                         // capacity x nT: the filter of the sweep's M pass (recorded kappa4, or 1 where M is wanted)
     int32_t *kgTracerDev = nullptr;                  // nF
     double **kgWdev = nullptr;                       // 2 nF
+    // gradient with respect to kappaV_j (moka_tracer_adjoint_want_vertical_gradient): the nV flagged tracers in ascending order.  Allocated
+    // by a flag, never by moka_tracer_tape_create, and replaced as a whole when the set changes (only an empty tape may change it).
+    std::vector<char> wantV;                         // nT
+    std::vector<int32_t> vgTracer;                   // nV
+    double *vgP = nullptr;                           // capacity x nV x (K, nC): phi_new of the flagged tracers as each step left it
+    double *vgD = nullptr;                           // nV x (K, nC): the densities D_f
+    int32_t *vgSlot = nullptr;                       // nT on the device: a tracer's slot in vgP / vgD, -1 when it is not flagged
     bool seeded = false;
     bool pending = false;                            // seeded and not yet swept
     int path = 0;                                    // moka_tracer_adjoint_path
@@ -1553,6 +1562,11 @@ static int step_rk4(moka_state *st, double dt, moka_tracer_tape *rec)
             const size_t nF = rec->kgTracer.size();
             for (size_t f = 0; f < nF; ++f)
                 HIPCHK(c, hipMemcpyAsync(rec->kgP + nCK * ((4 * rec->n + s - 1) * nF + f), pphi + nCK * rec->kgTracer[f], nCK * sizeof(double),
+                                         hipMemcpyDeviceToDevice, c->stream));
+            // phi_new of the tracers flagged for the vertical gradient: behind the vertical pass where one ran, else what stage 4 formed
+            const size_t nV = rec->vgTracer.size();
+            for (size_t f = 0; s == 4 && f < nV; ++f)
+                HIPCHK(c, hipMemcpyAsync(rec->vgP + nCK * (rec->n * nV + f), st->trPhi[0] + nCK * rec->vgTracer[f], nCK * sizeof(double),
                                          hipMemcpyDeviceToDevice, c->stream));
         }
     }
@@ -2136,6 +2150,7 @@ int moka_tracer_tape_create(moka_state *st, int64_t capacity_steps, moka_tracer_
     t->G.assign((size_t)t->nT, nullptr);
     t->wantG.assign((size_t)t->nT, 0);
     t->wantK.assign((size_t)t->nT, 0);
+    t->wantV.assign((size_t)t->nT, 0);
     t->capacity = capacity_steps;
     const size_t nEK = (size_t)p.K * p.nE, nCK = (size_t)p.K * p.nC, cap = (size_t)capacity_steps;
     int rc = MOKA_OK;
@@ -2226,6 +2241,7 @@ int moka_tracer_adjoint_seed(moka_tracer_tape *t, int32_t j, const double *host)
         for (double *G : t->G)
             if (G) HIPCHK(t->ctx, hipMemsetAsync(G, 0, nCK * sizeof(double), t->ctx->stream));
         if (t->kgW) HIPCHK(t->ctx, hipMemsetAsync(t->kgW, 0, 2 * t->kgTracer.size() * (size_t)p.nC * sizeof(double), t->ctx->stream));
+        if (t->vgD) HIPCHK(t->ctx, hipMemsetAsync(t->vgD, 0, t->vgTracer.size() * nCK * sizeof(double), t->ctx->stream));
     }
     t->seeded = true;
     t->pending = true;
@@ -2265,10 +2281,12 @@ int moka_tracer_adjoint_sweep(moka_tracer_tape *t)
     const MeshDev dev = launch_bounds(mm);
     const bool generic = t->ctx->variant == 3;
     const size_t nEK = (size_t)p.K * p.nE, nCK = (size_t)p.K * p.nC;
-    // the vertical pass of a recorded step (its kappaV, its dt): skipped as in the forward step
+    // the vertical pass of a recorded step (its kappaV, its dt): skipped as in the forward step, unless some tracer is flagged for the
+    // vertical gradient -- then the gradient instances run, for a step whose kappaV are all zero the gradient alone
+    const size_t nV = t->vgTracer.size();
     auto vmix_of = [&](int64_t n) {
         return p.K >= 2 && t->dts[n] != 0.0 &&
-               std::any_of(t->kappaV.begin() + n * t->nT, t->kappaV.begin() + (n + 1) * t->nT, [](double k) { return k != 0.0; });
+               (nV > 0 || std::any_of(t->kappaV.begin() + n * t->nT, t->kappaV.begin() + (n + 1) * t->nT, [](double k) { return k != 0.0; }));
     };
     for (int64_t n = 0; n < t->n && !t->vmScratch; ++n)
         if (vmix_of(n))
@@ -2282,7 +2300,8 @@ int moka_tracer_adjoint_sweep(moka_tracer_tape *t)
         const double b[4] = {dt / 6., dt / 3., dt / 3., dt / 6.};
         int cur = 0;
         if (vmix_of(n))             // S^T = diag(h) A^-1 on X, ahead of g = X / hn
-            if (int rc = tracer_vmix(mm, t->ctx, t->nT, t->hn + nCK * n, t->X, t->kv + (size_t)n * t->nT, dt, t->vmScratch, true, &t->vmixPath)) return rc;
+            if (int rc = tracer_vmix(mm, t->ctx, t->nT, t->hn + nCK * n, t->X, t->kv + (size_t)n * t->nT, dt, t->vmScratch, true, &t->vmixPath,
+                                     nV > 0 ? t->vgSlot : nullptr, nV > 0 ? t->vgP + nCK * ((size_t)n * nV) : nullptr, t->vgD)) return rc;
         HIPCHK(t->ctx, launch_tracer_adj_seed(dev, t->X, t->hn + nCK * n, t->g, t->y[cur], b[3], t->nT, G, s));
         for (int rs = 3; rs >= 0; --rs) {
             TracerAdjArgs q{};
@@ -2467,6 +2486,92 @@ int moka_tracer_adjoint_diffusivity_gradient(moka_tracer_tape *t, int32_t j, int
     if (int rc = get_rows(t->st->mesh, w.data(), row, MOKA_CELL, (int64_t)w.size(), 1)) return rc;
     long double sum = 0.0L;            // the caller's cell numbering, ascending, one rounding at the end: independent of the plan's order
     for (double v : w) sum += (long double)v;
+    *out = (double)sum;
+    return MOKA_OK;
+}
+
+// ---- d J / d kappaV_j (include/moka_hip.h: the algebra; the gradient instances of tracer_vmix.hip) ----
+int moka_tracer_adjoint_want_vertical_gradient(moka_tracer_tape *t, int32_t j, int on)
+{
+    if (!t) return fail(nullptr, MOKA_ERR_ARG, "tracer tape is NULL");
+    if (j < 0 || j >= t->nT) return fail(t->ctx, MOKA_ERR_ARG, "tracer index out of range (moka_tracer_tape_create)");
+    if (t->n > 0) return fail(t->ctx, MOKA_ERR_ARG, "tracer tape: the vertical gradient may be chosen only while the tape holds no recorded step");
+    if (t->pending) return fail(t->ctx, MOKA_ERR_ARG, "tracer tape: not between a seed and its sweep");
+    HIPCHK(t->ctx, hipSetDevice(t->ctx->device));
+    std::vector<char> want = t->wantV;
+    want[j] = on ? 1 : 0;
+    if (want == t->wantV) return MOKA_OK;
+    const Plan &p = t->st->mesh->plan;
+    std::vector<int32_t> tr, slot((size_t)t->nT, -1);
+    for (int i = 0; i < t->nT; ++i)
+        if (want[i]) { slot[i] = (int32_t)tr.size(); tr.push_back(i); }
+    const size_t nV = tr.size(), nCK = (size_t)p.K * p.nC, cap = (size_t)t->capacity;
+    HIPCHK(t->ctx, hipStreamSynchronize(t->ctx->stream));        // no launch is reading what goes
+    // the new arrays first (each zeroed): a failure leaves the tape as it was
+    double *P = nullptr, *D = nullptr, *sl = nullptr;
+    if (nV > 0) {
+        int rc = MOKA_OK;
+        auto A = [&](double **q, size_t n) { if (rc == MOKA_OK) rc = ttape_alloc(t, q, n); };
+        A(&P, nCK * nV * cap); A(&D, nCK * nV); A(&sl, ((size_t)t->nT * sizeof(int32_t) + sizeof(double) - 1) / sizeof(double));
+        if (rc == MOKA_OK) rc = h2d(t->ctx, sl, slot.data(), slot.size() * sizeof(int32_t));
+        if (rc != MOKA_OK) {
+            (void)hipStreamSynchronize(t->ctx->stream);
+            for (double *q : {P, D, sl}) ttape_free(t, q);
+            return rc;
+        }
+    }
+    for (void *q : {(void *)t->vgP, (void *)t->vgD, (void *)t->vgSlot}) ttape_free(t, q);
+    t->vgP = P; t->vgD = D; t->vgSlot = reinterpret_cast<int32_t *>(sl);
+    t->wantV = want;
+    t->vgTracer = tr;
+    return MOKA_OK;
+}
+
+// the density of tracer j in the caller's cell numbering, (K, nC) as every field, or an error
+static int vgrad_density(moka_tracer_tape *t, int32_t j, const void *out, std::vector<double> &d)
+{
+    if (!t) return fail(nullptr, MOKA_ERR_ARG, "tracer tape is NULL");
+    if (j < 0 || j >= t->nT) return fail(t->ctx, MOKA_ERR_ARG, "tracer index out of range (moka_tracer_tape_create)");
+    if (!out) return fail(t->ctx, MOKA_ERR_ARG, "NULL argument");
+    if (!t->wantV[j]) return fail(t->ctx, MOKA_ERR_ARG, "tracer tape: this gradient was not asked for (moka_tracer_adjoint_want_vertical_gradient)");
+    HIPCHK(t->ctx, hipSetDevice(t->ctx->device));
+    const Plan &p = t->st->mesh->plan;
+    const size_t f = std::lower_bound(t->vgTracer.begin(), t->vgTracer.end(), j) - t->vgTracer.begin();
+    d.resize((size_t)p.K * p.nC);
+    return get_rows(t->st->mesh, d.data(), t->vgD + f * d.size(), MOKA_CELL, p.nC, p.K);
+}
+
+int moka_tracer_adjoint_vertical_density_download(moka_tracer_tape *t, int32_t j, int view, double *host)
+{
+    if (t && view != MOKA_VGRAD_INTERFACE && view != MOKA_VGRAD_CELL && view != MOKA_VGRAD_PROFILE)
+        return fail(t->ctx, MOKA_ERR_ARG, "tracer tape: view must be MOKA_VGRAD_INTERFACE, MOKA_VGRAD_CELL or MOKA_VGRAD_PROFILE");
+    std::vector<double> d;
+    if (int rc = vgrad_density(t, j, host, d)) return rc;
+    const int64_t K = t->st->mesh->plan.K, nC = t->st->mesh->plan.nC;
+    if (view == MOKA_VGRAD_INTERFACE) {
+        std::copy(d.begin(), d.end(), host);
+    } else if (view == MOKA_VGRAD_CELL) {         // ascending k, long double, one rounding
+        for (int64_t c = 0; c < nC; ++c) {
+            long double sum = 0.0L;
+            for (int64_t k = 0; k < K; ++k) sum += (long double)d[(size_t)(c * K + k)];
+            host[c] = (double)sum;
+        }
+    } else {                                      // ascending over the caller's cells
+        for (int64_t k = 0; k < K; ++k) {
+            long double sum = 0.0L;
+            for (int64_t c = 0; c < nC; ++c) sum += (long double)d[(size_t)(c * K + k)];
+            host[k] = (double)sum;
+        }
+    }
+    return MOKA_OK;
+}
+
+int moka_tracer_adjoint_vertical_gradient(moka_tracer_tape *t, int32_t j, double *out)
+{
+    std::vector<double> d;
+    if (int rc = vgrad_density(t, j, out, d)) return rc;
+    long double sum = 0.0L;            // cell-major over the caller's numbering, one rounding at the end: independent of the plan's order
+    for (double v : d) sum += (long double)v;
     *out = (double)sum;
     return MOKA_OK;
 }

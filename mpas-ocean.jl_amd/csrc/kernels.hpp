@@ -310,15 +310,21 @@ struct VmixArgs {
     double dt;
     const int32_t *nLev;          // (nC) active depth of a cell (Plan.nLev)
     double *scratch;              // 2 * K * nC doubles: g and y of the column form (the tile form keeps them in LDS)
+    // the gradient instances of the reverse pass only (moka_tracer_adjoint_want_vertical_gradient; nullptr otherwise):
+    const int32_t *gslot;         // nT: the slot f of a flagged tracer in p and D, -1 for an unflagged one
+    const double *p;              // nF fields `stride` apart: the recorded phi_new of this step
+    double *D;                    // nF fields `stride` apart: the densities, D[k,c] = D[k,c] - e
 };
 // The kernel that serves the pass (tracer_vmix.hip holds the LDS formula): form 1 = k_vmix_tile over tiles of `tc` columns with `lds`
-// bytes of dynamic LDS, form 2 = k_vmix_column.  generic: the caller asks for form 2 (kernel variant 3).
+// bytes of dynamic LDS, form 2 = k_vmix_column.  generic: the caller asks for form 2 (kernel variant 3).  sets: the column sets a
+// resident column takes in LDS, 3 for the forward and the plain reverse pass, 4 for the gradient instances.
 struct VmixKernel {
     int form;
     size_t lds;
     int tc;
 };
-VmixKernel vmix_kernel(int K, bool generic);
+VmixKernel vmix_kernel(int K, bool generic, int sets = 3);
+// a.gslot != nullptr (reverse only): the gradient instances, which also serve the unflagged tracers of the step
 hipError_t launch_tracer_vmix(const VmixArgs &a, bool reverse, bool generic, hipStream_t s);
 
 // ---- reverse mode of one Forward-Euler step: gather form, the oracle's summation order ----

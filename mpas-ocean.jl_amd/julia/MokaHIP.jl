@@ -681,6 +681,24 @@ function diffusivity_density!(out::Vector{Float64}, t::TracerTape, j::Integer; b
     check(ccall((:moka_tracer_adjoint_diffusivity_density_download, lib), Cint, (Ptr{Cvoid}, Int32, Cint, Ptr{Float64}), t.handle, j - 1, biharmonic ? TRACER_GRAD_KAPPA4 : TRACER_GRAD_KAPPA, out), t.state.backend.ctx)
     out
 end
+# d J / d kappaV_j (include/moka_hip.h states the algebra): flag tracer j (1-based) while the tape holds no recorded step; the steps
+# recorded from then on also keep its new-level field.  Changing the set of flagged tracers drops what earlier sweeps accumulated.
+const VGRAD_INTERFACE = Cint(0)
+const VGRAD_CELL = Cint(1)
+const VGRAD_PROFILE = Cint(2)
+function want_vertical_gradient!(t::TracerTape, j::Integer, on::Bool = true)
+    check(ccall((:moka_tracer_adjoint_want_vertical_gradient, lib), Cint, (Ptr{Cvoid}, Int32, Cint), t.handle, j - 1, on ? 1 : 0), t.state.backend.ctx)
+end
+function vertical_gradient(t::TracerTape, j::Integer)
+    out = Ref{Float64}(0.0)
+    check(ccall((:moka_tracer_adjoint_vertical_gradient, lib), Cint, (Ptr{Cvoid}, Int32, Ref{Float64}), t.handle, j - 1, out), t.state.backend.ctx)
+    out[]
+end
+# the density into `out`: (nVertLevels, nCells) for VGRAD_INTERFACE, nCells values for VGRAD_CELL, nVertLevels for VGRAD_PROFILE
+function vertical_density!(out::Array{Float64}, t::TracerTape, j::Integer; view::Cint = VGRAD_INTERFACE)
+    check(ccall((:moka_tracer_adjoint_vertical_density_download, lib), Cint, (Ptr{Cvoid}, Int32, Cint, Ptr{Float64}), t.handle, j - 1, view, out), t.state.backend.ctx)
+    out
+end
 # 1 the patch form, 2 the generic form of the reverse tracer kernel served the last reverse stage, 0 none yet
 tracer_adjoint_path(t::TracerTape) = Int(ccall((:moka_tracer_adjoint_path, lib), Cint, (Ptr{Cvoid},), t.handle))
 # the same for the vertical pass of the last reverse step: 1 the tile form, 2 the column form, 0 none yet

@@ -806,7 +806,8 @@ class TracerAdjointTape:
     step), the flow held as it ran.  The tracer step is linear in the tracers, so this is an exact transpose; it works over the
     linear, nonlinear, Del2 and Del4 dycores alike.  want_source_gradient(j) makes the sweep also return d J / d q_j for a source
     q_j that acts identically in every recorded step, want_diffusivity_gradient(j) -- before the first recorded step -- the scalars
-    d J / d kappa_j and d J / d kappa4_j and their per-cell densities.  Sensitivities to the flow are out of scope."""
+    d J / d kappa_j and d J / d kappa4_j and their per-cell densities, want_vertical_gradient(j) -- likewise before the first recorded
+    step -- d J / d kappaV_j with its density per interface and cell.  Sensitivities to the flow are out of scope."""
 
     def __init__(self, Prog: "PrognosticVars", capacity_steps: int):
         self._state = Prog._state
@@ -814,6 +815,7 @@ class TracerAdjointTape:
         self._shape = tuple(Prog.layerThickness[-1].shape)
         self._h = C.c_void_p()
         self._kflags = {}
+        self._vflags = set()
         L.check(L.lib().moka_tracer_tape_create(self._state._h, int(capacity_steps), C.byref(self._h)), self._ctx)
         _own(self, L.lib().moka_tracer_tape_destroy, self._h, self._state, self._state.mesh, self._state.mesh.backend)
         self._state._dependents.append(weakref.ref(self))
@@ -887,11 +889,38 @@ class TracerAdjointTape:
         L.check(L.lib().moka_tracer_adjoint_diffusivity_density_download(self._h, int(j), what, L.f64(out)), self._ctx)
         return out
 
-    def gradient(self, seeds, sources: bool = False, diffusivity: bool = False):
+    def want_vertical_gradient(self, j: int, on: bool = True):
+        """moka_tracer_adjoint_want_vertical_gradient: the steps recorded from now on also keep tracer j's new-level field, and the
+        sweep accumulates the density of d J / d kappaV_j (on=False: no longer).  Only while the tape holds no recorded step.  Changing
+        the set of flagged tracers drops what earlier sweeps left."""
+        L.check(L.lib().moka_tracer_adjoint_want_vertical_gradient(self._h, int(j), 1 if on else 0), self._ctx)
+        (self._vflags.add if on else self._vflags.discard)(int(j))
+
+    def vertical_gradient(self, j: int) -> float:
+        """d J / d kappaV_j as it stands (after a sweep: the derivative with respect to a vertical diffusivity that acts identically in
+        every recorded step): the sum of vertical_density(j) over interfaces and cells."""
+        out = C.c_double()
+        L.check(L.lib().moka_tracer_adjoint_vertical_gradient(self._h, int(j), C.byref(out)), self._ctx)
+        return float(out.value)
+
+    def vertical_density(self, j: int, view: str = "interface") -> np.ndarray:
+        """The sensitivity density of d J / d kappaV_j in the caller's numbering.  view="interface": (nCells, K), column k the interface
+        between levels k and k+1 (d J / d kappaV at that interface of that cell; columns k >= the cell's active depth - 1 are zero);
+        "cell": its sums over the interfaces, nCells values; "profile": its sums over the cells, K values."""
+        views = {"interface": (L.VGRAD_INTERFACE, self._shape), "cell": (L.VGRAD_CELL, self._shape[0]), "profile": (L.VGRAD_PROFILE, self._shape[1])}
+        if view not in views:
+            raise ValueError(f"vertical_density: view must be one of {sorted(views)}, not {view!r}")
+        what, shape = views[view]
+        out = np.empty(shape, dtype=np.float64)
+        L.check(L.lib().moka_tracer_adjoint_vertical_density_download(self._h, int(j), what, L.f64(out)), self._ctx)
+        return out
+
+    def gradient(self, seeds, sources: bool = False, diffusivity: bool = False, vertical: bool = False):
         """seeds: one entry per tracer, None meaning zero.  Seeds, sweeps and returns the list of gradients d J / d phi_0; with
         sources=True every tracer's source gradient is asked for and (dphi0, dq) is returned.  diffusivity=True appends the two
         vectors (d J / d kappa_j), (d J / d kappa4_j) over the tracers, NaN where want_diffusivity_gradient did not ask (that has to
-        happen before the steps are recorded, so this call cannot do it)."""
+        happen before the steps are recorded, so this call cannot do it).  vertical=True appends the vector (d J / d kappaV_j), NaN where
+        want_vertical_gradient did not ask."""
         seeds = list(seeds)
         if sources:
             for j in range(len(seeds)):
@@ -911,6 +940,12 @@ class TracerAdjointTape:
                 if k4 and j < len(seeds):
                     dk4[j] = self.biharmonic_gradient(j)
             out += (dk, dk4)
+        if vertical:
+            dkv = np.full(len(seeds), np.nan)
+            for j in self._vflags:
+                if j < len(seeds):
+                    dkv[j] = self.vertical_gradient(j)
+            out += (dkv,)
         return out if len(out) > 1 else dphi0
 
     def path(self) -> int:
@@ -918,7 +953,8 @@ class TracerAdjointTape:
         return int(L.lib().moka_tracer_adjoint_path(self._h))
 
     def vmix_path(self) -> int:
-        """moka_tracer_adjoint_vmix_path: 1 the tile form, 2 the column form of the last reverse step's vertical pass, 0 none yet."""
+        """moka_tracer_adjoint_vmix_path: 1 the tile form, 2 the column form of the last reverse step's vertical pass (with a tracer
+        flagged by want_vertical_gradient: of its gradient instances), 0 none yet."""
         return int(L.lib().moka_tracer_adjoint_vmix_path(self._h))
 
     def close(self):

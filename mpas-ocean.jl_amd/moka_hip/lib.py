@@ -18,6 +18,7 @@ OK = 0
 ERR_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_ALLOC, ERR_UNSUPPORTED, ERR_COMM = -1, -2, -3, -4, -5, -6
 ORDER_DEFAULT, ORDER_NONE, ORDER_RCM, ORDER_RCB = 0, 1, 2, 3
 TRACER_GRAD_KAPPA, TRACER_GRAD_KAPPA4 = 1, 2       # moka_tracer_adjoint_want_diffusivity_gradient
+VGRAD_INTERFACE, VGRAD_CELL, VGRAD_PROFILE = 0, 1, 2    # moka_tracer_adjoint_vertical_density_download
 CELL, EDGE, VERTEX = 0, 1, 2
 (F_SSH, F_NORMAL_VELOCITY, F_LAYER_THICKNESS, F_LAYER_THICKNESS_EDGE, F_THICKNESS_FLUX,
  F_VELOCITY_DIV_CELL, F_RELATIVE_VORTICITY, F_TEND_NORMAL_VELOCITY, F_TEND_LAYER_THICKNESS) = range(9)
@@ -109,6 +110,8 @@ EXPORTS = [
     "moka_tracer_adjoint_want_source_gradient", "moka_tracer_adjoint_source_download",
     "moka_tracer_adjoint_want_diffusivity_gradient", "moka_tracer_adjoint_diffusivity_gradient",
     "moka_tracer_adjoint_diffusivity_density_download",
+    "moka_tracer_adjoint_want_vertical_gradient", "moka_tracer_adjoint_vertical_gradient",
+    "moka_tracer_adjoint_vertical_density_download",
     "moka_tracer_tape_create", "moka_tracer_tape_destroy", "moka_step_rk4_tracer_taped", "moka_tracer_tape_steps",
     "moka_tracer_adjoint_seed", "moka_tracer_adjoint_sweep", "moka_tracer_adjoint_download", "moka_tracer_adjoint_path",
 ]
@@ -275,6 +278,9 @@ def lib():
     L.moka_tracer_adjoint_want_diffusivity_gradient.argtypes = [vp, C.c_int32, C.c_int, C.c_int]
     L.moka_tracer_adjoint_diffusivity_gradient.argtypes = [vp, C.c_int32, C.c_int, C.POINTER(C.c_double)]
     L.moka_tracer_adjoint_diffusivity_density_download.argtypes = [vp, C.c_int32, C.c_int, vp]
+    L.moka_tracer_adjoint_want_vertical_gradient.argtypes = [vp, C.c_int32, C.c_int]
+    L.moka_tracer_adjoint_vertical_gradient.argtypes = [vp, C.c_int32, C.POINTER(C.c_double)]
+    L.moka_tracer_adjoint_vertical_density_download.argtypes = [vp, C.c_int32, C.c_int, vp]
     L.moka_tape_create.argtypes = [vp, C.c_int64, C.POINTER(vp)]
     L.moka_tape_destroy.argtypes = [vp]
     L.moka_tape_destroy.restype = None
