@@ -664,8 +664,9 @@ int  moka_tracer_has_source(const moka_state *st, int32_t j, int *out);
  * allocates and records what a state that never set one does.  moka_set_tracers (any count, 0 included) resets every value to zero.
  * Gradient with respect to kappaV_j (moka_tracer_adjoint_want_vertical_gradient, with the tracer tape below).  d J / d kappaV_j =
  * -dt sum over columns and k of (z[k] - z[k+1]) (phi_new[k] - phi_new[k+1]) / hm[k] with z = A^-1 X and hm[k] = 0.5 (h[k] + h[k+1]);
- * the unsummed term is, per interface and cell, d J / d kappaV(k+1/2, c): the sensitivity to a depth-dependent diffusivity, evaluated
- * at the uniform value the run used.  The product keeps that density.  Consider a recorded step with its own dt, hn (h below) and
+ * the unsummed term is, per interface and cell, d J / d kappaV(k+1/2, c): the sensitivity to a depth-dependent diffusivity, at the
+ * diffusivity the run used -- the uniform kappaV_j, or the field f_j of moka_tracer_vertical_field_upload below, for which D_j is
+ * d J / d f_j[k,c] itself.  The product keeps that density.  Consider a recorded step with its own dt, hn (h below) and
  * kappaV_j; X_j the adjoint of phi_new as it stands at the head of the reversed step, BEFORE S^T is applied; p = phi_new,j, tracer j at
  * the new level as the step left it (after the vertical pass where one ran, otherwise what stage 4 formed), recorded behind the step by
  * a copy.  For a flagged tracer j and a column with n = nLev[c] >= 2, every operation rounded once, nothing contracted:
@@ -685,15 +686,53 @@ int  moka_tracer_has_source(const moka_state *st, int32_t j, int *out);
  * map is linear in the seed; values at levels >= nLev[c] of p and X (NaN fill under the sea floor) never reach D.  The derivative is
  * with respect to a coefficient acting identically in every recorded step (the values the steps ran with may differ from step to
  * step), the flow held as it ran.
- * Out of scope: a forward model with a kappaV that varies in space or time (only the derivative at the uniform point is delivered), a
- * per-step split of D, second derivatives, vertical advection, vertical mixing of momentum, Forward Euler, fp32 storage, partitioned
- * meshes, YAML keys and NetCDF I/O, the 13-stream form. */
+ * Out of scope: a kappaV that varies in time other than by a new call between steps, a per-step split of D, second derivatives,
+ * vertical advection, vertical mixing of momentum, Forward Euler, fp32 storage, partitioned meshes, YAML keys and NetCDF I/O, the
+ * 13-stream form. */
 int  moka_set_tracer_vertical_diffusion(moka_state *st, const double *kappaV);
 /* the vertical diffusivity of tracer j (0-based) into *out; MOKA_ERR_ARG for j out of range */
 int  moka_tracer_vertical_diffusion(const moka_state *st, int32_t j, double *out);
 /* which kernel served the last vertical pass of this state: 1 the tile form (column tiles staged in LDS, a lane per column; nVertLevels
  * <= 105), 2 the column form (a lane per column from global memory: deeper columns, and kernel variant 3), 0 no vertical pass yet */
 int  moka_state_tracer_vmix_path(const moka_state *st);
+/* A vertical diffusivity per interface and cell (default: none).  Tracer j may carry a field f_j >= 0 (m^2/s), laid out as every tracer
+ * field and as D_j are: (nVertLevels, nCells) doubles, row k of a column the interface between levels k and k+1.  Rows
+ * k >= nLev[c] - 1, row nVertLevels - 1 included, are never read and may hold anything, NaN included.  For such a tracer the recipe
+ * above changes in one operand,
+ *   s[k] = dt * f_j[k,c]                          (one product, rounded once)
+ *   w[k] = s[k] / (0.5 * (h[k] + h[k+1]))         k = 0 .. n-2
+ * and stays as it is, letter for letter, in d, Lv, Solve, the forward line x + Solve(Lv(x)), the reverse line X + Lv(Solve(X)) and the
+ * gradient lines q, c, e and D = D - e, with z from the field's solve.  While tracer j has a field its kappaV_j is not read for it (the
+ * scalar is kept and acts again once the field is removed).
+ * Hence: a field that equals kappa at every active interface gives the bits of the scalar kappa, forwards, backwards and in D (dt *
+ * kappa is the same product); an interface with f == 0 decouples the column there (w == 0, g == 0, no pivot is lost: beta >= h > 0);
+ * A stays symmetric and strictly diagonally dominant for f >= 0, h > 0; the unit tracer stays exactly 1.0, the column content stays
+ * conserved and every active value stays inside its column's former range, as above; D_j[k,c] is d J / d f_j[k,c] for a field that
+ * acts in every recorded step, and the scalar view is the directional derivative along the all-ones field.
+ * A field whose active entries are all zero (found by the host scan of the upload) counts as kappaV_j == 0: the tracer is skipped by
+ * the wave-uniform branch and keeps every bit, and a gradient takes z[k] = X[k] / h[k].
+ * "The pass is on" -- nLev and the scratch of the column form exist, dt < 0 is refused, the launch is skipped only for nVertLevels < 2
+ * and dt == 0.0 -- now reads: some kappaV_j != 0 that is not set aside by a field, or some tracer has a field with a nonzero active
+ * entry.  A state that never uploads a field launches, allocates and records exactly what it did before.
+ * The tile form stages s[k] into the column set that y[k] overwrites once s[k] is read: the same LDS, the same tiles, the same paths
+ * (moka_state_tracer_vmix_path, moka_tracer_adjoint_vmix_path), one more field read per tracer with a field.
+ * host: (nCells, nVertLevels) in the caller's numbering like moka_tracer_upload; NULL removes the field and the tracer returns to its
+ * scalar.  MOKA_ERR_ARG, with nothing changed, for j out of range, a state without tracers, and a negative, NaN or infinite value at an
+ * active row, k < nLev[c] - 1 by the plan's nLev (MOKA_PA_NLEV); inactive rows are not inspected.  The call synchronises the stream
+ * before it replaces a field a launch may still read, and takes effect with the next RK4 step or moka_run.  moka_set_tracers frees
+ * every field; moka_set_tracer_vertical_diffusion leaves them alone.
+ * Tape: moka_step_rk4_tracer_taped keeps, per tracer, a copy of the field the step ran with -- K * nCells doubles, taken device to
+ * device on the context's stream ahead of the step's first launch, and only when the field was uploaded or removed since the tape's
+ * newest copy of it -- so that the reverse pass and the gradient instances of a recorded step use the field of that step.  The copies
+ * are released when a sweep has emptied the tape and when the tape is destroyed.  A tape whose steps never saw a field allocates,
+ * records and launches what it did before.
+ * Out of scope: a field shared across tracers (upload the same array per tracer), closures that would compute the field
+ * (Richardson number, KPP), vertical mixing of momentum, and everything listed above. */
+int  moka_tracer_vertical_field_upload(moka_state *st, int32_t j, const double *host);
+/* the diffusivity field of tracer j into host (zeros when tracer j has none); MOKA_ERR_ARG for j out of range or a NULL host */
+int  moka_tracer_vertical_field_download(moka_state *st, int32_t j, double *host);
+/* *out = 1 when tracer j has a diffusivity field, else 0; MOKA_ERR_ARG for j out of range or a NULL out */
+int  moka_tracer_has_vertical_field(const moka_state *st, int32_t j, int *out);
 
 /* ---- reverse mode of passive tracer transport over a frozen flow (extension) ---------------------------------------
  * Once the flow is given the tracer step above is linear in phi, so d J(phi_N) / d phi_0 is the exact transpose of a linear map.  It
@@ -764,7 +803,7 @@ int  moka_state_tracer_vmix_path(const moka_state *st);
  * state or of the tracers (the new launches read ph, y and M and write arrays of their own); the tracer that is 1 everywhere stays exactly 1.0, so its L == 0
  * and both its gradients are exactly 0.0; a zero seed gives densities that are exactly zero; an unflagged tracer is neither recorded, read nor written.
  * Usage: tracer_tape_create -> n x step_rk4_tracer_taped -> seed (per tracer) -> sweep -> download (per tracer).
- * Out of scope: sensitivities of the tracers to the flow (d phi_N / d (u, h)), a spatially varying or time-dependent kappa or kappaV and a
+ * Out of scope: sensitivities of the tracers to the flow (d phi_N / d (u, h)), a spatially varying or time-dependent kappa and a
  * per-step split of its gradient, second derivatives, time-dependent sources and a per-step
  * split of G, coupling to moka_tape, Forward Euler, partitioned meshes, fp32 storage. */
 typedef struct moka_tracer_tape moka_tracer_tape;

@@ -1454,9 +1454,11 @@ static hipError_t tracer_stage(moka_state *st, int s, const StageArgs &g)
 
 // The vertical pass (implicit vertical diffusion, include/moka_hip.h): forwards behind the stage-4 tracer launch on the new tracers with
 // the new thickness, backwards at the head of a reversed step on X with the recorded hn.  The callers skip it when K < 2, when dt == 0.0
-// and while every kappaV is zero.  *path takes the form that served it.  gslot (reverse only): the gradient instances, with the step's
-// recorded phi_new in p and the densities in D (moka_tracer_adjoint_want_vertical_gradient).
-static int tracer_vmix(moka_mesh *mm, moka_ctx *ctx, int nT, const double *h, double *x, const double *kv, double dt, double *scratch,
+// and while every kappaV is zero and no tracer has a diffusivity field that is on.  *path takes the form that served it.  fld: the
+// device table of the diffusivity fields (nullptr: none -- the scalar instances).  gslot (reverse only): the gradient instances, with the
+// step's recorded phi_new in p and the densities in D (moka_tracer_adjoint_want_vertical_gradient).
+static int tracer_vmix(moka_mesh *mm, moka_ctx *ctx, int nT, const double *h, double *x, const double *kv, const double *const *fld, double dt,
+                       double *scratch,
                        bool reverse, int *path, const int32_t *gslot = nullptr, const double *p_new = nullptr, double *D = nullptr)
 {
     const Plan &p = mm->plan;
@@ -1464,7 +1466,7 @@ static int tracer_vmix(moka_mesh *mm, moka_ctx *ctx, int nT, const double *h, do
         if (int rc = upload_vec(mm, p.nLev, &mm->nLev)) return rc;
     VmixArgs a{};
     a.nT = nT; a.nC = p.nC; a.K = p.K; a.stride = (int64_t)p.K * p.nC;
-    a.h = h; a.x = x; a.kv = kv; a.dt = dt; a.nLev = mm->nLev; a.scratch = scratch;
+    a.h = h; a.x = x; a.kv = kv; a.fld = fld; a.dt = dt; a.nLev = mm->nLev; a.scratch = scratch;
     a.gslot = gslot; a.p = p_new; a.D = D;
     const bool generic = ctx->variant == 3;
     *path = vmix_kernel(p.K, generic, gslot ? 4 : 3).form;
@@ -1488,6 +1490,14 @@ struct moka_tracer_tape {
     bool kvUsed = false;                             // some recorded step had a nonzero kappaV: slots of kv may hold old values
     double *vmScratch = nullptr;                     // 2 x (K, nC): the column form's g and y, allocated by the first sweep that has a vertical pass
     int vmixPath = 0;                                // moka_tracer_adjoint_vmix_path
+    // the diffusivity fields the recorded steps ran with (moka_tracer_vertical_field_upload).  A step copies a tracer's field only when
+    // the state's generation of it differs from that of the tape's newest copy; all of this is allocated by the first recorded step
+    // that sees a field that is on, and the copies are released when a sweep has emptied the tape.
+    std::vector<double *> vfCopies;                  // (K, nC) each
+    std::vector<int32_t> vfNewest;                   // nT: a tracer's newest copy in vfCopies, -1 none
+    std::vector<uint64_t> vfGen;                     // nT: ... and the generation it was taken at
+    std::vector<int32_t> vfStep;                     // n x nT once vfTab exists: the copy a recorded step ran with, -1 the scalar
+    double **vfTab = nullptr;                        // capacity x nT on the device: vfStep as the pointers the field instances read
     double *M = nullptr;                             // nT x (K, nC): Lap(ph_s, y) of a reverse stage (biharmonic term)
     double *X = nullptr, *g = nullptr, *S = nullptr, *y[2] = {nullptr, nullptr};   // nT x (K, nC) each: the adjoint state and the sweep's work arrays
     // gradient with respect to the sources (moka_tracer_adjoint_want_source_gradient): the (K, nC) accumulator of every tracer that was
@@ -1526,7 +1536,7 @@ struct moka_tracer_tape {
 static int step_rk4(moka_state *st, double dt, moka_tracer_tape *rec)
 {
     HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
-    const bool vmix = st->nTracers > 0 && st->trKappaVDev != nullptr;      // (non-null exactly while some kappaV != 0)
+    const bool vmix = st->nTracers > 0 && st->trKappaVDev != nullptr;      // (non-null exactly while some kappaV != 0 or some diffusivity field is on)
     if (vmix && dt < 0.0) return fail(st->ctx, MOKA_ERR_ARG, "vertical tracer diffusion: dt must be >= 0 (the implicit solve is not reversible in time)");
     const double *ssh0 = nullptr;
     int rc = rk4_begin(st, &ssh0);
@@ -1550,7 +1560,7 @@ static int step_rk4(moka_state *st, double dt, moka_tracer_tape *rec)
         HIPCHK(c, run_stage(st, g));
         if (st->nTracers > 0) HIPCHK(c, tracer_stage(st, s, g));
         if (s == 4 && vmix && st->mesh->plan.K >= 2 && dt != 0.0)       // the split step: the new tracers (still in the previous level's array) over the new thickness
-            if ((rc = tracer_vmix(st->mesh, c, st->nTracers, g.nh_out, st->trPhi[0], st->trKappaVDev, dt, st->trVmixScratch, false, &st->vmixPath))) return rc;
+            if ((rc = tracer_vmix(st->mesh, c, st->nTracers, g.nh_out, st->trPhi[0], st->trKappaVDev, st->trVfDev, dt, st->trVmixScratch, false, &st->vmixPath))) return rc;
         if (rec) {
             const Plan &p = st->mesh->plan;
             const size_t nEK = (size_t)p.K * p.nE, nCK = (size_t)p.K * p.nC;
@@ -1848,6 +1858,18 @@ static void drop_sources(moka_state *st)
     st->trSrcDev = nullptr;
 }
 
+// likewise for the diffusivity fields of the vertical pass (moka_tracer_vertical_field_upload, further down)
+static void drop_vfields(moka_state *st)
+{
+    for (double *q : st->trVf)
+        if (q) state_free(st, q);
+    st->trVf.clear();
+    st->trVfOn.clear();
+    st->trVfGen.clear();                 // (trVfClock goes on counting)
+    if (st->trVfDev) state_free(st, st->trVfDev);
+    st->trVfDev = nullptr;
+}
+
 int moka_tracer_source_upload(moka_state *st, int32_t j, const double *host)
 {
     if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
@@ -1923,6 +1945,7 @@ int moka_set_tracers(moka_state *st, int32_t nTracers)
                        &st->trKappaVDev, &st->trVmixScratch};
     auto release = [&]() {
         drop_sources(st);                // every source goes with the tracers
+        drop_vfields(st);                // ... and every diffusivity field
         for (double **q : arr) {
             if (!*q) continue;
             st->allocs.erase(std::remove(st->allocs.begin(), st->allocs.end(), (void *)*q), st->allocs.end());
@@ -2067,30 +2090,44 @@ int moka_tracer_biharmonic(const moka_state *st, int32_t j, double *out)
     return MOKA_OK;
 }
 
-int moka_set_tracer_vertical_diffusion(moka_state *st, const double *kappaV)
+// ---- what the vertical pass is to take for every tracer: its scalar, or its diffusivity field (include/moka_hip.h) ----
+static bool vfield_on(const moka_state *st, int j) { return !st->trVf.empty() && st->trVf[j] && st->trVfOn[j]; }
+
+// the coefficient the pass and a tape take for tracer j while the scalars are kv (empty = all zero): a field whose active entries are
+// all zero makes it 0.0; beside a field that is on it is not read
+static double vmix_coefficient(const moka_state *st, const std::vector<double> &kv, int j)
 {
-    if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
+    if (!st->trVf.empty() && st->trVf[j] && !st->trVfOn[j]) return 0.0;
+    return kv.empty() ? 0.0 : kv[j];
+}
+
+// Brings the device side in line with the scalars kv (empty = all zero) and the fields as they stand: the coefficient array, the table of
+// the fields that are on, nLev and the scratch of the column form exist exactly while the pass is on.  The caller has synchronised the
+// stream.  The scalars are taken over once nothing can fail any more.
+static int vmix_commit(moka_state *st, std::vector<double> kv)
+{
     const int nT = st->nTracers;
-    if (kappaV && nT == 0) return fail(st->ctx, MOKA_ERR_ARG, "vertical tracer diffusion: the state has no tracers (moka_set_tracers)");
-    bool any = false;
-    for (int j = 0; kappaV && j < nT; ++j) {
-        if (!(kappaV[j] >= 0.0) || !std::isfinite(kappaV[j]))
-            return fail(st->ctx, MOKA_ERR_ARG, "vertical tracer diffusion: every diffusivity must be finite and >= 0");
-        any = any || kappaV[j] != 0.0;
-    }
     moka_mesh *mm = st->mesh;
-    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
-    HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));      // no launch is reading the old values
+    std::vector<double> eff((size_t)nT, 0.0);
+    std::vector<double *> tab((size_t)nT, nullptr);
+    bool any = false, anyField = false;
+    for (int j = 0; j < nT; ++j) {
+        eff[j] = vmix_coefficient(st, kv, j);
+        if (vfield_on(st, j)) { tab[j] = st->trVf[j]; anyField = true; }
+        any = any || tab[j] || eff[j] != 0.0;
+    }
     auto drop = [&](double **q) {
         if (!*q) return;
         st->allocs.erase(std::remove(st->allocs.begin(), st->allocs.end(), (void *)*q), st->allocs.end());
         (void)hipFree(*q);
         *q = nullptr;
     };
+    if (std::all_of(kv.begin(), kv.end(), [](double k) { return k == 0.0; })) kv.clear();
+    if (!anyField) drop(reinterpret_cast<double **>(&st->trVfDev));
     if (!any) {
         drop(&st->trKappaVDev);
         drop(&st->trVmixScratch);
-        st->trKappaV.clear();
+        st->trKappaV = std::move(kv);
         return MOKA_OK;
     }
     const Plan &p = mm->plan;
@@ -2104,8 +2141,105 @@ int moka_set_tracer_vertical_diffusion(moka_state *st, const double *kappaV)
             drop(&st->trVmixScratch);
             return rc;
         }
-    if (int rc = h2d(st->ctx, st->trKappaVDev, kappaV, (size_t)nT * sizeof(double))) return rc;
-    st->trKappaV.assign(kappaV, kappaV + nT);
+    if (anyField && !st->trVfDev)
+        if (int rc = alloc_field(st, reinterpret_cast<double **>(&st->trVfDev), (size_t)nT, sizeof(double *))) return rc;
+    if (int rc = h2d(st->ctx, st->trKappaVDev, eff.data(), (size_t)nT * sizeof(double))) return rc;
+    if (anyField)
+        if (int rc = h2d(st->ctx, st->trVfDev, tab.data(), (size_t)nT * sizeof(double *))) return rc;
+    st->trKappaV = std::move(kv);
+    return MOKA_OK;
+}
+
+int moka_set_tracer_vertical_diffusion(moka_state *st, const double *kappaV)
+{
+    if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
+    const int nT = st->nTracers;
+    if (kappaV && nT == 0) return fail(st->ctx, MOKA_ERR_ARG, "vertical tracer diffusion: the state has no tracers (moka_set_tracers)");
+    for (int j = 0; kappaV && j < nT; ++j)
+        if (!(kappaV[j] >= 0.0) || !std::isfinite(kappaV[j]))
+            return fail(st->ctx, MOKA_ERR_ARG, "vertical tracer diffusion: every diffusivity must be finite and >= 0");
+    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));      // no launch is reading the old values
+    return vmix_commit(st, kappaV ? std::vector<double>(kappaV, kappaV + nT) : std::vector<double>());
+}
+
+int moka_tracer_vertical_field_upload(moka_state *st, int32_t j, const double *host)
+{
+    if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
+    if (st->nTracers == 0) return fail(st->ctx, MOKA_ERR_ARG, "vertical diffusivity field: the state has no tracers (moka_set_tracers)");
+    if (j < 0 || j >= st->nTracers) return fail(st->ctx, MOKA_ERR_ARG, "tracer index out of range (moka_set_tracers)");
+    const Plan &p = st->mesh->plan;
+    const size_t nCK = (size_t)p.K * p.nC;
+    bool on = false;                     // the host scan: the interfaces k < nLev[c] - 1 of every column, and nothing else
+    for (int i = 0; host && i < p.nC; ++i) {
+        const double *col = host + (size_t)p.cellN2O[i] * p.K;
+        for (int k = 0; k < p.nLev[i] - 1; ++k) {
+            if (!(col[k] >= 0.0) || !std::isfinite(col[k]))
+                return fail(st->ctx, MOKA_ERR_ARG, "vertical diffusivity field: every value at an active interface must be finite and >= 0");
+            on = on || col[k] != 0.0;
+        }
+    }
+    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));      // no launch is reading the old table or the old values
+    const bool had = !st->trVf.empty() && st->trVf[j];
+    if (!host && !had) return MOKA_OK;
+    // The new field goes into an array of its own and the old one stays until the device side has been brought in line: a failure
+    // on the way leaves the tracer with the field, the table and the generation it had.
+    double *fresh = nullptr;
+    if (host) {
+        if (int rc = alloc_field(st, &fresh, nCK)) return rc;
+        if (int rc = put_rows(st->mesh, fresh, host, MOKA_CELL, p.nC, p.K)) {
+            (void)hipStreamSynchronize(st->ctx->stream);
+            state_free(st, fresh);
+            return rc;
+        }
+    }
+    const std::vector<double *> vf0 = st->trVf;
+    const std::vector<char> on0 = st->trVfOn;
+    const std::vector<uint64_t> gen0 = st->trVfGen;
+    st->trVf.resize((size_t)st->nTracers, nullptr);
+    st->trVfOn.resize((size_t)st->nTracers, 0);
+    st->trVfGen.resize((size_t)st->nTracers, 0);
+    double *const old = st->trVf[j];
+    st->trVf[j] = fresh;
+    st->trVfOn[j] = fresh && on ? 1 : 0;
+    st->trVfGen[j] = st->trVfClock + 1;
+    if (std::all_of(st->trVf.begin(), st->trVf.end(), [](double *q) { return !q; })) {
+        st->trVf.clear();
+        st->trVfOn.clear();
+    }
+    if (int rc = vmix_commit(st, st->trKappaV)) {
+        (void)hipStreamSynchronize(st->ctx->stream);
+        st->trVf = vf0;
+        st->trVfOn = on0;
+        st->trVfGen = gen0;
+        if (fresh) state_free(st, fresh);
+        (void)vmix_commit(st, st->trKappaV);     // the table and the coefficients of the fields as they were
+        return rc;
+    }
+    ++st->trVfClock;
+    if (old) state_free(st, old);
+    return MOKA_OK;
+}
+
+int moka_tracer_vertical_field_download(moka_state *st, int32_t j, double *host)
+{
+    if (!st || !host) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    if (j < 0 || j >= st->nTracers) return fail(st->ctx, MOKA_ERR_ARG, "tracer index out of range (moka_set_tracers)");
+    const Plan &p = st->mesh->plan;
+    if (st->trVf.empty() || !st->trVf[j]) {
+        std::fill(host, host + (size_t)p.K * p.nC, 0.0);
+        return MOKA_OK;
+    }
+    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    return get_rows(st->mesh, host, st->trVf[j], MOKA_CELL, p.nC, p.K);
+}
+
+int moka_tracer_has_vertical_field(const moka_state *st, int32_t j, int *out)
+{
+    if (!st || !out) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    if (j < 0 || j >= st->nTracers) return fail(st->ctx, MOKA_ERR_ARG, "tracer index out of range (moka_set_tracers)");
+    *out = !st->trVf.empty() && st->trVf[j] ? 1 : 0;
     return MOKA_OK;
 }
 
@@ -2189,7 +2323,56 @@ int moka_step_rk4_tracer_taped(moka_tracer_tape *t, double dt)
     if (t->n >= t->capacity) return fail(t->ctx, MOKA_ERR_ARG, "tracer tape is full");
     if (st->nTracers != t->nT) return fail(t->ctx, MOKA_ERR_ARG, "tracer tape: the state's tracer count has changed since the tape was created");
     HIPCHK(t->ctx, hipSetDevice(t->ctx->device));
+    if (dt < 0.0 && st->trKappaVDev) return step_rk4(st, dt, t);      // (refused there, before any launch)
+    // the diffusivity fields the step is about to run with: a copy of every one the tape does not hold yet, allocated ahead of the
+    // step's first launch -- a failure leaves the state and the tape as they were
+    const Plan &p = st->mesh->plan;
+    const size_t nCK = (size_t)p.K * p.nC;
+    std::vector<int> fresh;
+    bool fields = false;
+    for (int j = 0; j < t->nT; ++j) {
+        if (!vfield_on(st, j)) continue;
+        fields = true;
+        if (t->vfNewest.empty() || t->vfNewest[j] < 0 || t->vfGen[j] != st->trVfGen[j]) fresh.push_back(j);
+    }
+    if (fields && !t->vfTab) {
+        if (int rc = ttape_alloc(t, reinterpret_cast<double **>(&t->vfTab), (size_t)t->capacity * t->nT * sizeof(double *) / sizeof(double))) return rc;
+        t->vfStep.assign((size_t)t->n * t->nT, -1);
+        t->vfNewest.assign((size_t)t->nT, -1);
+        t->vfGen.assign((size_t)t->nT, 0);
+    }
+    if (!fresh.empty()) {
+        std::vector<void *> got;
+        for (size_t i = 0; i < fresh.size(); ++i) {
+            void *d = nullptr;
+            if (hipError_t e = hipMalloc(&d, std::max<size_t>(nCK * sizeof(double), 16)); e != hipSuccess) {
+                for (void *q : got) (void)hipFree(q);
+                return fail(t->ctx, MOKA_ERR_ALLOC, std::string("tracer tape: hipMalloc of a diffusivity field: ") + hipGetErrorString(e));
+            }
+            got.push_back(d);
+        }
+        for (size_t i = 0; i < fresh.size(); ++i) {
+            const int j = fresh[i];
+            t->allocs.push_back(got[i]);
+            t->vfCopies.push_back(static_cast<double *>(got[i]));
+            t->vfNewest[j] = (int32_t)t->vfCopies.size() - 1;
+            t->vfGen[j] = st->trVfGen[j];
+            HIPCHK(t->ctx, hipMemcpyAsync(got[i], st->trVf[j], nCK * sizeof(double), hipMemcpyDeviceToDevice, t->ctx->stream));
+        }
+    }
     if (int rc = step_rk4(st, dt, t)) return rc;
+    if (t->vfTab) {                  // which copy the step ran with, per tracer
+        std::vector<double *> row((size_t)t->nT, nullptr);
+        for (int j = 0; j < t->nT; ++j) {
+            const int32_t i = vfield_on(st, j) ? t->vfNewest[j] : -1;
+            t->vfStep.push_back(i);
+            if (i >= 0) row[j] = t->vfCopies[i];
+        }
+        if (int rc = h2d(t->ctx, t->vfTab + (size_t)t->n * t->nT, row.data(), row.size() * sizeof(double *))) {
+            t->vfStep.resize((size_t)t->n * t->nT);
+            return rc;
+        }
+    }
     // the diffusivities the step's launches read (every copy on the context's stream, device to device: no host buffer to keep alive)
     double *kd = t->kap + (size_t)t->n * t->nT;
     if (st->trKappaDev) HIPCHK(t->ctx, hipMemcpyAsync(kd, st->trKappaDev, (size_t)t->nT * sizeof(double), hipMemcpyDeviceToDevice, t->ctx->stream));
@@ -2205,7 +2388,7 @@ int moka_step_rk4_tracer_taped(moka_tracer_tape *t, double dt)
         t->kvUsed = true;
     } else if (t->kvUsed)            // (the array is created zeroed: a tape that never saw a kappaV issues nothing here)
         HIPCHK(t->ctx, hipMemsetAsync(kvd, 0, (size_t)t->nT * sizeof(double), t->ctx->stream));
-    for (int j = 0; j < t->nT; ++j) t->kappaV.push_back(st->trKappaV.empty() ? 0.0 : st->trKappaV[j]);
+    for (int j = 0; j < t->nT; ++j) t->kappaV.push_back(vmix_coefficient(st, st->trKappaV, j));
     t->dts.push_back(dt);
     ++t->n;
     t->seeded = false;
@@ -2252,6 +2435,8 @@ int moka_tracer_adjoint_seed(moka_tracer_tape *t, int32_t j, const double *host)
     return put_rows(t->st->mesh, d, host, MOKA_CELL, p.nC, p.K);
 }
 
+static void ttape_free(moka_tracer_tape *t, void *q);
+
 int moka_tracer_adjoint_sweep(moka_tracer_tape *t)
 {
     if (!t) return fail(nullptr, MOKA_ERR_ARG, "tracer tape is NULL");
@@ -2282,11 +2467,16 @@ int moka_tracer_adjoint_sweep(moka_tracer_tape *t)
     const bool generic = t->ctx->variant == 3;
     const size_t nEK = (size_t)p.K * p.nE, nCK = (size_t)p.K * p.nC;
     // the vertical pass of a recorded step (its kappaV, its dt): skipped as in the forward step, unless some tracer is flagged for the
-    // vertical gradient -- then the gradient instances run, for a step whose kappaV are all zero the gradient alone
+    // vertical gradient -- then the gradient instances run, for a step whose kappaV are all zero the gradient alone.  A step that ran
+    // with a diffusivity field takes the field instances and its row of the table of copies.
     const size_t nV = t->vgTracer.size();
+    auto fields_of = [&](int64_t n) {
+        return !t->vfStep.empty() && std::any_of(t->vfStep.begin() + n * t->nT, t->vfStep.begin() + (n + 1) * t->nT, [](int32_t i) { return i >= 0; });
+    };
     auto vmix_of = [&](int64_t n) {
         return p.K >= 2 && t->dts[n] != 0.0 &&
-               (nV > 0 || std::any_of(t->kappaV.begin() + n * t->nT, t->kappaV.begin() + (n + 1) * t->nT, [](double k) { return k != 0.0; }));
+               (nV > 0 || fields_of(n) ||
+                std::any_of(t->kappaV.begin() + n * t->nT, t->kappaV.begin() + (n + 1) * t->nT, [](double k) { return k != 0.0; }));
     };
     for (int64_t n = 0; n < t->n && !t->vmScratch; ++n)
         if (vmix_of(n))
@@ -2300,7 +2490,8 @@ int moka_tracer_adjoint_sweep(moka_tracer_tape *t)
         const double b[4] = {dt / 6., dt / 3., dt / 3., dt / 6.};
         int cur = 0;
         if (vmix_of(n))             // S^T = diag(h) A^-1 on X, ahead of g = X / hn
-            if (int rc = tracer_vmix(mm, t->ctx, t->nT, t->hn + nCK * n, t->X, t->kv + (size_t)n * t->nT, dt, t->vmScratch, true, &t->vmixPath,
+            if (int rc = tracer_vmix(mm, t->ctx, t->nT, t->hn + nCK * n, t->X, t->kv + (size_t)n * t->nT,
+                                     fields_of(n) ? t->vfTab + (size_t)n * t->nT : nullptr, dt, t->vmScratch, true, &t->vmixPath,
                                      nV > 0 ? t->vgSlot : nullptr, nV > 0 ? t->vgP + nCK * ((size_t)n * nV) : nullptr, t->vgD)) return rc;
         HIPCHK(t->ctx, launch_tracer_adj_seed(dev, t->X, t->hn + nCK * n, t->g, t->y[cur], b[3], t->nT, G, s));
         for (int rs = 3; rs >= 0; --rs) {
@@ -2340,6 +2531,13 @@ int moka_tracer_adjoint_sweep(moka_tracer_tape *t)
         t->kappa.resize((size_t)n * t->nT);
         t->kappa4.resize((size_t)n * t->nT);
         t->kappaV.resize((size_t)n * t->nT);
+        if (!t->vfStep.empty()) t->vfStep.resize((size_t)n * t->nT);
+    }
+    if (!t->vfCopies.empty()) {         // the tape is empty: its copies of the diffusivity fields go once the sweep has read them
+        HIPCHK(t->ctx, hipStreamSynchronize(s));
+        for (double *q : t->vfCopies) ttape_free(t, q);
+        t->vfCopies.clear();
+        t->vfNewest.assign((size_t)t->nT, -1);
     }
     return MOKA_OK;
 }

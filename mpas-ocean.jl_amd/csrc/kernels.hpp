@@ -301,6 +301,8 @@ hipError_t launch_tracer_kgrad(const MeshDev &m, const TracerKgradArgs &a, int l
 // tracer launch, x = the new tracers and h the new thickness; reverse at the head of a reversed step, x = X and h the recorded hn.
 // Per column c with n = nLev[c] >= 2 and s = dt * kv[j] (the recipe of include/moka_hip.h):
 //   forward:  x = x + Solve(Lv(x))        reverse:  x = x + Lv(Solve(x))
+// fld != nullptr: the field instances.  A tracer j with fld[j] != nullptr takes s[k] = dt * fld[j][k,c] per interface and its kv[j] is
+// not read; one with fld[j] == nullptr takes dt * kv[j] as above (moka_tracer_vertical_field_upload).
 struct VmixArgs {
     int nT, nC, K;
     int64_t stride;               // K * nC: the fields of x lie this far apart
@@ -314,6 +316,8 @@ struct VmixArgs {
     const int32_t *gslot;         // nT: the slot f of a flagged tracer in p and D, -1 for an unflagged one
     const double *p;              // nF fields `stride` apart: the recorded phi_new of this step
     double *D;                    // nF fields `stride` apart: the densities, D[k,c] = D[k,c] - e
+    // the field instances only (moka_tracer_vertical_field_upload; nullptr otherwise):
+    const double *const *fld;     // nullptr, or nT device pointers: (K, nC) diffusivity per interface and cell, nullptr = the scalar kv[j]
 };
 // The kernel that serves the pass (tracer_vmix.hip holds the LDS formula): form 1 = k_vmix_tile over tiles of `tc` columns with `lds`
 // bytes of dynamic LDS, form 2 = k_vmix_column.  generic: the caller asks for form 2 (kernel variant 3).  sets: the column sets a

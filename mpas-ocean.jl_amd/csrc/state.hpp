@@ -133,6 +133,18 @@ struct moka_state {
     std::vector<double> trKappaV;
     double *trKappaVDev = nullptr, *trVmixScratch = nullptr;
     int vmixPath = 0;                 // moka_state_tracer_vmix_path
+    // diffusivity fields (moka_tracer_vertical_field_upload): only a tracer with a field owns a (K, nC) device array.  trVf holds nTracers
+    // pointers (nullptr = the scalar) and is empty while no tracer has a field; trVfOn[j]: the field has a nonzero value at an active
+    // interface (the host scan of the upload) -- one that has none counts as kappaV_j == 0.  trVfDev is the device table of the fields
+    // that are on, the one the field instances of the vertical pass read, nullptr while there is none: the pass is then the scalar
+    // one.  With fields, trKappaVDev holds what the pass is to take for a tracer -- 0.0 for one whose field is all zero -- and is
+    // non-null exactly while some such value is nonzero or some field is on.  trVfGen[j] takes the next value of trVfClock with every
+    // upload and removal (empty until the first upload): a tape compares it with that of its newest copy.
+    std::vector<double *> trVf;
+    std::vector<char> trVfOn;
+    std::vector<uint64_t> trVfGen;
+    uint64_t trVfClock = 0;
+    double **trVfDev = nullptr;
     // tracer sources (moka_tracer_source_upload): only a sourced tracer owns a (K, nC) device array.  trSrc holds nTracers pointers
     // (nullptr = no source) and is empty while no tracer has a source; trSrcDev is its copy on the device, the table the tracer
     // launches read -- nullptr while trSrc is empty: the launches are then those of a state that never had a source.  Sources do

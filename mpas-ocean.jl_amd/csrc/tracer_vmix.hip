@@ -22,9 +22,12 @@ namespace moka {
 //     p(k)                   the recorded field, read once, in ascending k, beside h(k)
 //     putC / c               c[k], formed on the way down where p[k], p[k+1], h[k], h[k+1] sit in registers
 //     emitE(k, e)            D[k] = D[k] - e (the tile form defers the subtraction to its write-back)
-// Levels k >= n are never touched.
+// FLD (a tracer with a diffusivity field, moka_tracer_vertical_field_upload): s is not one number but s[k] = dt * f[k] per interface,
+//     s(k)                   read once, in ascending k, beside h(k + 1) and before putY(k)
+// and nothing else changes: where f is uniform the product is the scalar's, hence every bit is.
+// Levels k >= n are never touched, and of the field no row k >= n - 1.
 // ------------------------------------------------------------------------------------------------
-template <bool REV, bool GRAD, class C>
+template <bool REV, bool GRAD, bool FLD, class C>
 __device__ __forceinline__ void vmix_column(C &c, const int n, const double s, const double dt)
 {
     static_assert(REV || !GRAD, "the gradient belongs to the reverse pass");
@@ -32,7 +35,7 @@ __device__ __forceinline__ void vmix_column(C &c, const int n, const double s, c
     double xm = 0.0, xk = c.x(0), xn = c.x(1);
     double pk = 0.0, pn = 0.0;
     double hm = 0.5 * (hk + hn);
-    double w = s / hm;                              // w[0]
+    double w = (FLD ? c.s(0) : s) / hm;             // w[0]
     if (GRAD) {
         pk = c.p(0); pn = c.p(1);
         c.putC(0, (pk - pn) * (dt / hm));
@@ -50,7 +53,7 @@ __device__ __forceinline__ void vmix_column(C &c, const int n, const double s, c
         if (k < n - 1) {
             hn = c.h(k + 1); xn = c.x(k + 1);
             hm = 0.5 * (hk + hn);
-            w = s / hm;
+            w = (FLD ? c.s(k) : s) / hm;
             d = (hk + wp) + w;
             r = REV ? xk : wp * (xm - xk) + w * (xn - xk);
             if (REV) c.putW(k, w);
@@ -113,6 +116,9 @@ __device__ __forceinline__ void vgrad_column_at_zero(C &c, const int n, const do
 // Gradient instances: a fourth set, staged with p beside h and X; its slot k takes c[k] on the way down (p[k] and p[k+1] are in
 // registers by then) and e[k] on the way up; the tile's span of D is then read, reduced by e and written back the way X is, interface
 // rows k < n - 1 only.  One field read and one read-modify-write more per flagged tracer, a column at 4 cs doubles.
+// Field instances: s[k] = dt * f[k] of a tracer with a diffusivity field is staged into set 2 beside h and the field; the sweep reads
+// slot k at iteration k, before it writes y[k] there, as g overwrites h -- no further set, the LDS formula and the choice of tc stand,
+// and the pass moves one more field per such tracer.  A tracer without a field stages nothing there and sweeps with its dt * kv.
 // vmix_kernel() holds the LDS formula and the choice of tc.
 // ------------------------------------------------------------------------------------------------
 constexpr int VM_NT = 64;             // threads of a tile-form workgroup: one wave
@@ -127,6 +133,7 @@ struct VmixTileCol {
     __device__ __forceinline__ double g(int k) const { return hs[k]; }
     __device__ __forceinline__ void putY(int k, double v) { ys[k] = v; }
     __device__ __forceinline__ double y(int k) const { return ys[k]; }
+    __device__ __forceinline__ double s(int k) const { return ys[k]; }          // field instances: staged where y[k] goes once s[k] is read
     __device__ __forceinline__ void putW(int k, double v) { xs[k] = v; }
     __device__ __forceinline__ double w(int k) const { return xs[k]; }
     __device__ __forceinline__ void emit(int k, double inc)
@@ -191,7 +198,7 @@ __device__ __forceinline__ void vm_write_back(double *dG, const double *S, const
     }
 }
 
-template <bool REV, bool GRAD>
+template <bool REV, bool GRAD, bool FLD>
 __device__ __forceinline__ void vmix_tile(const VmixArgs &a, const int tc, const int cs, const unsigned magic)
 {
     extern __shared__ __align__(16) unsigned char vm_smem[];
@@ -214,29 +221,34 @@ __device__ __forceinline__ void vmix_tile(const VmixArgs &a, const int tc, const
     for (int j = 0; j < a.nT; ++j) {
         const double kv = a.kv[j];
         const int f = GRAD ? a.gslot[j] : -1;       // wave-uniform, like kv
-        if (kv == 0.0 && f < 0) continue;           // such a tracer is neither read nor written
+        const double *const sF = FLD ? a.fld[j] : nullptr;      // ... and like the tracer's diffusivity field, which replaces kv
+        if (!(FLD && sF) && kv == 0.0 && f < 0) continue;       // such a tracer is neither read nor written
         double *fG = a.x + (size_t)j * a.stride + base;
         const double *pG = f >= 0 ? a.p + (size_t)f * a.stride + base : hG;
         double *dG = f >= 0 ? a.D + (size_t)f * a.stride + base : fG;
+        const double *sG = FLD && sF ? sF + base : hG;
         const bool vec = ((reinterpret_cast<uintptr_t>(hG) | reinterpret_cast<uintptr_t>(fG) | reinterpret_cast<uintptr_t>(pG) |
-                           reinterpret_cast<uintptr_t>(dG)) & 15) == 0;
+                           reinterpret_cast<uintptr_t>(dG) | reinterpret_cast<uintptr_t>(sG)) & 15) == 0;
         __syncthreads();                            // the previous tracer's write-back has read its sets
         for (unsigned e0 = 2u * tid; e0 < nEl; e0 += 2u * VM_NT * VM_U) {
-            double2 vh[VM_U], vx[VM_U], vp[VM_U];
+            double2 vh[VM_U], vx[VM_U], vp[VM_U], vs[VM_U];
 #pragma unroll
             for (int u = 0; u < VM_U; ++u) {
                 const unsigned e = e0 + 2u * VM_NT * u;
-                vh[u] = vx[u] = vp[u] = make_double2(0.0, 0.0);
+                vh[u] = vx[u] = vp[u] = vs[u] = make_double2(0.0, 0.0);
                 if (vec && e + 1 < nEl) {
                     vh[u] = *reinterpret_cast<const double2 *>(hG + e);
                     vx[u] = *reinterpret_cast<const double2 *>(fG + e);
                     if (GRAD && f >= 0) vp[u] = *reinterpret_cast<const double2 *>(pG + e);
+                    if (FLD && sF) vs[u] = *reinterpret_cast<const double2 *>(sG + e);
                 } else if (e < nEl) {
                     vh[u].x = hG[e]; vx[u].x = fG[e];
                     if (GRAD && f >= 0) vp[u].x = pG[e];
+                    if (FLD && sF) vs[u].x = sG[e];
                     if (e + 1 < nEl) {
                         vh[u].y = hG[e + 1]; vx[u].y = fG[e + 1];
                         if (GRAD && f >= 0) vp[u].y = pG[e + 1];
+                        if (FLD && sF) vs[u].y = sG[e + 1];
                     }
                 }
             }
@@ -248,64 +260,72 @@ __device__ __forceinline__ void vmix_tile(const VmixArgs &a, const int tc, const
                     const unsigned q = vm_slot(e, magic, K, cs, cc);
                     H[q] = vh[u].x; X[q] = vx[u].x;
                     if (GRAD && f >= 0) P[q] = vp[u].x;
+                    if (FLD && sF) Y[q] = a.dt * vs[u].x;       // s[k] = dt * f[k], the one product
                 }
                 if (e + 1 < nEl) {
                     const unsigned q = vm_slot(e + 1, magic, K, cs, cc);
                     H[q] = vh[u].y; X[q] = vx[u].y;
                     if (GRAD && f >= 0) P[q] = vp[u].y;
+                    if (FLD && sF) Y[q] = a.dt * vs[u].y;
                 }
             }
         }
         __syncthreads();
         if (n >= 2) {
             if (GRAD && f >= 0) {
-                if (kv != 0.0) vmix_column<REV, GRAD>(col, n, a.dt * kv, a.dt);
+                if (FLD && sF) vmix_column<REV, GRAD, true>(col, n, 0.0, a.dt);
+                else if (kv != 0.0) vmix_column<REV, GRAD, false>(col, n, a.dt * kv, a.dt);
                 else vgrad_column_at_zero(col, n, a.dt);
-            } else vmix_column<REV, false>(col, n, a.dt * kv, a.dt);
+            } else if (FLD && sF) vmix_column<REV, false, true>(col, n, 0.0, a.dt);
+            else vmix_column<REV, false, false>(col, n, a.dt * kv, a.dt);
         }
         __syncthreads();
         // back: forward the field set, reverse X + Lv; only the active levels of a column are written
         if (!REV) vm_write_back<0, 0>(fG, X, nl, vec, tid, nEl, magic, K, cs);
-        else if (kv != 0.0) vm_write_back<1, 0>(fG, Y, nl, vec, tid, nEl, magic, K, cs);
+        else if ((FLD && sF) || kv != 0.0) vm_write_back<1, 0>(fG, Y, nl, vec, tid, nEl, magic, K, cs);
         if (GRAD && f >= 0) vm_write_back<2, 1>(dG, P, nl, vec, tid, nEl, magic, K, cs);
     }
 }
 
-// the forward and the plain reverse pass, and the gradient instance of the reverse pass
-template <bool REV>
+// the forward and the plain reverse pass, and the gradient instance of the reverse pass; FLD: their field instances (a.fld != nullptr)
+template <bool REV, bool FLD>
 __global__ __launch_bounds__(VM_NT) void k_vmix_tile(const VmixArgs a, const int tc, const int cs, const unsigned magic)
 {
-    vmix_tile<REV, false>(a, tc, cs, magic);
+    vmix_tile<REV, false, FLD>(a, tc, cs, magic);
 }
 
+template <bool FLD>
 __global__ __launch_bounds__(VM_NT) void k_vmix_tile_grad(const VmixArgs a, const int tc, const int cs, const unsigned magic)
 {
-    vmix_tile<true, true>(a, tc, cs, magic);
+    vmix_tile<true, true, FLD>(a, tc, cs, magic);
 }
 
 // ------------------------------------------------------------------------------------------------
 // Form 2, column.  One lane per column straight from global memory; g and y in a global scratch of 2 * K * nC doubles laid out level-major
 // ((K, nC) transposed: the lanes of a wave store side by side); the reverse sweep forms w again from h, the same division with the same
 // operands, and the gradient instances c[k] again from p and h, likewise.  Any K, any mesh; the tracers of a column one after the
-// other, so one scratch serves them all.
+// other, so one scratch serves them all.  FLD: s[k] = dt * f[k] from the tracer's field column, the product formed again wherever w is.
 // ------------------------------------------------------------------------------------------------
+template <bool FLD>
 struct VmixGlobalCol {
     const double *hc;                 // the column's thickness
     double *fc;                       // ... and field
     double *gs, *ys;                  // scratch: element k at [k * nC]
     size_t nC;
-    double s;
+    double su;                        // dt * kappaV of a tracer without a field
     const double *pc;                 // gradient instances: the column's recorded phi_new
     double *dc;                       // ... and density
     double dt;
+    const double *sc;                 // field instances: the column's diffusivity field
     __device__ __forceinline__ double h(int k) const { return hc[k]; }
     __device__ __forceinline__ double x(int k) const { return fc[k]; }
+    __device__ __forceinline__ double s(int k) const { return dt * sc[k]; }
     __device__ __forceinline__ void putG(int k, double v) { gs[k * nC] = v; }
     __device__ __forceinline__ double g(int k) const { return gs[k * nC]; }
     __device__ __forceinline__ void putY(int k, double v) { ys[k * nC] = v; }
     __device__ __forceinline__ double y(int k) const { return ys[k * nC]; }
     __device__ __forceinline__ void putW(int, double) {}
-    __device__ __forceinline__ double w(int k) const { return s / (0.5 * (hc[k] + hc[k + 1])); }
+    __device__ __forceinline__ double w(int k) const { return (FLD ? dt * sc[k] : su) / (0.5 * (hc[k] + hc[k + 1])); }
     __device__ __forceinline__ void emit(int k, double inc) { fc[k] = fc[k] + inc; }
     __device__ __forceinline__ double p(int k) const { return pc[k]; }
     __device__ __forceinline__ void putC(int, double) {}
@@ -313,7 +333,7 @@ struct VmixGlobalCol {
     __device__ __forceinline__ void emitE(int k, double e) { dc[k] = dc[k] - e; }
 };
 
-template <bool REV, bool GRAD>
+template <bool REV, bool GRAD, bool FLD>
 __device__ __forceinline__ void vmix_columns(const VmixArgs &a)
 {
     const int c = blockIdx.x * BLOCK + threadIdx.x;
@@ -324,26 +344,37 @@ __device__ __forceinline__ void vmix_columns(const VmixArgs &a)
     for (int j = 0; j < a.nT; ++j) {
         const double kv = a.kv[j];
         const int f = GRAD ? a.gslot[j] : -1;
+        const double *const sF = FLD ? a.fld[j] : nullptr;
+        if (FLD && sF) {
+            VmixGlobalCol<true> col{a.h + off, a.x + (size_t)j * a.stride + off, a.scratch + c, a.scratch + nCK + c, (size_t)a.nC, 0.0,
+                                    f >= 0 ? a.p + (size_t)f * a.stride + off : nullptr, f >= 0 ? a.D + (size_t)f * a.stride + off : nullptr, a.dt,
+                                    sF + off};
+            if (GRAD && f >= 0) vmix_column<REV, GRAD, true>(col, n, 0.0, a.dt);
+            else vmix_column<REV, false, true>(col, n, 0.0, a.dt);
+            continue;
+        }
         if (kv == 0.0 && f < 0) continue;
         const double s = a.dt * kv;
-        VmixGlobalCol col{a.h + off, a.x + (size_t)j * a.stride + off, a.scratch + c, a.scratch + nCK + c, (size_t)a.nC, s,
-                          f >= 0 ? a.p + (size_t)f * a.stride + off : nullptr, f >= 0 ? a.D + (size_t)f * a.stride + off : nullptr, a.dt};
+        VmixGlobalCol<false> col{a.h + off, a.x + (size_t)j * a.stride + off, a.scratch + c, a.scratch + nCK + c, (size_t)a.nC, s,
+                                 f >= 0 ? a.p + (size_t)f * a.stride + off : nullptr, f >= 0 ? a.D + (size_t)f * a.stride + off : nullptr, a.dt,
+                                 nullptr};
         if (GRAD && f >= 0) {
-            if (kv != 0.0) vmix_column<REV, GRAD>(col, n, s, a.dt);
+            if (kv != 0.0) vmix_column<REV, GRAD, false>(col, n, s, a.dt);
             else vgrad_column_at_zero(col, n, a.dt);
-        } else vmix_column<REV, false>(col, n, s, a.dt);
+        } else vmix_column<REV, false, false>(col, n, s, a.dt);
     }
 }
 
-template <bool REV>
+template <bool REV, bool FLD>
 __global__ __launch_bounds__(BLOCK) void k_vmix_column(const VmixArgs a)
 {
-    vmix_columns<REV, false>(a);
+    vmix_columns<REV, false, FLD>(a);
 }
 
+template <bool FLD>
 __global__ __launch_bounds__(BLOCK) void k_vmix_column_grad(const VmixArgs a)
 {
-    vmix_columns<true, true>(a);
+    vmix_columns<true, true, FLD>(a);
 }
 
 // The kernel that serves a vertical pass, chosen in one place for the launcher, moka_state_tracer_vmix_path and
@@ -387,11 +418,16 @@ hipError_t launch_tracer_vmix(const VmixArgs &a, bool reverse, bool generic, hip
     if (a.nT <= 0 || a.nC <= 0 || a.K < 2) return hipSuccess;
     if (a.gslot) {
         if (!reverse || !a.p || !a.D) return hipErrorInvalidValue;
-        return launch_vmix_with(k_vmix_tile_grad, k_vmix_column_grad, a, vmix_kernel(a.K, generic, 4), s);
+        const VmixKernel k = vmix_kernel(a.K, generic, 4);
+        return a.fld ? launch_vmix_with(k_vmix_tile_grad<true>, k_vmix_column_grad<true>, a, k, s)
+                     : launch_vmix_with(k_vmix_tile_grad<false>, k_vmix_column_grad<false>, a, k, s);
     }
-    const VmixKernel k = vmix_kernel(a.K, generic);
-    return reverse ? launch_vmix_with(k_vmix_tile<true>, k_vmix_column<true>, a, k, s)
-                   : launch_vmix_with(k_vmix_tile<false>, k_vmix_column<false>, a, k, s);
+    const VmixKernel k = vmix_kernel(a.K, generic);       // (the field instances stage s into set 2: the same sets, the same tiles)
+    if (a.fld)
+        return reverse ? launch_vmix_with(k_vmix_tile<true, true>, k_vmix_column<true, true>, a, k, s)
+                       : launch_vmix_with(k_vmix_tile<false, true>, k_vmix_column<false, true>, a, k, s);
+    return reverse ? launch_vmix_with(k_vmix_tile<true, false>, k_vmix_column<true, false>, a, k, s)
+                   : launch_vmix_with(k_vmix_tile<false, false>, k_vmix_column<false, false>, a, k, s);
 }
 
 }  // namespace moka

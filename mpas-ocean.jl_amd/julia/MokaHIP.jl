@@ -547,6 +547,29 @@ function tracer_has_source(Prog::MProg, j::Integer)
     check(ccall((:moka_tracer_has_source, lib), Cint, (Ptr{Cvoid}, Int32, Ref{Cint}), s.handle, j - 1, out), s.backend.ctx)
     out[] != 0
 end
+# A vertical diffusivity per interface and cell (include/moka_hip.h): f of tracer j (1-based), a (nVertLevels, nCells) matrix in m^2/s,
+# row k the interface between levels k and k+1, finite and >= 0 at every active interface (rows at or below a cell's deepest interface
+# are never read); nothing removes it, and the tracer's scalar acts again.  Takes effect with the next RK4 step.
+function set_tracer_vertical_field!(Prog::MProg, j::Integer, f::Union{Matrix{Float64}, Nothing})
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    p = f === nothing ? Ptr{Float64}(C_NULL) : pointer(f)
+    GC.@preserve f check(ccall((:moka_tracer_vertical_field_upload, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), s.handle, j - 1, p), s.backend.ctx)
+end
+# the diffusivity field of tracer j (1-based) into `out` (zeros when it has none)
+function tracer_vertical_field!(out::Matrix{Float64}, Prog::MProg, j::Integer)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    check(ccall((:moka_tracer_vertical_field_download, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), s.handle, j - 1, out), s.backend.ctx)
+    out
+end
+function tracer_has_vertical_field(Prog::MProg, j::Integer)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    out = Ref{Cint}(0)
+    check(ccall((:moka_tracer_has_vertical_field, lib), Cint, (Ptr{Cvoid}, Int32, Ref{Cint}), s.handle, j - 1, out), s.backend.ctx)
+    out[] != 0
+end
 # 1 the patch form, 2 the generic form of the tracer kernel served the last RK4 stage, 0 none yet
 function tracer_path(Prog::MProg)
     s = Prog.ssh[end].state

@@ -690,6 +690,35 @@ class Tracers:
         """moka_state_tracer_vmix_path: 1 the tile form, 2 the column form of the vertical pass, 0 before the first one."""
         return int(L.lib().moka_state_tracer_vmix_path(self._s._h))
 
+    def set_vertical_field(self, j: int, field):
+        """moka_tracer_vertical_field_upload: a vertical diffusivity per interface and cell for tracer j (m^2/s, finite and >= 0 at
+        every active interface).  `field`: an (nCells, K) array in the layout of every tracer field, column k the interface between
+        levels k and k+1 (the last column, and every row at or below a cell's deepest interface, is never read and may hold anything);
+        or a profile of K or K-1 values, taken for every cell; None removes the field, and the tracer's scalar acts again.  While the
+        tracer has a field its scalar vertical diffusivity is not read.  Takes effect with the next RK4 step or run."""
+        a = None
+        if field is not None:
+            a = np.asarray(field, dtype=np.float64)
+            nC, K = self.shape
+            if a.ndim == 1 and a.size in (K, K - 1):
+                prof = np.zeros(K)
+                prof[:a.size] = a
+                a = np.broadcast_to(prof, (nC, K))
+            elif a.shape != self.shape:
+                raise ValueError(f"vertical field: shape {a.shape}; expected {self.shape} or a profile of {K} or {K - 1} values")
+            a = np.ascontiguousarray(a, dtype=np.float64)
+        L.check(L.lib().moka_tracer_vertical_field_upload(self._s._h, int(j), None if a is None else L.f64(a)), self._s.mesh.backend._h)
+
+    def vertical_field(self, j: int):
+        """moka_tracer_vertical_field_download: the diffusivity field of tracer j as it was uploaded, or None when it has none."""
+        v = C.c_int()
+        L.check(L.lib().moka_tracer_has_vertical_field(self._s._h, int(j), C.byref(v)), self._s.mesh.backend._h)
+        if not v.value:
+            return None
+        out = np.empty(self.shape, dtype=np.float64)
+        L.check(L.lib().moka_tracer_vertical_field_download(self._s._h, int(j), L.f64(out)), self._s.mesh.backend._h)
+        return out
+
     def set_source(self, j: int, a):
         """moka_tracer_source_upload: the source q_j of tracer j, an (nCells, K) field in tracer * m/s (the rate of change of the
         content h phi), constant in time until changed; None removes it.  Takes effect with the next RK4 step or run.  Every value
@@ -720,7 +749,7 @@ def set_tracers(Prog: "PrognosticVars", arrays, *positional, vertical=None, diff
     sources: one entry per tracer, an (nCells, K) field or None for a tracer without a source (Tracers.set_source).
     biharmonic: a scalar or one coefficient per tracer (Tracers.set_biharmonic); None leaves the term off.
     vertical (keyword only): a scalar or one vertical diffusivity per tracer (Tracers.set_vertical_diffusivity); None leaves the term
-    off.  Arguments given by position beyond `arrays` are diffusivity, sources, biharmonic, as they always were."""
+    off.  An entry of a per-tracer list may be an array instead: that tracer's diffusivity field (Tracers.set_vertical_field).  Arguments given by position beyond `arrays` are diffusivity, sources, biharmonic, as they always were."""
     if len(positional) > 3:
         raise TypeError("set_tracers: at most diffusivity, sources, biharmonic by position")
     diffusivity, sources, biharmonic = (list(positional) + [diffusivity, sources, biharmonic][len(positional):])
@@ -735,7 +764,14 @@ def set_tracers(Prog: "PrognosticVars", arrays, *positional, vertical=None, diff
         tr.set_diffusivity(diffusivity)
     if biharmonic is not None:
         tr.set_biharmonic(biharmonic)
-    if vertical is not None:
+    if isinstance(vertical, (list, tuple)) and any(np.ndim(v) > 0 for v in vertical):
+        if len(vertical) != len(arrays):
+            raise ValueError(f"vertical: {len(vertical)} entries for {len(arrays)} tracers")
+        tr.set_vertical_diffusivity([0.0 if np.ndim(v) > 0 else float(v) for v in vertical])
+        for j, v in enumerate(vertical):
+            if np.ndim(v) > 0:
+                tr.set_vertical_field(j, v)
+    elif vertical is not None:
         tr.set_vertical_diffusivity(vertical)
     if sources is not None:
         sources = list(sources)
@@ -898,14 +934,17 @@ class TracerAdjointTape:
 
     def vertical_gradient(self, j: int) -> float:
         """d J / d kappaV_j as it stands (after a sweep: the derivative with respect to a vertical diffusivity that acts identically in
-        every recorded step): the sum of vertical_density(j) over interfaces and cells."""
+        every recorded step): the sum of vertical_density(j) over interfaces and cells.  For a tracer that ran with a diffusivity field
+        (Tracers.set_vertical_field) this is the directional derivative along the all-ones field."""
         out = C.c_double()
         L.check(L.lib().moka_tracer_adjoint_vertical_gradient(self._h, int(j), C.byref(out)), self._ctx)
         return float(out.value)
 
     def vertical_density(self, j: int, view: str = "interface") -> np.ndarray:
         """The sensitivity density of d J / d kappaV_j in the caller's numbering.  view="interface": (nCells, K), column k the interface
-        between levels k and k+1 (d J / d kappaV at that interface of that cell; columns k >= the cell's active depth - 1 are zero);
+        between levels k and k+1 (d J / d kappaV at that interface of that cell -- the derivative with respect to the diffusivity field
+        the steps ran with, Tracers.set_vertical_field, or, for a scalar, to a field at that uniform value; columns k >= the cell's
+        active depth - 1 are zero);
         "cell": its sums over the interfaces, nCells values; "profile": its sums over the cells, K values."""
         views = {"interface": (L.VGRAD_INTERFACE, self._shape), "cell": (L.VGRAD_CELL, self._shape[0]), "profile": (L.VGRAD_PROFILE, self._shape[1])}
         if view not in views:

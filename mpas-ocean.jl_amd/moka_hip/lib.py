@@ -107,6 +107,7 @@ EXPORTS = [
     "moka_set_tracer_biharmonic", "moka_tracer_biharmonic",
     "moka_set_tracer_vertical_diffusion", "moka_tracer_vertical_diffusion", "moka_state_tracer_vmix_path", "moka_tracer_adjoint_vmix_path",
     "moka_tracer_source_upload", "moka_tracer_source_download", "moka_tracer_has_source",
+    "moka_tracer_vertical_field_upload", "moka_tracer_vertical_field_download", "moka_tracer_has_vertical_field",
     "moka_tracer_adjoint_want_source_gradient", "moka_tracer_adjoint_source_download",
     "moka_tracer_adjoint_want_diffusivity_gradient", "moka_tracer_adjoint_diffusivity_gradient",
     "moka_tracer_adjoint_diffusivity_density_download",
@@ -273,6 +274,9 @@ def lib():
     L.moka_tracer_source_upload.argtypes = [vp, C.c_int32, vp]
     L.moka_tracer_source_download.argtypes = [vp, C.c_int32, vp]
     L.moka_tracer_has_source.argtypes = [vp, C.c_int32, C.POINTER(C.c_int)]
+    L.moka_tracer_vertical_field_upload.argtypes = [vp, C.c_int32, vp]
+    L.moka_tracer_vertical_field_download.argtypes = [vp, C.c_int32, vp]
+    L.moka_tracer_has_vertical_field.argtypes = [vp, C.c_int32, C.POINTER(C.c_int)]
     L.moka_tracer_adjoint_want_source_gradient.argtypes = [vp, C.c_int32, C.c_int]
     L.moka_tracer_adjoint_source_download.argtypes = [vp, C.c_int32, vp]
     L.moka_tracer_adjoint_want_diffusivity_gradient.argtypes = [vp, C.c_int32, C.c_int, C.c_int]

@@ -111,25 +111,31 @@ def sign_index_fields(cellsOnEdge, verticesOnEdge, nEdgesOnCell, edgesOnCell, ed
 # planar periodic hexagons (SURVEY.md Appendix B recipe; coordinates as MPAS `planar_hex`)
 # --------------------------------------------------------------------------------------------
 
-def planar_hex_mesh(nx: int, ny: int, dc: float, f0: float = 0.0) -> MeshData:
-    if ny % 2:
-        raise ValueError("ny must be even for a doubly periodic hex mesh")
+def planar_hex_mesh(nx: int, ny: int, dc: float, f0: float = 0.0, sheared: bool = False) -> MeshData:
+    """sheared: the rows are not staggered back and forth but each half a cell to the right of the one below (a rhombic patch of the
+    same hexagons), and the wrap in y closes it as a sheared torus.  Every cell still has its six neighbours, and ny may be odd -- the
+    staggered mesh needs an even ny to close --, which gives meshes with an odd cell count."""
+    if ny % 2 and not sheared:
+        raise ValueError("ny must be even for a doubly periodic hex mesh (or sheared=True)")
+    if sheared and (nx < 3 or ny < 3):
+        raise ValueError("a sheared mesh needs nx, ny >= 3")
     nC, nE, nV = nx * ny, 3 * nx * ny, 2 * nx * ny
     r, c = np.divmod(np.arange(nC), nx)
     even = (r % 2) == 0
+    up, down = (np.ones(nC, dtype=bool), np.zeros(nC, dtype=bool)) if sheared else (even, even)   # which stagger the rows above / below have
 
     def cid(rr, cc):
         return (rr % ny) * nx + (cc % nx)
 
     E = cid(r, c + 1)
-    NE = np.where(even, cid(r + 1, c), cid(r + 1, c + 1))
-    NW = np.where(even, cid(r + 1, c - 1), cid(r + 1, c))
+    NE = np.where(up, cid(r + 1, c), cid(r + 1, c + 1))
+    NW = np.where(up, cid(r + 1, c - 1), cid(r + 1, c))
     W = cid(r, c - 1)
-    SW = np.where(even, cid(r - 1, c - 1), cid(r - 1, c))
-    SE = np.where(even, cid(r - 1, c), cid(r - 1, c + 1))
+    SW = np.where(down, cid(r - 1, c - 1), cid(r - 1, c))
+    SE = np.where(down, cid(r - 1, c), cid(r - 1, c + 1))
     nbr = np.stack([E, NE, NW, W, SW, SE], axis=1)  # CCW from 0 degrees
 
-    xC = np.where(even, dc * (c + 0.5), dc * (c + 1.0)).astype(F64)
+    xC = (dc * (c + 0.5 + 0.5 * r) if sheared else np.where(even, dc * (c + 0.5), dc * (c + 1.0))).astype(F64)
     yC = (dc * (r + 1.0) * math.sqrt(3.0) / 2.0).astype(F64)
 
     # edges: cell owns d = 0,1,2 (towards E, NE, NW)
@@ -222,7 +228,7 @@ def planar_hex_mesh(nx: int, ny: int, dc: float, f0: float = 0.0) -> MeshData:
         areaTriangle=np.full(nV, math.sqrt(3.0) / 4.0 * dc * dc),
         edgesOnVertex=edgesOnVertex, cellsOnVertex=(cellsOnVertex0 + 1).astype(I32),
         edgeSignOnVertex=esv, on_sphere=False, is_periodic=True,
-        meta={"kind": "planar_hex", "nx": nx, "ny": ny, "dc": dc},
+        meta={"kind": "planar_hex", "nx": nx, "ny": ny, "dc": dc, "sheared": bool(sheared)},
         kiteAreasOnVertex=np.full((nV, 3), math.sqrt(3.0) / 12.0 * dc * dc),      # a third of the triangle each
     )
 
