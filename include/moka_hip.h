@@ -734,6 +734,66 @@ int  moka_tracer_vertical_field_download(moka_state *st, int32_t j, double *host
 /* *out = 1 when tracer j has a diffusivity field, else 0; MOKA_ERR_ARG for j out of range or a NULL out */
 int  moka_tracer_has_vertical_field(const moka_state *st, int32_t j, int *out);
 
+/* ---- implicit vertical mixing of momentum with a surface stress and a bottom drag (extension; default off) -----------
+ * The other half of what MPAS-Ocean's vmix does, and the first forcing of this model.  nuV >= 0 (m^2/s) and a linear bottom drag
+ * r >= 0 (m/s) are one scalar each per state; tau_e (m^2/s^2: wind stress over rho0 along the edge normal) is an optional field of
+ * nEdges doubles.  After stage 4 of the RK4 step has formed the new level (u*, h_new) the step is split, per edge column:
+ *   (h_e u_new)[k] - dt d/dz(nuV d/dz u_new)[k] = (h_e u*)[k],      top flux = tau_e,   bottom flux = -r * u_new[n-1]
+ * -- backward Euler, unconditionally stable; nothing else in the step changes.
+ * Arithmetic.  For edge e with n = maxLevelEdgeTop[e] (at most nVertLevels) and c1, c2 = cellsOnEdge, every operation below rounded
+ * once, nothing contracted; x[k] = u*[k,e]; h[k] = 0.5 * (h_new[k,c1] + h_new[k,c2]), the hE of the tracer recipe; s = dt * nuV,
+ * q = dt * r, b = dt * tau[e], one product each; Lv and Solve those of the tracer recipe above:
+ *   w[k]  = s / (0.5 * (h[k] + h[k+1]))                      k = 0 .. n-2
+ *   d[0]  = h[0] + w[0];  d[k] = (h[k] + w[k-1]) + w[k];  d[n-1] = h[n-1] + w[n-2]      (n == 1: d[0] = h[0])
+ *   drag on (r != 0):     d[n-1] = d[n-1] + q
+ *   R     = Lv(x)                                             (n == 1: R[0] = 0.0)
+ *   stress present:       R[0]   = R[0] + b
+ *   drag on:              R[n-1] = R[n-1] - q * x[n-1]        (after the stress addition when n == 1)
+ *   u_new = x + Solve(R)                                      (Solve with this d; n == 1: y[0] = R[0] / d[0])
+ * This is the increment form of A u_new = h o u* + b e_0 with A = diag(h) + s W + q e_{n-1} e_{n-1}^T; A is symmetric and strictly
+ * diagonally dominant for h > 0: no pivoting.  h > 0 on active levels is required and not checked.
+ * The stress and drag lines are wave-uniform switches, not added zeros: a state with r == 0 and no stress runs the nuV-only
+ * arithmetic.  A stress that is zero at every edge with n >= 1 (found by the host scan of the upload) counts as absent.
+ * Which columns: a column is computed when n >= 2, or when n == 1 and drag or stress is on.  Edges with n == 0 are never touched and
+ * their cells never read; the same for n == 1 with only nuV on.  Levels k >= n of u and of both cells' h are neither read into
+ * arithmetic nor written.
+ * Hence: without drag and stress a depth-uniform column has Lv(x) == 0 exactly and comes back bit for bit; the column momentum obeys
+ * sum_k h u_new - sum_k h u* = dt tau - dt r u_new[n-1] to round-off; without stress sum_k h u_new^2 does not grow, and without stress
+ * and drag every value stays inside the column's former range (A^-1 diag(h) is row-stochastic and non-negative); the profile
+ * u[n-1] = tau / r, u[k] - u[k+1] = tau hm[k] / nuV is a fixed point.
+ * "The pass is on": nuV != 0, or r != 0, or a stress is present with a nonzero entry at an edge with n >= 1.  While it is off a step
+ * launches, allocates and records exactly what it does without this extension.  The launch is skipped for dt == 0.0 (and for
+ * nVertLevels == 1 with only nuV on); dt < 0 with the pass on is MOKA_ERR_ARG before any launch (moka_step_rk4, moka_run,
+ * moka_step_rk4_tracer_taped).  The pass runs behind stage 4 of moka_step_rk4 in the 16- and the 13-stream form, over the linear, the
+ * nonlinear, the Del2 and the Del4 dycore, inside the graph moka_run replays (the step allocates nothing, synchronises nothing and
+ * reads nothing back); ssh of the new level depends on h only and stays valid; the lazily produced stage-4 tendencies are those of the
+ * provisional state and are untouched; the diagnostics of the new level come from the mixed u.  Tracers never see the pass inside a
+ * step -- their stage 4 reads the provisional flow -- so their launches, their tape and the tracer vertical pass keep their arithmetic;
+ * they see a different flow from the next step on.
+ * Values take effect with the next RK4 step or moka_run.  MOKA_ERR_ARG, with nothing changed, for a negative, NaN or infinite nuV or r,
+ * a NaN or infinite stress value and NULL out-pointers.  MOKA_ERR_UNSUPPORTED, for a call that asks for a nonzero value or uploads a
+ * stress, on fp32-storage states, states with a halo or on a partitioned mesh, and states that have a moka_tape.  While the pass is on
+ * moka_step_fe, moka_run(MOKA_FORWARD_EULER), moka_tape_create, moka_halo_create and the moka_rk4_dist_* calls return
+ * MOKA_ERR_UNSUPPORTED.  The first call that turns the pass on allocates the column form's scratch of 2 * nVertLevels * nEdges doubles;
+ * no step allocates anything.  moka_state_optimize_placement neither times nor moves the new arrays.
+ * Out of scope: reverse mode through the pass (the operator depends on h_new, so the flow adjoint gains thickness terms), a nuV field
+ * per interface and edge, quadratic drag, closures (Richardson number, KPP), Forward Euler, fp32 storage, partitioned meshes, YAML keys
+ * and NetCDF I/O, a time-dependent stress other than by a new upload between steps. */
+int  moka_set_vertical_viscosity(moka_state *st, double nuV, double bottomDrag);
+/* the two scalars as they stand; MOKA_ERR_ARG for a NULL out-pointer */
+int  moka_vertical_viscosity(const moka_state *st, double *nuV, double *bottomDrag);
+/* host: nEdges doubles in the caller's edge numbering; NULL removes the stress.  The call synchronises the stream before it replaces an
+ * array a launch may still read. */
+int  moka_surface_stress_upload(moka_state *st, const double *host);
+/* the stress into host (nEdges doubles; zeros when there is none); MOKA_ERR_ARG for a NULL host */
+int  moka_surface_stress_download(moka_state *st, double *host);
+/* *out = 1 when a stress is present (all-zero ones included), else 0; MOKA_ERR_ARG for a NULL out */
+int  moka_has_surface_stress(const moka_state *st, int *out);
+/* which kernel served the last momentum pass of this state: 1 the tile form (tiles of edge columns staged in LDS, the edge thickness
+ * gathered from the two cell columns; nVertLevels <= 105), 2 the column form (a lane per edge from global memory: deeper columns,
+ * nVertLevels == 1 and kernel variant 3), 0 no pass yet */
+int  moka_state_momentum_vmix_path(const moka_state *st);
+
 /* ---- reverse mode of passive tracer transport over a frozen flow (extension) ---------------------------------------
  * Once the flow is given the tracer step above is linear in phi, so d J(phi_N) / d phi_0 is the exact transpose of a linear map.  It
  * needs no adjoint of the dycore, only the provisional states the step forms anyway, and therefore works over the linear, nonlinear,

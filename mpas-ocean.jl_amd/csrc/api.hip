@@ -1250,6 +1250,7 @@ int moka_step_fe(moka_state *st, double dt, int flags)
     if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
     if (st->nonlinear) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "nonlinear terms: moka_tendencies / RK4 only");
     if (st->nTracers > 0) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "tracers: transported by RK4 steps only (no Forward Euler)");
+    if (mom_vmix_on(st)) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "vertical momentum mixing: applied by RK4 steps only (no Forward Euler)");
     HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
     const moka_mesh *mm = st->mesh;
     const bool whole = mm->plan.nPatchesLaunch == mm->plan.nPatches;
@@ -1474,6 +1475,24 @@ static int tracer_vmix(moka_mesh *mm, moka_ctx *ctx, int nT, const double *h, do
     return MOKA_OK;
 }
 
+// The vertical pass of the flow (implicit vertical mixing of momentum with a surface stress and a bottom drag, include/moka_hip.h): behind
+// stage 4 on the new level's normalVelocity and layerThickness, through the same two pointers in the 16- and the 13-stream form.  The
+// caller skips it while the pass is off and when dt == 0.0.  Launches only: nothing is allocated, synchronised or read back, so a
+// captured step replays it.
+static int momentum_vmix(moka_state *st, double *u, const double *h, double dt)
+{
+    const Plan &p = st->mesh->plan;
+    MomVmixArgs a{};
+    a.nE = p.nE; a.K = p.K; a.ehdr = st->mesh->dev.ehdr; a.u = u; a.h = h;
+    a.tau = st->momTau && st->momTauOn ? st->momTau : nullptr;
+    a.dt = dt; a.nu = st->momNuV; a.drag = st->momDrag; a.scratch = st->momScratch;
+    if (p.K < 2 && a.drag == 0.0 && !a.tau) return MOKA_OK;      // one level and the viscosity alone: no column has anything to do
+    const bool generic = st->ctx->variant == 3;
+    HIPCHK(st->ctx, launch_momentum_vmix(a, generic, st->ctx->stream));
+    st->momVmixPath = momentum_vmix_form(p.K, generic);
+    return MOKA_OK;
+}
+
 // Tape of the tracer reverse mode (moka_tracer_tape_*, further down).  Per recorded step: the four provisional states the stage launches
 // read, the new level's thickness and the diffusivities in force -- K * (4 nEdges + 5 nCells) doubles and nTracers more.
 struct moka_tracer_tape {
@@ -1538,6 +1557,8 @@ static int step_rk4(moka_state *st, double dt, moka_tracer_tape *rec)
     HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
     const bool vmix = st->nTracers > 0 && st->trKappaVDev != nullptr;      // (non-null exactly while some kappaV != 0 or some diffusivity field is on)
     if (vmix && dt < 0.0) return fail(st->ctx, MOKA_ERR_ARG, "vertical tracer diffusion: dt must be >= 0 (the implicit solve is not reversible in time)");
+    const bool mvmix = mom_vmix_on(st);
+    if (mvmix && dt < 0.0) return fail(st->ctx, MOKA_ERR_ARG, "vertical momentum mixing: dt must be >= 0 (the implicit solve is not reversible in time)");
     const double *ssh0 = nullptr;
     int rc = rk4_begin(st, &ssh0);
     if (rc) return rc;
@@ -1561,6 +1582,8 @@ static int step_rk4(moka_state *st, double dt, moka_tracer_tape *rec)
         if (st->nTracers > 0) HIPCHK(c, tracer_stage(st, s, g));
         if (s == 4 && vmix && st->mesh->plan.K >= 2 && dt != 0.0)       // the split step: the new tracers (still in the previous level's array) over the new thickness
             if ((rc = tracer_vmix(st->mesh, c, st->nTracers, g.nh_out, st->trPhi[0], st->trKappaVDev, st->trVfDev, dt, st->trVmixScratch, false, &st->vmixPath))) return rc;
+        if (s == 4 && mvmix && dt != 0.0)       // the split step of the flow: the new normalVelocity over the new thickness (the tracers' stage 4 has read the provisional flow)
+            if ((rc = momentum_vmix(st, g.nu_out, g.nh_out, dt))) return rc;
         if (rec) {
             const Plan &p = st->mesh->plan;
             const size_t nEK = (size_t)p.K * p.nE, nCK = (size_t)p.K * p.nC;
@@ -1632,6 +1655,10 @@ int moka_run(moka_state *st, int integrator, double dt, int64_t nsteps, int flag
     if (integrator != MOKA_FORWARD_EULER && integrator != MOKA_RUNGE_KUTTA_4) return fail(st->ctx, MOKA_ERR_ARG, "unknown integrator");
     if (integrator == MOKA_RUNGE_KUTTA_4 && dt < 0.0 && st->nTracers > 0 && st->trKappaVDev)
         return fail(st->ctx, MOKA_ERR_ARG, "vertical tracer diffusion: dt must be >= 0 (the implicit solve is not reversible in time)");
+    if (integrator == MOKA_RUNGE_KUTTA_4 && dt < 0.0 && mom_vmix_on(st))
+        return fail(st->ctx, MOKA_ERR_ARG, "vertical momentum mixing: dt must be >= 0 (the implicit solve is not reversible in time)");
+    if (integrator == MOKA_FORWARD_EULER && mom_vmix_on(st))
+        return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "vertical momentum mixing: applied by RK4 steps only (no Forward Euler)");
     auto one = [&]() { return integrator == MOKA_FORWARD_EULER ? moka_step_fe(st, dt, flags) : moka_step_rk4(st, dt); };
     int64_t done = 0;
     int rc;
@@ -2253,6 +2280,105 @@ int moka_tracer_vertical_diffusion(const moka_state *st, int32_t j, double *out)
 
 int moka_state_tracer_vmix_path(const moka_state *st) { return st ? st->vmixPath : 0; }
 
+// ---- implicit vertical mixing of momentum (include/moka_hip.h: the recipe; momentum_vmix.hip: the kernels) ----
+// what a state must be for the pass to be switched on (checked only when a call asks for something other than zero / NULL)
+static int mom_vmix_supported(moka_state *st)
+{
+    const Plan &p = st->mesh->plan;
+    if (st->f32) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "vertical momentum mixing: Float64 states only");
+    if (st->halos > 0) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "vertical momentum mixing: not on a state with a halo");
+    if (p.nPatchesLaunch != p.nPatches) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "vertical momentum mixing: whole (unpartitioned) meshes only");
+    if (st->dycoreTapes > 0)
+        return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "vertical momentum mixing: not while a moka_tape of this state exists (reverse mode does not cover the pass)");
+    return MOKA_OK;
+}
+
+// the scratch of the column form, allocated by the first call that turns the pass on (never by a step) and kept
+static int mom_vmix_scratch(moka_state *st)
+{
+    if (st->momScratch) return MOKA_OK;
+    const Plan &p = st->mesh->plan;
+    if (int rc = alloc_field(st, &st->momScratch, 2 * (size_t)p.K * p.nE)) return rc;
+    HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));
+    return MOKA_OK;
+}
+
+int moka_set_vertical_viscosity(moka_state *st, double nuV, double bottomDrag)
+{
+    if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
+    if (!(nuV >= 0.0) || !std::isfinite(nuV) || !(bottomDrag >= 0.0) || !std::isfinite(bottomDrag))
+        return fail(st->ctx, MOKA_ERR_ARG, "vertical momentum mixing: the viscosity and the bottom drag must be finite and >= 0");
+    if (nuV != 0.0 || bottomDrag != 0.0) {
+        if (int rc = mom_vmix_supported(st)) return rc;
+        HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+        if (int rc = mom_vmix_scratch(st)) return rc;
+    }
+    st->momNuV = nuV; st->momDrag = bottomDrag;      // (kernel arguments of the next step's launch: nothing on the device changes)
+    return MOKA_OK;
+}
+
+int moka_vertical_viscosity(const moka_state *st, double *nuV, double *bottomDrag)
+{
+    if (!st || !nuV || !bottomDrag) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    *nuV = st->momNuV; *bottomDrag = st->momDrag;
+    return MOKA_OK;
+}
+
+int moka_surface_stress_upload(moka_state *st, const double *host)
+{
+    if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
+    const Plan &p = st->mesh->plan;
+    bool on = false;                     // the host scan: a nonzero entry at an edge with an active level
+    for (int e = 0; host && e < p.nE; ++e) {
+        const double v = host[p.edgeN2O[e]];
+        if (!std::isfinite(v))
+            return fail(st->ctx, MOKA_ERR_ARG, "surface stress: every value must be finite");
+        on = on || (v != 0.0 && p.ehdr[(size_t)e * 4 + 3] >= 1 && p.K >= 1);
+    }
+    if (host)
+        if (int rc = mom_vmix_supported(st)) return rc;
+    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));      // no launch is reading the old array
+    if (!host) {
+        if (st->momTau) state_free(st, st->momTau);
+        st->momTau = nullptr; st->momTauOn = false;
+        return MOKA_OK;
+    }
+    if (on)
+        if (int rc = mom_vmix_scratch(st)) return rc;
+    double *fresh = nullptr;             // the new stress goes into an array of its own: a failure leaves the old one in force
+    if (int rc = alloc_field(st, &fresh, (size_t)p.nE)) return rc;
+    if (int rc = put_rows(st->mesh, fresh, host, MOKA_EDGE, p.nE, 1)) {
+        (void)hipStreamSynchronize(st->ctx->stream);
+        state_free(st, fresh);
+        return rc;
+    }
+    if (st->momTau) state_free(st, st->momTau);
+    st->momTau = fresh; st->momTauOn = on;
+    return MOKA_OK;
+}
+
+int moka_surface_stress_download(moka_state *st, double *host)
+{
+    if (!st || !host) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    const Plan &p = st->mesh->plan;
+    if (!st->momTau) {
+        std::fill(host, host + (size_t)p.nE, 0.0);
+        return MOKA_OK;
+    }
+    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    return get_rows(st->mesh, host, st->momTau, MOKA_EDGE, p.nE, 1);
+}
+
+int moka_has_surface_stress(const moka_state *st, int *out)
+{
+    if (!st || !out) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    *out = st->momTau ? 1 : 0;
+    return MOKA_OK;
+}
+
+int moka_state_momentum_vmix_path(const moka_state *st) { return st ? st->momVmixPath : 0; }
+
 // ---------------------------------------------------------------------------------------------
 // reverse mode of the tracer transport over a frozen flow (include/moka_hip.h: the algebra; tracer_adjoint.hip: the kernels).  A handle of
 // its own, separate from moka_tape: the tracer step is linear in phi, so its transpose needs the recorded provisional states only.
@@ -2323,7 +2449,7 @@ int moka_step_rk4_tracer_taped(moka_tracer_tape *t, double dt)
     if (t->n >= t->capacity) return fail(t->ctx, MOKA_ERR_ARG, "tracer tape is full");
     if (st->nTracers != t->nT) return fail(t->ctx, MOKA_ERR_ARG, "tracer tape: the state's tracer count has changed since the tape was created");
     HIPCHK(t->ctx, hipSetDevice(t->ctx->device));
-    if (dt < 0.0 && st->trKappaVDev) return step_rk4(st, dt, t);      // (refused there, before any launch)
+    if (dt < 0.0 && (st->trKappaVDev || mom_vmix_on(st))) return step_rk4(st, dt, t);      // (refused there, before any launch)
     // the diffusivity fields the step is about to run with: a copy of every one the tape does not hold yet, allocated ahead of the
     // step's first launch -- a failure leaves the state and the tape as they were
     const Plan &p = st->mesh->plan;
@@ -2835,6 +2961,7 @@ int moka_tape_create(moka_state *st, int64_t capacity_steps, moka_tape **out)
     if (st->f32) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "reverse mode: Float64 states only");
     if (st->nonlinear) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "reverse mode covers the reference's linear terms only");
     if (st->nTracers > 0) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "tracers: no reverse mode (moka_set_tracers(st, 0) first)");
+    if (mom_vmix_on(st)) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "vertical momentum mixing: no reverse mode (moka_set_vertical_viscosity(st, 0, 0) and a NULL stress first)");
     const Plan &p = st->mesh->plan;
     HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
     // transposed Coriolis stencil, sources sorted by (caller's edge id, slot): the oracle's summation order

@@ -349,6 +349,7 @@ int moka_halo_create(moka_state *st, int32_t nNeighbors, const int32_t *sendCell
     if (st->viscDel4 != 0.0)
         return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "Del4 mixing: not on a state with a halo (its stencil reaches three cell rings, the nonlinear halo two)");
     if (st->nTracers > 0) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "tracers: whole meshes only (no halo; moka_set_tracers(st, 0) first)");
+    if (mom_vmix_on(st)) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "vertical momentum mixing: whole meshes only (no halo; switch the pass off first)");
     if (nNeighbors > 60) return fail(st->ctx, MOKA_ERR_ARG, "at most 60 neighbours");
     if (nPatchesBoundary < 0 || nPatchesOwned < nPatchesBoundary || nPatchesOwned > p.nPatches)
         return fail(st->ctx, MOKA_ERR_ARG, "patch ranges must satisfy 0 <= boundary <= owned <= nPatches");
@@ -877,6 +878,7 @@ int moka_rk4_dist_begin(moka_halo *h, double dt)
     moka_state *st = h->st;
     if (st->viscDel4 != 0.0) return hfail(h, MOKA_ERR_UNSUPPORTED, "Del4 mixing: whole meshes only (no distributed RK4 step)");
     if (st->nTracers > 0) return hfail(h, MOKA_ERR_UNSUPPORTED, "tracers: whole meshes only (no distributed RK4 step)");
+    if (mom_vmix_on(st)) return hfail(h, MOKA_ERR_UNSUPPORTED, "vertical momentum mixing: whole meshes only (no distributed RK4 step)");
     HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
     // like moka_step_rk4: lazily pending diagnostics / stage-4 tendencies of the previous step are superseded, not computed
     h->dt = dt;
@@ -903,6 +905,7 @@ int moka_rk4_dist_stage(moka_halo *h, int stage, int part)
     moka_state *st = h->st;
     if (st->viscDel4 != 0.0) return hfail(h, MOKA_ERR_UNSUPPORTED, "Del4 mixing: whole meshes only (no distributed RK4 step)");
     if (st->nTracers > 0) return hfail(h, MOKA_ERR_UNSUPPORTED, "tracers: whole meshes only (no distributed RK4 step)");
+    if (mom_vmix_on(st)) return hfail(h, MOKA_ERR_UNSUPPORTED, "vertical momentum mixing: whole meshes only (no distributed RK4 step)");
     HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
     if (part == 2) {
         const StageArgs g = rk4_stage_args(st, stage, h->dt, h->ssh0);
@@ -957,6 +960,7 @@ int moka_rk4_dist_stage_launch(moka_halo *h, int stage)
     if (!h) return fail(nullptr, MOKA_ERR_ARG, "halo is NULL");
     if (h->st->viscDel4 != 0.0) return hfail(h, MOKA_ERR_UNSUPPORTED, "Del4 mixing: whole meshes only (no distributed RK4 step)");
     if (h->st->nTracers > 0) return hfail(h, MOKA_ERR_UNSUPPORTED, "tracers: whole meshes only (no distributed RK4 step)");
+    if (mom_vmix_on(h->st)) return hfail(h, MOKA_ERR_UNSUPPORTED, "vertical momentum mixing: whole meshes only (no distributed RK4 step)");
     int rc;
     if ((rc = moka_rk4_dist_stage(h, stage, 0))) return rc;
     if ((rc = moka_halo_push_begin(h, stage))) return rc;

@@ -331,6 +331,24 @@ VmixKernel vmix_kernel(int K, bool generic, int sets = 3);
 // a.gslot != nullptr (reverse only): the gradient instances, which also serve the unflagged tracers of the step
 hipError_t launch_tracer_vmix(const VmixArgs &a, bool reverse, bool generic, hipStream_t s);
 
+// ---- implicit vertical mixing of momentum (moka_set_vertical_viscosity / moka_surface_stress_upload; momentum_vmix.hip) ----
+// One launch over every edge column behind stage 4 of an RK4 step: u = the new normalVelocity, updated in place, h = the new
+// layerThickness, from which a column's thickness 0.5 * (h[k,c1] + h[k,c2]) is gathered.  Per edge with n = min(maxLevelEdgeTop[e], K)
+// (the recipe of include/moka_hip.h): u = u + Solve(R), R = Lv(u) (+ dt * tau[e] in row 0) (- dt * drag * u[n-1] in row n-1).
+// Columns with n >= 2 are computed, columns with n == 1 only when drag != 0 or tau != nullptr.
+struct MomVmixArgs {
+    int nE, K;
+    const int32_t *ehdr;          // (4, nE) c1, c2, -, maxLevelEdgeTop
+    double *u;                    // (K, nE), updated in place
+    const double *h;              // (K, nC)
+    const double *tau;            // (nE) surface stress over rho0 in device edge numbering; nullptr: none (the instances without it)
+    double dt, nu, drag;          // drag == 0.0: the instances without it
+    double *scratch;              // 2 * K * nE doubles: g and y of the column form (the tile form keeps them in LDS)
+};
+// the form vmix_kernel(K, generic, 3) gives the pass: 1 = k_mvmix_tile, 2 = k_mvmix_column
+int momentum_vmix_form(int K, bool generic);
+hipError_t launch_momentum_vmix(const MomVmixArgs &a, bool generic, hipStream_t s);
+
 // ---- reverse mode of one Forward-Euler step: gather form, the oracle's summation order ----
 struct AdjMesh {
     int32_t nC, nE, K, ME, W;          // W = width of the transposed Coriolis lists

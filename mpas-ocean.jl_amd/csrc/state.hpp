@@ -151,6 +151,14 @@ struct moka_state {
     // not rotate with the time levels.
     std::vector<double *> trSrc;
     double **trSrcDev = nullptr;
+    // implicit vertical mixing of momentum (moka_set_vertical_viscosity, moka_surface_stress_upload): the two scalars; the surface
+    // stress in device edge numbering (nullptr: none) and whether it has a nonzero entry at an edge with an active level (the host scan
+    // of the upload; one that has none counts as absent); the scratch of the column form (2 * K * nE doubles), allocated by the first
+    // call that turns the pass on and kept.  mk::mom_vmix_on says whether the pass is on.
+    double momNuV = 0.0, momDrag = 0.0;
+    double *momTau = nullptr, *momScratch = nullptr;
+    bool momTauOn = false;
+    int momVmixPath = 0;              // moka_state_momentum_vmix_path
     std::vector<void *> allocs;
     // objects that hold or have exported the addresses of this state's arrays (halos, tapes): while any exists the arrays stay
     // where they are (moka_state_optimize_placement refuses)
@@ -193,6 +201,8 @@ inline MeshDev launch_bounds(const moka_mesh *mm)
     dev.maxOwnE = std::max(mm->plan.maxOwnELaunch, 1); dev.maxOwnC = std::max(mm->plan.maxOwnCLaunch, 1);
     return dev;
 }
+// is the vertical momentum pass on: some coefficient nonzero, or a stress with a nonzero entry at an edge that has an active level
+inline bool mom_vmix_on(const moka_state *st) { return st->momNuV != 0.0 || st->momDrag != 0.0 || (st->momTau && st->momTauOn); }
 // `form` of the nonlinear launchers: kernel variants 4 / 3 select the plainer forms of the nonlinear kernels too
 inline int nl_form(const moka_ctx *ctx) { return ctx->variant == 4 ? 1 : ctx->variant == 3 ? 3 : 0; }
 

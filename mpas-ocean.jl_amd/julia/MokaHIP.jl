@@ -570,6 +570,34 @@ function tracer_has_vertical_field(Prog::MProg, j::Integer)
     check(ccall((:moka_tracer_has_vertical_field, lib), Cint, (Ptr{Cvoid}, Int32, Ref{Cint}), s.handle, j - 1, out), s.backend.ctx)
     out[] != 0
 end
+# Implicit vertical mixing of momentum behind every RK4 step (include/moka_hip.h states the recipe): `viscosity` nuV (m^2/s, >= 0),
+# `bottom_drag` r (m/s, >= 0, linear) and `surface_stress`, nothing or nEdges values tau / rho0 (m^2/s^2) along the edge normals in the
+# mesh's edge order.  All three are replaced by a call; zeros and nothing switch the pass off.  Takes effect with the next RK4 step.
+function set_vertical_mixing!(Prog::MProg; viscosity::Real = 0.0, bottom_drag::Real = 0.0, surface_stress::Union{Vector{Float64}, Nothing} = nothing)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    check(ccall((:moka_set_vertical_viscosity, lib), Cint, (Ptr{Cvoid}, Float64, Float64), s.handle, viscosity, bottom_drag), s.backend.ctx)
+    p = surface_stress === nothing ? Ptr{Float64}(C_NULL) : pointer(surface_stress)
+    GC.@preserve surface_stress check(ccall((:moka_surface_stress_upload, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), s.handle, p), s.backend.ctx)
+end
+# (viscosity, bottom_drag, surface_stress) as they stand; the stress is nothing when there is none
+function vertical_mixing(Prog::MProg)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    nu = Ref{Float64}(0.0); r = Ref{Float64}(0.0); has = Ref{Cint}(0)
+    check(ccall((:moka_vertical_viscosity, lib), Cint, (Ptr{Cvoid}, Ref{Float64}, Ref{Float64}), s.handle, nu, r), s.backend.ctx)
+    check(ccall((:moka_has_surface_stress, lib), Cint, (Ptr{Cvoid}, Ref{Cint}), s.handle, has), s.backend.ctx)
+    has[] == 0 && return (nu[], r[], nothing)
+    tau = Vector{Float64}(undef, size(Prog.normalVelocity[end], 2))        # (nVertLevels, nEdges)
+    check(ccall((:moka_surface_stress_download, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), s.handle, tau), s.backend.ctx)
+    (nu[], r[], tau)
+end
+# 1 the tile form, 2 the column form of the momentum pass served the last step, 0 none yet
+function momentum_vmix_path(Prog::MProg)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    Int(ccall((:moka_state_momentum_vmix_path, lib), Cint, (Ptr{Cvoid},), s.handle))
+end
 # 1 the patch form, 2 the generic form of the tracer kernel served the last RK4 stage, 0 none yet
 function tracer_path(Prog::MProg)
     s = Prog.ssh[end].state

@@ -31,6 +31,7 @@ __all__ = [
     "attachAlarm", "setCurrentTime", "ocn_setup_clock", "ocn_setup_mesh", "ocn_init", "write_netcdf",
     "ConfigRead", "ConfigGet", "GlobalConfig", "AdjointTape", "set_nonlinear", "REFERENCE_COMPAT", "prognostic_vars_best_placement",
     "set_tracers", "Tracers", "TracerAdjointTape",
+    "set_vertical_mixing", "vertical_mixing", "momentum_vmix_path",
 ]
 
 MokaError = L.MokaError
@@ -592,6 +593,43 @@ def set_nonlinear(Prog: "PrognosticVars", on: bool = True, visc_del2: float = 0.
                 raise ValueError(f"mesh_scaling_del4: {sc.size} values for {nE} edges")
         L.check(L.lib().moka_set_viscosity_del4(Prog._state._h, float(visc_del4), None if sc is None else sc.ctypes.data),
                 Prog._state.mesh.backend._h)
+
+
+def set_vertical_mixing(Prog: "PrognosticVars", viscosity: float = 0.0, bottom_drag: float = 0.0, surface_stress=None):
+    """Implicit vertical mixing of momentum behind every RK4 step (moka_set_vertical_viscosity, moka_surface_stress_upload; an
+    extension, default off; include/moka_hip.h states the recipe).  `viscosity`: nuV >= 0 in m^2/s; `bottom_drag`: a linear drag
+    r >= 0 in m/s on the deepest active level of every edge; `surface_stress`: None, or one value tau / rho0 (m^2/s^2) per edge along
+    the edge normal, in the mesh's edge order.  All three are replaced by a call: zeros and None switch the pass off.  They take effect
+    with the next RK4 step or run_steps."""
+    st = Prog._state
+    h = st.mesh.backend._h
+    L.check(L.lib().moka_set_vertical_viscosity(st._h, float(viscosity), float(bottom_drag)), h)
+    tau = None
+    if surface_stress is not None:
+        tau = np.ascontiguousarray(surface_stress, dtype=np.float64).reshape(-1)
+        nE = st.mesh.HorzMesh.data.nEdges
+        if tau.size != nE:
+            raise ValueError(f"surface_stress: {tau.size} values for {nE} edges")
+    L.check(L.lib().moka_surface_stress_upload(st._h, None if tau is None else tau.ctypes.data), h)
+
+
+def vertical_mixing(Prog: "PrognosticVars"):
+    """(viscosity, bottom_drag, surface_stress) as they stand: the stress as an array of nEdges values, or None when there is none."""
+    st = Prog._state
+    h = st.mesh.backend._h
+    nu, r, has = C.c_double(0.0), C.c_double(0.0), C.c_int(0)
+    L.check(L.lib().moka_vertical_viscosity(st._h, C.byref(nu), C.byref(r)), h)
+    L.check(L.lib().moka_has_surface_stress(st._h, C.byref(has)), h)
+    if not has.value:
+        return nu.value, r.value, None
+    tau = np.empty(st.mesh.HorzMesh.data.nEdges, dtype=np.float64)
+    L.check(L.lib().moka_surface_stress_download(st._h, L.f64(tau)), h)
+    return nu.value, r.value, tau
+
+
+def momentum_vmix_path(Prog: "PrognosticVars") -> int:
+    """moka_state_momentum_vmix_path: 1 the tile form, 2 the column form of the momentum pass, 0 before the first one."""
+    return int(L.lib().moka_state_momentum_vmix_path(Prog._state._h))
 
 
 class Tracers:

@@ -108,6 +108,8 @@ EXPORTS = [
     "moka_set_tracer_vertical_diffusion", "moka_tracer_vertical_diffusion", "moka_state_tracer_vmix_path", "moka_tracer_adjoint_vmix_path",
     "moka_tracer_source_upload", "moka_tracer_source_download", "moka_tracer_has_source",
     "moka_tracer_vertical_field_upload", "moka_tracer_vertical_field_download", "moka_tracer_has_vertical_field",
+    "moka_set_vertical_viscosity", "moka_vertical_viscosity", "moka_surface_stress_upload", "moka_surface_stress_download",
+    "moka_has_surface_stress", "moka_state_momentum_vmix_path",
     "moka_tracer_adjoint_want_source_gradient", "moka_tracer_adjoint_source_download",
     "moka_tracer_adjoint_want_diffusivity_gradient", "moka_tracer_adjoint_diffusivity_gradient",
     "moka_tracer_adjoint_diffusivity_density_download",
@@ -277,6 +279,12 @@ def lib():
     L.moka_tracer_vertical_field_upload.argtypes = [vp, C.c_int32, vp]
     L.moka_tracer_vertical_field_download.argtypes = [vp, C.c_int32, vp]
     L.moka_tracer_has_vertical_field.argtypes = [vp, C.c_int32, C.POINTER(C.c_int)]
+    L.moka_set_vertical_viscosity.argtypes = [vp, C.c_double, C.c_double]
+    L.moka_vertical_viscosity.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.moka_surface_stress_upload.argtypes = [vp, vp]
+    L.moka_surface_stress_download.argtypes = [vp, vp]
+    L.moka_has_surface_stress.argtypes = [vp, C.POINTER(C.c_int)]
+    L.moka_state_momentum_vmix_path.argtypes = [vp]
     L.moka_tracer_adjoint_want_source_gradient.argtypes = [vp, C.c_int32, C.c_int]
     L.moka_tracer_adjoint_source_download.argtypes = [vp, C.c_int32, vp]
     L.moka_tracer_adjoint_want_diffusivity_gradient.argtypes = [vp, C.c_int32, C.c_int, C.c_int]
