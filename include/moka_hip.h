@@ -776,7 +776,8 @@ int  moka_tracer_has_vertical_field(const moka_state *st, int32_t j, int *out);
  * moka_step_fe, moka_run(MOKA_FORWARD_EULER), moka_tape_create, moka_halo_create and the moka_rk4_dist_* calls return
  * MOKA_ERR_UNSUPPORTED.  The first call that turns the pass on allocates the column form's scratch of 2 * nVertLevels * nEdges doubles;
  * no step allocates anything.  moka_state_optimize_placement neither times nor moves the new arrays.
- * Out of scope: reverse mode through the pass (the operator depends on h_new, so the flow adjoint gains thickness terms), a nuV field
+ * Out of scope: reverse mode through the pass by a moka_tape handle (the operator depends on h_new, so the flow adjoint gains thickness terms;
+ * the moka_forced_tape handle, below, carries them), a nuV field
  * per interface and edge, quadratic drag, closures (Richardson number, KPP), Forward Euler, fp32 storage, partitioned meshes, YAML keys
  * and NetCDF I/O, a time-dependent stress other than by a new upload between steps. */
 int  moka_set_vertical_viscosity(moka_state *st, double nuV, double bottomDrag);
@@ -977,6 +978,80 @@ int  moka_adjoint_fe_step(moka_tape *t);
 /* field: MOKA_F_SSH, MOKA_F_NORMAL_VELOCITY, MOKA_F_LAYER_THICKNESS (d_Prog of the reference test) or
  * MOKA_F_LAYER_THICKNESS_EDGE (the carried diagnostic of the reference_compat sequence); caller's numbering */
 int  moka_adjoint_download(moka_tape *t, int field, double *host);
+
+/* ---- reverse mode through the forced RK4 step: gradients of wind stress, viscosity and drag (extension) -------------------
+ * A handle of its own, separate from moka_tape, which keeps every answer it gave (it still refuses a state whose vertical momentum
+ * pass is on, and the pass setters a state that has one).  A moka_forced_tape records RK4 steps of a Float64 state on a whole mesh
+ * with the linear dycore, the pass on or off, and its sweep runs, per recorded step backwards, first the transposed pass and then the
+ * four transposed RK stages of moka_adjoint_sweep (the same launches).
+ * The transposed pass.  Notation of the forward recipe (moka_set_vertical_viscosity): for an edge column of depth n, h[k] = 0.5 *
+ * (hn[k,c1] + hn[k,c2]) from the recorded new thickness hn, un the recorded mixed velocity, s = dt * nuV, q = dt * r, b = dt * tau[e]
+ * (the step's values), A = diag(h) + s W + q e_{n-1} e_{n-1}^T, symmetric.  Differentiating A(h) u_new = h o u* + b e_0, and using
+ * h o (u_new - u*) = R(u_new), which holds exactly, gives, with X = (XU, XH) the adjoint of (u_new, h_new), every operation rounded once,
+ * nothing contracted, in this order:
+ *   z      = Solve_A(XU[0..n-1])              w, d, and the sweep (g = w[k-1] / beta, beta = d[k] - w[k-1] * g, y = (XU[k] + w[k-1] * y)
+ *                                             / beta; z[k] = y[k] + g[k] * z[k+1]) exactly as the forward pass forms them; n == 1: XU[0] / d[0]
+ *   then for k = 0 .. n-1 ascending, hm[k] = 0.5 * (h[k] + h[k+1]), w[k] = s / hm[k]:
+ *   de[k]  = (z[k] - z[k+1]) * (un[k] - un[k+1]);   P[k] = (w[k] / hm[k]) * de[k]                       k = 0 .. n-2
+ *   Rn     = R(un): w[k-1] * (un[k-1] - un[k]) + w[k] * (un[k+1] - un[k]) (end rows: the one term; n == 1: 0.0), then + b in row 0
+ *            with a stress, then - q * un[n-1] in row n-1 with drag: the forward's right-hand side formed from x := un
+ *   hbar[k]= 0.5 * (P[k-1] + P[k]) - z[k] * (Rn[k] / h[k])      (end rows: 0.5 * the one P; n == 1: 0.0 - z[0] * (Rn[0] / h[0]))
+ *   XU[k]  = h[k] * z[k]                                         the adjoint of u*
+ * and then, per cell c and level k, S = 0.0; for the slots i of edgesOnCell[c] in ascending order whose edge e is a computed column
+ * with k < n_e: S = S + hbar[k,e]; when at least one slot took part: XH[k,c] = XH[k,c] + 0.5 * S (a gather: no atomics; rows of hbar at
+ * or below an edge's depth are never read).
+ * Computed columns are exactly those the forward pass computed in that step (n >= 2, or n == 1 with drag or stress; none in a step
+ * that ran without the pass); every other element of XU and XH keeps its bits.  A step recorded with dt == 0.0 skips the pass both ways.
+ * Parameter sensitivities (moka_forced_adjoint_want_gradient): three densities of nEdges doubles take, per reversed step with
+ * dt != 0.0 and per edge with n >= 1, each operation rounded once:
+ *   G_tau[e] = G_tau[e] + dt * z[0]
+ *   D_nu[e]  = D_nu[e]  - dt * sum,   sum = 0.0; sum = sum + de[k] / hm[k] for k = 0 .. n-2 ascending   (n == 1: D_nu[e] is left alone)
+ *   D_r[e]   = D_r[e]   - dt * (z[n-1] * un[n-1])
+ * While any is flagged, z is also computed in the columns with n >= 1 the forward pass skipped -- n == 1 with only nuV on, and every
+ * column of a step that ran without the pass, where A = diag(h) and the result is the derivative at zero -- for the densities alone:
+ * such a column writes neither XU nor hbar, so X after a flagged sweep has the bits of an unflagged one.  d J / d nuV = sum_e D_nu[e]
+ * and d J / d r = sum_e D_r[e], summed on the host over the caller's edge numbering, ascending, in long double and rounded once; G_tau
+ * itself is d J / d tau_e for a stress that acts in every recorded step.  The densities show where J feels each parameter.  Every
+ * seed zeroes them.
+ * Kernels: the edge columns run in the forward's two forms with one device function behind both -- the tile form with four column
+ * sets in LDS (vmix_kernel(K, generic, 4): tiles of 64 columns for nVertLevels <= 19, of 32 for <= 79), the column form deeper, for
+ * nVertLevels == 1 and with kernel variant 3 -- then the cell gather.  Both forms and the numpy twin of the tests agree bit for bit.
+ * The tape: moka_step_rk4_forced_taped leaves state and diagnostics with the bits of moka_step_rk4 and records what
+ * moka_step_rk4_taped records; when the pass is on in that step, or any gradient is flagged, also u_new and h_new (K * (nEdges +
+ * nCells) doubles more) and the step's nuV, r and whether the stress was on.  Allocations happen at create (those of moka_tape_create),
+ * at the first taped step (those of moka_step_rk4_taped; with the first step that records the new level, capacity * K * (nEdges + nCells)
+ * + 3 * K * nEdges doubles more) and at moka_forced_adjoint_want_gradient (nEdges doubles a bit); MOKA_ERR_ALLOC leaves nothing changed.
+ * MOKA_ERR_UNSUPPORTED at create: fp32 storage, the nonlinear terms, tracers, a state with a halo, a partitioned mesh, an existing
+ * moka_tape or moka_forced_tape.  While a forced tape exists moka_tape_create, moka_set_tracers(st, n > 0), moka_set_nonlinear,
+ * moka_halo_create and moka_state_optimize_placement return MOKA_ERR_UNSUPPORTED; moka_set_vertical_viscosity is allowed at any time
+ * (the values are recorded per step); moka_surface_stress_upload returns MOKA_ERR_UNSUPPORTED while the tape holds recorded steps (the
+ * reverse pass reads the stress the steps ran with, and G_tau is the gradient of one stress field).  MOKA_ERR_ARG: dt < 0 with the pass
+ * on, a full tape, NULL arguments, a sweep without a seed, a `what` that is not flagged (or not one bit where one is asked for),
+ * moka_forced_adjoint_want_gradient with recorded steps.  The state must outlive the tape.
+ * Usage: forced_tape_create -> [want_gradient] -> n x step_rk4_forced_taped -> seed -> sweep -> download / density_download / gradient.
+ * Out of scope: the nonlinear, Del2 and Del4 dycores (no moka_tape covers them either), Forward Euler, the piecewise, partitioned
+ * taping calls, fp32 storage, a time-dependent stress and a per-step split of the densities, second derivatives, a nuV field per
+ * interface and edge, quadratic drag, coupling to the tracer tape, the 13-stream form for taped steps, YAML keys and NetCDF I/O. */
+typedef struct moka_forced_tape moka_forced_tape;
+int  moka_forced_tape_create(moka_state *st, int64_t capacity_steps, moka_forced_tape **out);
+void moka_forced_tape_destroy(moka_forced_tape *t);
+int  moka_step_rk4_forced_taped(moka_forced_tape *t, double dt);
+/* X := d sum(ssh^2) / d (normalVelocity, layerThickness) at the current state, as moka_adjoint_seed_sum_sq_ssh for an RK4 tape */
+int  moka_forced_adjoint_seed_sum_sq_ssh(moka_forced_tape *t);
+/* X := the caller's (nEdges, nVertLevels) and (nCells, nVertLevels) doubles, caller's numbering */
+int  moka_forced_adjoint_seed(moka_forced_tape *t, const double *hostU, const double *hostH);
+int  moka_forced_adjoint_sweep(moka_forced_tape *t);            /* reverse over (and pop) every recorded step */
+/* field: MOKA_F_NORMAL_VELOCITY or MOKA_F_LAYER_THICKNESS; X as it stands */
+int  moka_forced_adjoint_download(moka_forced_tape *t, int field, double *host);
+enum { MOKA_FORCED_GRAD_STRESS = 1, MOKA_FORCED_GRAD_VISCOSITY = 2, MOKA_FORCED_GRAD_DRAG = 4 };
+/* what: a nonempty set of the bits; on != 0 adds them, 0 removes them.  Only while no step is recorded. */
+int  moka_forced_adjoint_want_gradient(moka_forced_tape *t, int what, int on);
+/* what: exactly one flagged bit.  host: the density, nEdges doubles in the caller's edge numbering; *out: the host sum (for
+ * MOKA_FORCED_GRAD_STRESS: the sum of G_tau, the derivative with respect to a uniform offset of the stress) */
+int  moka_forced_adjoint_density_download(moka_forced_tape *t, int what, double *host);
+int  moka_forced_adjoint_gradient(moka_forced_tape *t, int what, double *out);
+/* which kernel served the last transposed pass: 1 the tile form, 2 the column form, 0 none yet */
+int  moka_forced_tape_vmix_path(const moka_forced_tape *t);
 
 #ifdef __cplusplus
 }

@@ -1755,6 +1755,8 @@ int moka_set_nonlinear(moka_state *st, int on)
     if (st->f32) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "nonlinear terms: Float64 states only");
     if (st->dycoreTapes > 0)
         return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "nonlinear terms: not while a moka_tape of this state exists (reverse mode covers the linear terms only)");
+    if (st->forcedTapes > 0)
+        return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "nonlinear terms: not while a moka_forced_tape of this state exists (reverse mode covers the linear terms only)");
     if (!p.nlOk)
         return fail(st->ctx, MOKA_ERR_UNSUPPORTED,
                     "nonlinear terms need kiteAreasOnVertex, fVertex, verticesOnEdge and cellsOnVertex in the mesh descriptor");
@@ -2337,6 +2339,8 @@ int moka_surface_stress_upload(moka_state *st, const double *host)
     }
     if (host)
         if (int rc = mom_vmix_supported(st)) return rc;
+    if (st->forcedSteps > 0)             // the reverse pass reads the stress the recorded steps ran with, and G_tau is the gradient of one field
+        return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "surface stress: not while a moka_forced_tape of this state holds recorded steps");
     HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
     HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));      // no launch is reading the old array
     if (!host) {
@@ -2925,6 +2929,7 @@ struct moka_tape {
     moka::AdjMesh am{};
     std::vector<void *> allocs;
     bool counted = false;                            // st->attached includes this tape
+    bool forced = false;                             // the tape a moka_forced_tape embeds: counted in st->forcedTapes
 };
 
 static int tape_alloc(moka_tape *t, void **out, size_t bytes)
@@ -2954,14 +2959,16 @@ static int tape_upload(moka_tape *t, const std::vector<T> &v, const T **out)
 }
 }  // extern "C++"
 
-int moka_tape_create(moka_state *st, int64_t capacity_steps, moka_tape **out)
+// forced: the tape inside a moka_forced_tape, which transposes the vertical momentum pass itself
+static int tape_create(moka_state *st, int64_t capacity_steps, moka_tape **out, bool forced)
 {
     if (!st || !out || capacity_steps < 0) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "bad argument");
     *out = nullptr;
     if (st->f32) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "reverse mode: Float64 states only");
     if (st->nonlinear) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "reverse mode covers the reference's linear terms only");
     if (st->nTracers > 0) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "tracers: no reverse mode (moka_set_tracers(st, 0) first)");
-    if (mom_vmix_on(st)) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "vertical momentum mixing: no reverse mode (moka_set_vertical_viscosity(st, 0, 0) and a NULL stress first)");
+    if (!forced && mom_vmix_on(st)) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "vertical momentum mixing: no reverse mode (moka_set_vertical_viscosity(st, 0, 0) and a NULL stress first)");
+    if (st->forcedTapes > 0) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "reverse mode: a moka_forced_tape of this state exists");
     const Plan &p = st->mesh->plan;
     HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
     // transposed Coriolis stencil, sources sorted by (caller's edge id, slot): the oracle's summation order
@@ -3030,15 +3037,18 @@ int moka_tape_create(moka_state *st, int64_t capacity_steps, moka_tape **out)
     HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));
     state_attach(st);
     t->counted = true;
-    ++st->dycoreTapes;
+    t->forced = forced;
+    ++(forced ? st->forcedTapes : st->dycoreTapes);
     *out = t;
     return MOKA_OK;
 }
 
+int moka_tape_create(moka_state *st, int64_t capacity_steps, moka_tape **out) { return tape_create(st, capacity_steps, out, false); }
+
 void moka_tape_destroy(moka_tape *t)
 {
     if (!t) return;
-    if (t->counted) { state_detach(t->st); --t->st->dycoreTapes; }
+    if (t->counted) { state_detach(t->st); --(t->forced ? t->st->forcedTapes : t->st->dycoreTapes); }
     (void)hipSetDevice(t->st->ctx->device);
     if (t->st->lazyOwner == t) {        // the stage-4 tendencies of the last taped step would be produced from a slot of this tape
         if (t->st->tendDirty) (void)flush_lazy(t->st, false, true);
@@ -3447,5 +3457,239 @@ int moka_adjoint_download(moka_tape *t, int field, double *host)
         default: return fail(st->ctx, MOKA_ERR_ARG, "adjoint fields: ssh, normalVelocity, layerThickness, layerThicknessEdge");
     }
 }
+
+
+// ---------------------------------------------------------------------------------------------
+// reverse mode through the forced RK4 step (include/moka_hip.h: the recipe; momentum_vmix.hip: the transposed pass).  A handle of its
+// own, separate from moka_tape: it embeds one -- built without the check for the pass, counted in moka_state.forcedTapes -- for the
+// four transposed RK stages, and puts the transposed vertical pass in front of them.
+// ---------------------------------------------------------------------------------------------
+struct ForcedStep {
+    bool rec, on, stress;        // u_new / h_new were recorded; the pass ran; with the stress
+    double nu, drag;
+};
+
+struct moka_forced_tape {
+    moka_state *st = nullptr;
+    moka_tape *inner = nullptr;
+    int64_t capacity = 0;
+    double *unRec = nullptr, *hnRec = nullptr;       // capacity x (K, nE) / (K, nC): the new level of every step that recorded it
+    double *hbar = nullptr, *scratch = nullptr;      // (K, nE); 2 x (K, nE): the column form's g and y.  All four come with the first step that records.
+    double *dens[3] = {nullptr, nullptr, nullptr};   // G_tau, D_nu, D_r (nE each), allocated by the flag
+    int want = 0;                                    // MOKA_FORCED_GRAD_* bits
+    std::vector<ForcedStep> steps;
+    int path = 0;                                    // moka_forced_tape_vmix_path
+    std::vector<void *> allocs;
+};
+
+static int forced_alloc(moka_forced_tape *ft, std::initializer_list<std::pair<double **, size_t>> what)
+{
+    moka_ctx *ctx = ft->st->ctx;
+    std::vector<void *> got;
+    for (auto &w : what) {
+        void *d = nullptr;
+        hipError_t e = hipMalloc(&d, std::max<size_t>(w.second * sizeof(double), 16));
+        if (e == hipSuccess) e = hipMemsetAsync(d, 0, w.second * sizeof(double), ctx->stream);
+        if (e != hipSuccess) {                       // nothing changes: what this call took goes back
+            if (d) got.push_back(d);
+            (void)hipStreamSynchronize(ctx->stream);
+            for (void *q : got) (void)hipFree(q);
+            return fail(ctx, MOKA_ERR_ALLOC, std::string("forced tape: hipMalloc of ") + std::to_string(w.second * sizeof(double)) + " bytes: " + hipGetErrorString(e));
+        }
+        got.push_back(d);
+    }
+    size_t i = 0;
+    for (auto &w : what) { *w.first = static_cast<double *>(got[i]); ft->allocs.push_back(got[i++]); }
+    return MOKA_OK;
+}
+
+int moka_forced_tape_create(moka_state *st, int64_t capacity_steps, moka_forced_tape **out)
+{
+    if (!st || !out || capacity_steps < 0) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "bad argument");
+    *out = nullptr;
+    const Plan &p = st->mesh->plan;
+    if (st->halos > 0) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "forced tape: not on a state with a halo");
+    if (p.nPatchesLaunch != p.nPatches) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "forced tape: whole (unpartitioned) meshes only");
+    if (st->dycoreTapes > 0) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "forced tape: a moka_tape of this state exists");
+    moka_forced_tape *ft = new (std::nothrow) moka_forced_tape();
+    if (!ft) return fail(st->ctx, MOKA_ERR_ALLOC, "out of host memory");
+    if (int rc = tape_create(st, capacity_steps, &ft->inner, true)) { delete ft; return rc; }     // fp32, nonlinear, tracers, a forced tape
+    ft->inner->kind = 1;                             // RK4 only: a seed of the empty tape is an RK4 seed
+    ft->st = st;
+    ft->capacity = capacity_steps;
+    *out = ft;
+    return MOKA_OK;
+}
+
+void moka_forced_tape_destroy(moka_forced_tape *ft)
+{
+    if (!ft) return;
+    moka_state *st = ft->st;
+    st->forcedSteps -= (int64_t)ft->steps.size();
+    moka_tape_destroy(ft->inner);                    // synchronises the stream
+    for (void *q : ft->allocs) (void)hipFree(q);
+    delete ft;
+}
+
+int moka_step_rk4_forced_taped(moka_forced_tape *ft, double dt)
+{
+    if (!ft) return fail(nullptr, MOKA_ERR_ARG, "forced tape is NULL");
+    moka_state *st = ft->st;
+    const Plan &p = st->mesh->plan;
+    if ((int64_t)ft->steps.size() >= ft->capacity) return fail(st->ctx, MOKA_ERR_ARG, "forced tape is full");
+    const bool on = mom_vmix_on(st);
+    if (on && dt < 0.0) return fail(st->ctx, MOKA_ERR_ARG, "vertical momentum mixing: dt must be >= 0 (the implicit solve is not reversible in time)");
+    const bool rec = on || ft->want != 0;
+    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    const size_t nEK = (size_t)p.K * p.nE, nCK = (size_t)p.K * p.nC;
+    if (rec && !ft->unRec)
+        if (int rc = forced_alloc(ft, {{&ft->unRec, nEK * (size_t)ft->capacity}, {&ft->hnRec, nCK * (size_t)ft->capacity}, {&ft->hbar, nEK}, {&ft->scratch, 2 * nEK}}))
+            return rc;
+    if (int rc = moka_step_rk4_taped(ft->inner, dt)) return rc;
+    hipStream_t s = st->ctx->stream;
+    if (on && dt != 0.0)         // the split step of moka_step_rk4, on the same two arrays (rk4_end has made them the current level)
+        if (int rc = momentum_vmix(st, st->lev[1].u, st->lev[1].h, dt)) return rc;
+    const size_t i = ft->steps.size();
+    if (rec) {
+        HIPCHK(st->ctx, hipMemcpyAsync(ft->unRec + nEK * i, st->lev[1].u, nEK * sizeof(double), hipMemcpyDeviceToDevice, s));
+        HIPCHK(st->ctx, hipMemcpyAsync(ft->hnRec + nCK * i, st->lev[1].h, nCK * sizeof(double), hipMemcpyDeviceToDevice, s));
+    }
+    ft->steps.push_back({rec, on, st->momTau && st->momTauOn, st->momNuV, st->momDrag});
+    ++st->forcedSteps;
+    return MOKA_OK;
+}
+
+static int forced_zero_densities(moka_forced_tape *ft)
+{
+    for (double *d : ft->dens)
+        if (d) HIPCHK(ft->st->ctx, hipMemsetAsync(d, 0, (size_t)ft->st->mesh->plan.nE * sizeof(double), ft->st->ctx->stream));
+    return MOKA_OK;
+}
+
+int moka_forced_adjoint_seed_sum_sq_ssh(moka_forced_tape *ft)
+{
+    if (!ft) return fail(nullptr, MOKA_ERR_ARG, "forced tape is NULL");
+    if (int rc = moka_adjoint_seed_sum_sq_ssh(ft->inner)) return rc;
+    return forced_zero_densities(ft);
+}
+
+int moka_forced_adjoint_seed(moka_forced_tape *ft, const double *hostU, const double *hostH)
+{
+    if (!ft || !hostU || !hostH) return fail(ft ? ft->st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    moka_state *st = ft->st;
+    moka_tape *t = ft->inner;
+    const Plan &p = st->mesh->plan;
+    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    hipStream_t s = st->ctx->stream;
+    const size_t nEK = (size_t)p.K * p.nE;
+    t->cur = 0;
+    for (int b = 0; b < 2; ++b) {       // as the RK4 seed of moka_tape: the sweep never writes the ssh / layerThicknessEdge adjoints
+        HIPCHK(st->ctx, hipMemsetAsync(t->lamS[b], 0, (size_t)p.nC * sizeof(double), s));
+        HIPCHK(st->ctx, hipMemsetAsync(t->lamE[b], 0, nEK * sizeof(double), s));
+    }
+    if (int rc = put_rows(st->mesh, t->lamU[0], hostU, MOKA_EDGE, p.nE, p.K)) return rc;
+    if (int rc = put_rows(st->mesh, t->lamH[0], hostH, MOKA_CELL, p.nC, p.K)) return rc;
+    t->seeded = true;
+    return forced_zero_densities(ft);
+}
+
+int moka_forced_adjoint_sweep(moka_forced_tape *ft)
+{
+    if (!ft) return fail(nullptr, MOKA_ERR_ARG, "forced tape is NULL");
+    moka_state *st = ft->st;
+    moka_tape *t = ft->inner;
+    if (!t->seeded) return fail(st->ctx, MOKA_ERR_ARG, "seed the adjoint first (moka_forced_adjoint_seed_sum_sq_ssh, moka_forced_adjoint_seed)");
+    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    const Plan &p = st->mesh->plan;
+    const size_t nEK = (size_t)p.K * p.nE, nCK = (size_t)p.K * p.nC;
+    const bool generic = st->ctx->variant == 3;
+    while (!ft->steps.empty()) {
+        const ForcedStep r = ft->steps.back();
+        const size_t i = ft->steps.size() - 1;
+        const double dt = t->dts[i];
+        if (r.rec && dt != 0.0) {       // the transposed pass, at the head of the reversed step
+            MomVmixAdjArgs a{};
+            a.nE = p.nE; a.K = p.K; a.nC = p.nC; a.ME = p.ME;
+            a.ehdr = st->mesh->dev.ehdr; a.eoc = st->mesh->dev.eoc;
+            a.xu = t->lamU[t->cur]; a.xh = t->lamH[t->cur];
+            a.un = ft->unRec + nEK * i; a.hn = ft->hnRec + nCK * i;
+            a.tau = r.stress ? st->momTau : nullptr;
+            a.dt = dt; a.nu = r.nu; a.drag = r.drag; a.on = r.on ? 1 : 0;
+            a.hbar = ft->hbar; a.scratch = ft->scratch;
+            a.Gtau = (ft->want & MOKA_FORCED_GRAD_STRESS) ? ft->dens[0] : nullptr;
+            a.Dnu = (ft->want & MOKA_FORCED_GRAD_VISCOSITY) ? ft->dens[1] : nullptr;
+            a.Dr = (ft->want & MOKA_FORCED_GRAD_DRAG) ? ft->dens[2] : nullptr;
+            const bool launched = ft->want != 0 || (r.on && !(p.K < 2 && r.drag == 0.0 && !a.tau));
+            HIPCHK(st->ctx, launch_momentum_vmix_adjoint(a, generic, st->ctx->stream));
+            HIPCHK(st->ctx, launch_momentum_vmix_gather(a, st->ctx->stream));
+            if (launched) ft->path = momentum_vmix_adjoint_form(p.K, generic);
+        }
+        for (int sg = 4; sg >= 1; --sg)
+            if (int rc = rk4_reverse_stage(t, sg)) return rc;
+        ft->steps.pop_back();
+        --st->forcedSteps;
+    }
+    return MOKA_OK;
+}
+
+int moka_forced_adjoint_download(moka_forced_tape *ft, int field, double *host)
+{
+    if (!ft || !host) return fail(ft ? ft->st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    if (field != MOKA_F_NORMAL_VELOCITY && field != MOKA_F_LAYER_THICKNESS)
+        return fail(ft->st->ctx, MOKA_ERR_ARG, "forced adjoint fields: normalVelocity, layerThickness");
+    return moka_adjoint_download(ft->inner, field, host);
+}
+
+static int forced_bit(int what) { return what == MOKA_FORCED_GRAD_STRESS ? 0 : what == MOKA_FORCED_GRAD_VISCOSITY ? 1 : what == MOKA_FORCED_GRAD_DRAG ? 2 : -1; }
+
+int moka_forced_adjoint_want_gradient(moka_forced_tape *ft, int what, int on)
+{
+    if (!ft) return fail(nullptr, MOKA_ERR_ARG, "forced tape is NULL");
+    moka_state *st = ft->st;
+    const int all = MOKA_FORCED_GRAD_STRESS | MOKA_FORCED_GRAD_VISCOSITY | MOKA_FORCED_GRAD_DRAG;
+    if (what == 0 || (what & ~all)) return fail(st->ctx, MOKA_ERR_ARG, "forced tape: what must be a nonempty set of MOKA_FORCED_GRAD_* bits");
+    if (!ft->steps.empty()) return fail(st->ctx, MOKA_ERR_ARG, "forced tape: gradients are flagged while no step is recorded");
+    if (on) {
+        HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+        double *fresh[3] = {nullptr, nullptr, nullptr};
+        for (int b = 0; b < 3; ++b)
+            if ((what >> b & 1) && !ft->dens[b]) {
+                if (int rc = forced_alloc(ft, {{&fresh[b], (size_t)st->mesh->plan.nE}})) {
+                    for (int c = 0; c < b; ++c)     // nothing changes: the densities this call took go back
+                        if (fresh[c]) { ft->allocs.erase(std::find(ft->allocs.begin(), ft->allocs.end(), (void *)fresh[c])); (void)hipFree(fresh[c]); }
+                    return rc;
+                }
+            }
+        for (int b = 0; b < 3; ++b)
+            if (fresh[b]) ft->dens[b] = fresh[b];
+        HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));
+        ft->want |= what;
+    } else {
+        ft->want &= ~what;
+    }
+    return MOKA_OK;
+}
+
+int moka_forced_adjoint_density_download(moka_forced_tape *ft, int what, double *host)
+{
+    if (!ft || !host) return fail(ft ? ft->st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    const int b = forced_bit(what);
+    if (b < 0 || !(ft->want & what)) return fail(ft->st->ctx, MOKA_ERR_ARG, "forced tape: what must be one flagged MOKA_FORCED_GRAD_* bit");
+    HIPCHK(ft->st->ctx, hipSetDevice(ft->st->ctx->device));
+    return get_rows(ft->st->mesh, host, ft->dens[b], MOKA_EDGE, ft->st->mesh->plan.nE, 1);
+}
+
+int moka_forced_adjoint_gradient(moka_forced_tape *ft, int what, double *out)
+{
+    if (!ft || !out) return fail(ft ? ft->st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    std::vector<double> w((size_t)ft->st->mesh->plan.nE);
+    if (int rc = moka_forced_adjoint_density_download(ft, what, w.data())) return rc;
+    long double sum = 0.0L;            // the caller's edge numbering, ascending, one rounding at the end: independent of the plan's order
+    for (double v : w) sum += (long double)v;
+    *out = (double)sum;
+    return MOKA_OK;
+}
+
+int moka_forced_tape_vmix_path(const moka_forced_tape *ft) { return ft ? ft->path : 0; }
 
 }  // extern "C"

@@ -350,6 +350,7 @@ int moka_halo_create(moka_state *st, int32_t nNeighbors, const int32_t *sendCell
         return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "Del4 mixing: not on a state with a halo (its stencil reaches three cell rings, the nonlinear halo two)");
     if (st->nTracers > 0) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "tracers: whole meshes only (no halo; moka_set_tracers(st, 0) first)");
     if (mom_vmix_on(st)) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "vertical momentum mixing: whole meshes only (no halo; switch the pass off first)");
+    if (st->forcedTapes > 0) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "a moka_forced_tape of this state exists: whole meshes only (no halo)");
     if (nNeighbors > 60) return fail(st->ctx, MOKA_ERR_ARG, "at most 60 neighbours");
     if (nPatchesBoundary < 0 || nPatchesOwned < nPatchesBoundary || nPatchesOwned > p.nPatches)
         return fail(st->ctx, MOKA_ERR_ARG, "patch ranges must satisfy 0 <= boundary <= owned <= nPatches");

@@ -349,6 +349,28 @@ struct MomVmixArgs {
 int momentum_vmix_form(int K, bool generic);
 hipError_t launch_momentum_vmix(const MomVmixArgs &a, bool generic, hipStream_t s);
 
+// ---- the transposed pass (moka_forced_tape; momentum_vmix.hip) ----
+// At the head of a reversed step, per edge column the forward pass computed with these switches (the recipe of include/moka_hip.h):
+// z = Solve_A(xu), xu = h o z in place, hbar to its own (K, nE) array, active levels only; then launch_momentum_vmix_gather adds
+// 0.5 * (the sum of hbar over a cell's computed edges, slot order) to xh.  Gtau / Dnu / Dr (nE each; nullptr: not wanted): with any of
+// them the gradient instances run, which also solve the columns with n >= 1 the forward pass skipped, for the densities alone.
+struct MomVmixAdjArgs {
+    int nE, K, nC, ME;
+    const int32_t *ehdr;          // (4, nE) c1, c2, -, maxLevelEdgeTop
+    const int32_t *eoc;           // (ME, nC) edges of a cell, -1 = none
+    double *xu, *xh;              // the adjoint state (K, nE), (K, nC), updated in place
+    const double *un, *hn;        // the recorded u_new (K, nE) and h_new (K, nC) of the step
+    const double *tau;            // the stress of the step (nullptr: it had none)
+    double dt, nu, drag;          // the step's
+    int on;                       // 0: the step ran without the pass (gradient instances only: no column writes xu or hbar)
+    double *hbar;                 // (K, nE) work array
+    double *scratch;              // 2 * K * nE doubles: g and y of the column form
+    double *Gtau, *Dnu, *Dr;
+};
+int momentum_vmix_adjoint_form(int K, bool generic);            // vmix_kernel(K, generic, 4).form
+hipError_t launch_momentum_vmix_adjoint(const MomVmixAdjArgs &a, bool generic, hipStream_t s);
+hipError_t launch_momentum_vmix_gather(const MomVmixAdjArgs &a, hipStream_t s);
+
 // ---- reverse mode of one Forward-Euler step: gather form, the oracle's summation order ----
 struct AdjMesh {
     int32_t nC, nE, K, ME, W;          // W = width of the transposed Coriolis lists

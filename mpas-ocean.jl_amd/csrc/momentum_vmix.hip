@@ -1,7 +1,9 @@
 // momentum_vmix.hip -- implicit vertical mixing of momentum with a surface stress and a linear bottom drag (gfx950;
 // moka_set_vertical_viscosity / moka_surface_stress_upload, NOT in the reference): one tridiagonal solve per edge column behind stage 4
-// of an RK4 step, on the new normalVelocity over the new layerThickness.
+// of an RK4 step, on the new normalVelocity over the new layerThickness.  Second half of the file: the transpose of that pass for
+// moka_forced_tape (reverse mode through the forced step), in the same two forms, and the cell gather of its thickness terms.
 #include "kernels_common.hpp"
+#include "mvmix_index.hpp"
 
 namespace moka {
 
@@ -104,61 +106,39 @@ struct MvmixTileCol {
     __device__ __forceinline__ void emit(int k, double inc) { xs[k] = xs[k] + inc; }
 };
 
-// element e of a tile's span -> its place in a column set (magic = 2^32 / K + 1: exact while e * K < 2^32)
-__device__ __forceinline__ unsigned mv_slot(unsigned e, unsigned magic, unsigned K, unsigned cs, unsigned &col)
+// The staging of a tile, shared by the forward pass and its transpose (mvmix_index.hpp holds mv_slot and the span arithmetic).
+// mv_stage_span: the nEl doubles of a tile's span of an (K, nE) field into a column set, as they lie.
+__device__ __forceinline__ void mv_stage_span(double *const S, const double *const G, const unsigned nEl, const int tid, const unsigned magic,
+                                              const unsigned K, const unsigned cs)
 {
-    col = __umulhi(e, magic);
-    return col * cs + (e - col * K);
-}
-
-template <bool DRAG, bool STRESS>
-__global__ __launch_bounds__(MV_NT) void k_mvmix_tile(const MomVmixArgs a, const int te, const int cs, const unsigned magic)
-{
-    extern __shared__ __align__(16) unsigned char mv_smem[];
-    double *const H = reinterpret_cast<double *>(mv_smem), *const X = H + (size_t)te * cs, *const Y = X + (size_t)te * cs;
-    int4 *const hd = reinterpret_cast<int4 *>(Y + (size_t)te * cs);        // {c1, c2, -, n}: (3 te cs) doubles in, te even: 16-byte aligned
-    const int tid = threadIdx.x, K = a.K;
-    const int e0 = blockIdx.x * te, ncol = min(te, a.nE - e0);
-    const unsigned nEl = (unsigned)ncol * (unsigned)K;
-    const size_t base = (size_t)e0 * K;
-    int n = 0;
-    double b = 0.0;
-    if (tid < te) {
-        int4 r = make_int4(0, 0, 0, 0);
-        if (tid < ncol) {
-            r = *reinterpret_cast<const int4 *>(a.ehdr + (size_t)(e0 + tid) * 4);
-            n = mvmix_depth<DRAG, STRESS>(r.w, K);
-            if (STRESS && n > 0) b = a.dt * a.tau[e0 + tid];
-        }
-        r.w = n;
-        hd[tid] = r;
-    }
-    double *const uG = a.u + base;
-    const double *const hG = a.h;
-    const bool vec = (reinterpret_cast<uintptr_t>(uG) & 15) == 0, vecH = (reinterpret_cast<uintptr_t>(hG) & 15) == 0;
-    // u: the span as it lies
+    const bool vec = (reinterpret_cast<uintptr_t>(G) & 15) == 0;
     for (unsigned i0 = 2u * tid; i0 < nEl; i0 += 2u * MV_NT * MV_U) {
         double2 vx[MV_U];
 #pragma unroll
         for (int u = 0; u < MV_U; ++u) {
             const unsigned e = i0 + 2u * MV_NT * u;
             vx[u] = make_double2(0.0, 0.0);
-            if (vec && e + 1 < nEl) vx[u] = *reinterpret_cast<const double2 *>(uG + e);
+            if (vec && e + 1 < nEl) vx[u] = *reinterpret_cast<const double2 *>(G + e);
             else if (e < nEl) {
-                vx[u].x = uG[e];
-                if (e + 1 < nEl) vx[u].y = uG[e + 1];
+                vx[u].x = G[e];
+                if (e + 1 < nEl) vx[u].y = G[e + 1];
             }
         }
 #pragma unroll
         for (int u = 0; u < MV_U; ++u) {
             const unsigned e = i0 + 2u * MV_NT * u;
             unsigned cc;
-            if (e < nEl) X[mv_slot(e, magic, K, cs, cc)] = vx[u].x;
-            if (e + 1 < nEl) X[mv_slot(e + 1, magic, K, cs, cc)] = vx[u].y;
+            if (e < nEl) S[mv_slot(e, magic, K, cs, cc)] = vx[u].x;
+            if (e + 1 < nEl) S[mv_slot(e + 1, magic, K, cs, cc)] = vx[u].y;
         }
     }
-    __syncthreads();                                // the records are in place
-    // h_e: gathered from the two cell columns of every edge, active levels only
+}
+
+// mv_gather_h: h_e of every element (column, k) with k < hd[column].w from the two cell columns {hd.x, hd.y} of the edge
+__device__ __forceinline__ void mv_gather_h(double *const H, const double *const hG, const int4 *const hd, const unsigned nEl, const int tid,
+                                            const unsigned magic, const unsigned K, const unsigned cs)
+{
+    const bool vecH = (reinterpret_cast<uintptr_t>(hG) & 15) == 0;
     for (unsigned i0 = 2u * tid; i0 < nEl; i0 += 2u * MV_NT * MV_U) {
         double2 v1[MV_U], v2[MV_U];
         unsigned qa[MV_U], qb[MV_U];
@@ -197,32 +177,67 @@ __global__ __launch_bounds__(MV_NT) void k_mvmix_tile(const MomVmixArgs a, const
             if (okB[u]) H[qb[u]] = 0.5 * (v1[u].y + v2[u].y);
         }
     }
+}
+
+// mv_store_span: a column set back into the span, the rows k < depth of a column only (depth = hd.w, or hd.z with WZ: the transpose
+// keeps the depth it writes apart from the depth it stages)
+template <bool WZ>
+__device__ __forceinline__ void mv_store_span(const double *const S, double *const G, const int4 *const hd, const unsigned nEl, const int tid,
+                                              const unsigned magic, const unsigned K, const unsigned cs)
+{
+    const bool vec = (reinterpret_cast<uintptr_t>(G) & 15) == 0;
+    for (unsigned i0 = 2u * tid; i0 < nEl; i0 += 2u * MV_NT) {
+        const unsigned e = i0;
+        unsigned ca, cb = 0;
+        const unsigned qA = mv_slot(e, magic, K, cs, ca);
+        const bool okA = (int)(e - ca * K) < (WZ ? hd[ca].z : hd[ca].w);
+        bool okB = false;
+        double2 o = make_double2(0.0, 0.0);
+        if (okA) o.x = S[qA];
+        if (e + 1 < nEl) {
+            const unsigned qB = mv_slot(e + 1, magic, K, cs, cb);
+            okB = (int)(e + 1 - cb * K) < (WZ ? hd[cb].z : hd[cb].w);
+            if (okB) o.y = S[qB];
+        }
+        if (vec && okA && okB) *reinterpret_cast<double2 *>(G + e) = o;
+        else {
+            if (okA) G[e] = o.x;
+            if (okB) G[e + 1] = o.y;
+        }
+    }
+}
+
+template <bool DRAG, bool STRESS>
+__global__ __launch_bounds__(MV_NT) void k_mvmix_tile(const MomVmixArgs a, const int te, const int cs, const unsigned magic)
+{
+    extern __shared__ __align__(16) unsigned char mv_smem[];
+    double *const H = reinterpret_cast<double *>(mv_smem), *const X = H + (size_t)te * cs, *const Y = X + (size_t)te * cs;
+    int4 *const hd = reinterpret_cast<int4 *>(Y + (size_t)te * cs);        // {c1, c2, -, n}: (3 te cs) doubles in, te even: 16-byte aligned
+    const int tid = threadIdx.x, K = a.K;
+    const MvSpan sp = mv_span(blockIdx.x, te, a.nE, K);
+    int n = 0;
+    double b = 0.0;
+    if (tid < te) {
+        int4 r = make_int4(0, 0, 0, 0);
+        if (tid < sp.ncol) {
+            r = *reinterpret_cast<const int4 *>(a.ehdr + (size_t)(sp.e0 + tid) * 4);
+            n = mvmix_depth<DRAG, STRESS>(r.w, K);
+            if (STRESS && n > 0) b = a.dt * a.tau[sp.e0 + tid];
+        }
+        r.w = n;
+        hd[tid] = r;
+    }
+    double *const uG = a.u + sp.base;
+    mv_stage_span(X, uG, sp.nEl, tid, magic, K, cs);            // u: the span as it lies
+    __syncthreads();                                            // the records are in place
+    mv_gather_h(H, a.h, hd, sp.nEl, tid, magic, K, cs);         // h_e: gathered from the two cell columns of every edge, active levels only
     __syncthreads();
     if (n > 0) {
         MvmixTileCol col{H + (size_t)tid * cs, X + (size_t)tid * cs, Y + (size_t)tid * cs};
         mvmix_column<DRAG, STRESS>(col, n, a.dt * a.nu, a.dt * a.drag, b);
     }
     __syncthreads();
-    // back: the rows k < n of a column only
-    for (unsigned i0 = 2u * tid; i0 < nEl; i0 += 2u * MV_NT) {
-        const unsigned e = i0;
-        unsigned ca, cb = 0;
-        const unsigned qA = mv_slot(e, magic, K, cs, ca);
-        const bool okA = (int)(e - ca * K) < hd[ca].w;
-        bool okB = false;
-        double2 o = make_double2(0.0, 0.0);
-        if (okA) o.x = X[qA];
-        if (e + 1 < nEl) {
-            const unsigned qB = mv_slot(e + 1, magic, K, cs, cb);
-            okB = (int)(e + 1 - cb * K) < hd[cb].w;
-            if (okB) o.y = X[qB];
-        }
-        if (vec && okA && okB) *reinterpret_cast<double2 *>(uG + e) = o;
-        else {
-            if (okA) uG[e] = o.x;
-            if (okB) uG[e + 1] = o.y;
-        }
-    }
+    mv_store_span<false>(X, uG, hd, sp.nEl, tid, magic, K, cs); // back: the rows k < n of a column only
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -263,7 +278,7 @@ static hipError_t launch_mvmix_with(const MomVmixArgs &a, const VmixKernel &k, h
         const size_t lds = k.lds + 12 * (size_t)k.tc;       // the records take 16 bytes a column where vmix_kernel counts 4
         if (lds > 64 * 1024)
             if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_mvmix_tile<DRAG, STRESS>)}, 80 * 1024); e != hipSuccess) return e;
-        const unsigned magic = (unsigned)((1ull << 32) / (unsigned)a.K) + 1u;
+        const unsigned magic = mv_magic((unsigned)a.K);
         hipLaunchKernelGGL((k_mvmix_tile<DRAG, STRESS>), dim3((a.nE + k.tc - 1) / k.tc), dim3(MV_NT), lds, s, a, k.tc, a.K | 1, magic);
     } else {
         hipLaunchKernelGGL((k_mvmix_column<DRAG, STRESS>), dim3((a.nE + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, a);
@@ -282,6 +297,287 @@ hipError_t launch_momentum_vmix(const MomVmixArgs &a, bool generic, hipStream_t 
     if (k.form == 2 && !a.scratch) return hipErrorInvalidValue;
     return drag ? (stress ? launch_mvmix_with<true, true>(a, k, s) : launch_mvmix_with<true, false>(a, k, s))
                 : (stress ? launch_mvmix_with<false, true>(a, k, s) : launch_mvmix_with<false, false>(a, k, s));
+}
+
+// ================================================================================================
+// The transposed pass (moka_forced_tape): include/moka_hip.h states the recipe; this is it, once, for one edge column of n >= 1 levels.
+// A = diag(h) + s W + q e_{n-1} e_{n-1}^T is symmetric, so z = Solve_A(xu) takes the forward's factorisation and sweep with xu as the
+// right-hand side; then, ascending, hm[k] = 0.5 * (h[k] + h[k+1]), w[k] = s / hm[k] (the forward's bits), D = z[k] - z[k+1],
+// E = un[k] - un[k+1], P[k] = (w[k] / hm[k]) * (D * E), Rn = R(un) as mvmix_column forms R, hbar[k] = 0.5 * (P[k-1] + P[k]) - z[k] *
+// (Rn[k] / h[k]) (end rows: 0.5 * the one P; n == 1: 0.0 - z[0] * (Rn[0] / h[0])), xu[k] = h[k] * z[k].  GRAD: the three densities.
+// The accessor C:
+//     h(k), xu(k), un(k)     edge thickness, the adjoint's right-hand side (read once, before putY(k)), the recorded u_new
+//     putG / g, putY / y     the sweep's two work columns; y[k] takes z[k]
+//     putHbar, putXU         the results (an accessor of a column the forward pass skipped drops them)
+// ================================================================================================
+template <bool DRAG, bool STRESS, bool GRAD, class C>
+__device__ __forceinline__ void mvadj_column(C &c, const int n, const double s, const double q, const double b, const double dt,
+                                             double *const gt, double *const dn, double *const dr)
+{
+    double hk = c.h(0);
+    if (n == 1) {
+        double d = hk, r = 0.0;
+        if (DRAG) d = d + q;
+        const double z = c.xu(0) / d, uk = c.un(0);
+        if (STRESS) r = r + b;
+        if (DRAG) r = r - q * uk;
+        c.putHbar(0, 0.0 - z * (r / hk));
+        c.putXU(0, hk * z);
+        if (GRAD) {                                 // (the sum of D_nu is empty: the density is left alone)
+            if (gt) *gt = *gt + dt * z;
+            if (dr) *dr = *dr - dt * (z * uk);
+        }
+        return;
+    }
+    double hn = c.h(1);
+    double w = s / (0.5 * (hk + hn));               // w[0]
+    double beta = hk + w;                           // d[0]
+    double y = c.xu(0) / beta;
+    c.putY(0, y);
+    for (int k = 1; k < n; ++k) {
+        const double wp = w;                        // w[k-1]
+        hk = hn;
+        const double g = wp / beta;
+        c.putG(k - 1, g);
+        double d;
+        if (k < n - 1) {
+            hn = c.h(k + 1);
+            w = s / (0.5 * (hk + hn));
+            d = (hk + wp) + w;
+        } else {
+            d = hk + wp;
+            if (DRAG) d = d + q;
+        }
+        beta = d - wp * g;
+        y = (c.xu(k) + wp * y) / beta;
+        c.putY(k, y);
+    }
+    double z = y;                                   // z[n-1] already sits in y[n-1]
+    for (int k = n - 2; k >= 0; --k) {
+        z = c.y(k) + c.g(k) * z;
+        c.putY(k, z);
+    }
+    const double z0 = z;
+    // ascending: hbar and h o z
+    hk = c.h(0); hn = c.h(1);
+    double zk = z0, zn = c.y(1), uk = c.un(0), un = c.un(1), um = 0.0;
+    double hm = 0.5 * (hk + hn);
+    w = s / hm;
+    double de = (zk - zn) * (uk - un);
+    double P = (w / hm) * de, sum = 0.0;
+    if (GRAD) sum = sum + de / hm;
+    double r = w * (un - uk);
+    if (STRESS) r = r + b;
+    c.putHbar(0, 0.5 * P - zk * (r / hk));
+    c.putXU(0, hk * zk);
+    for (int k = 1; k < n; ++k) {
+        const double Pp = P, wp = w;
+        um = uk; uk = un; hk = hn; zk = zn;
+        double hb;
+        if (k < n - 1) {
+            hn = c.h(k + 1); un = c.un(k + 1); zn = c.y(k + 1);
+            hm = 0.5 * (hk + hn);
+            w = s / hm;
+            de = (zk - zn) * (uk - un);
+            P = (w / hm) * de;
+            if (GRAD) sum = sum + de / hm;
+            r = wp * (um - uk) + w * (un - uk);
+            hb = 0.5 * (Pp + P) - zk * (r / hk);
+        } else {
+            r = wp * (um - uk);
+            if (DRAG) r = r - q * uk;
+            hb = 0.5 * Pp - zk * (r / hk);
+        }
+        c.putHbar(k, hb);
+        c.putXU(k, hk * zk);
+    }
+    if (GRAD) {
+        if (gt) *gt = *gt + dt * z0;
+        if (dn) *dn = *dn - dt * sum;
+        if (dr) *dr = *dr - dt * (zk * uk);         // row n - 1
+    }
+}
+
+// the two depths of a column in a launch of the transpose: nw, the rows whose xu and hbar it writes -- the forward's mvmix_depth, 0
+// for a step that ran without the pass -- and n >= nw, the rows it solves: with GRAD every column that has an active level
+template <bool DRAG, bool STRESS, bool GRAD>
+__device__ __forceinline__ int mvadj_depth(const int mlt, const int K, const int on, int &nw)
+{
+    nw = on ? mvmix_depth<DRAG, STRESS>(mlt, K) : 0;
+    return GRAD ? max(min(mlt, K), 0) : nw;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Form 1, tile: the forward tile with four column sets --
+//     set 0: h_e | set 1: xu, its slot k taking y[k], then z[k], then h[k] * z[k] | set 2: g, its slot k taking hbar[k] | set 3: un
+// -- and the record {c1, c2, nw, n}.  xu and un are staged as spans, h_e gathered for the rows k < n, xu and hbar go back as spans,
+// rows k < nw only.  vmix_kernel(K, generic, 4) holds the choice of te: at most 32 * 79 * 8 * 4 + 16 * 32 = 81,408 bytes a tile.
+// ------------------------------------------------------------------------------------------------
+struct MvadjTileCol {
+    double *hs, *xs, *gs, *us;
+    __device__ __forceinline__ double h(int k) const { return hs[k]; }
+    __device__ __forceinline__ double xu(int k) const { return xs[k]; }
+    __device__ __forceinline__ double un(int k) const { return us[k]; }
+    __device__ __forceinline__ void putG(int k, double v) { gs[k] = v; }
+    __device__ __forceinline__ double g(int k) const { return gs[k]; }
+    __device__ __forceinline__ void putY(int k, double v) { xs[k] = v; }
+    __device__ __forceinline__ double y(int k) const { return xs[k]; }
+    __device__ __forceinline__ void putHbar(int k, double v) { gs[k] = v; }
+    __device__ __forceinline__ void putXU(int k, double v) { xs[k] = v; }
+};
+
+template <bool DRAG, bool STRESS, bool GRAD>
+__global__ __launch_bounds__(MV_NT) void k_mvadj_tile(const MomVmixAdjArgs a, const int te, const int cs, const unsigned magic)
+{
+    extern __shared__ __align__(16) unsigned char mv_smem[];
+    const size_t set = (size_t)te * cs;
+    double *const H = reinterpret_cast<double *>(mv_smem), *const X = H + set, *const Gs = X + set, *const U = Gs + set;
+    int4 *const hd = reinterpret_cast<int4 *>(U + set);                    // (4 te cs) doubles in, te even: 16-byte aligned
+    const int tid = threadIdx.x, K = a.K;
+    const MvSpan sp = mv_span(blockIdx.x, te, a.nE, K);
+    int n = 0;
+    double b = 0.0;
+    if (tid < te) {
+        int4 r = make_int4(0, 0, 0, 0);
+        if (tid < sp.ncol) {
+            r = *reinterpret_cast<const int4 *>(a.ehdr + (size_t)(sp.e0 + tid) * 4);
+            int nw;
+            n = mvadj_depth<DRAG, STRESS, GRAD>(r.w, K, a.on, nw);
+            if (STRESS && n > 0) b = a.dt * a.tau[sp.e0 + tid];
+            r.z = nw;
+        }
+        r.w = n;
+        hd[tid] = r;
+    }
+    mv_stage_span(X, a.xu + sp.base, sp.nEl, tid, magic, K, cs);
+    mv_stage_span(U, a.un + sp.base, sp.nEl, tid, magic, K, cs);
+    __syncthreads();
+    mv_gather_h(H, a.hn, hd, sp.nEl, tid, magic, K, cs);
+    __syncthreads();
+    if (n > 0) {
+        const size_t o = (size_t)tid * cs;
+        const int e = sp.e0 + tid;
+        MvadjTileCol col{H + o, X + o, Gs + o, U + o};
+        mvadj_column<DRAG, STRESS, GRAD>(col, n, a.dt * a.nu, a.dt * a.drag, b, a.dt, GRAD && a.Gtau ? a.Gtau + e : nullptr,
+                                         GRAD && a.Dnu ? a.Dnu + e : nullptr, GRAD && a.Dr ? a.Dr + e : nullptr);
+    }
+    __syncthreads();
+    mv_store_span<true>(X, a.xu + sp.base, hd, sp.nEl, tid, magic, K, cs);
+    mv_store_span<true>(Gs, a.hbar + sp.base, hd, sp.nEl, tid, magic, K, cs);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Form 2, column: a lane per edge from global memory, g and y in the level-major scratch of the forward's column form.
+// ------------------------------------------------------------------------------------------------
+struct MvadjGlobalCol {
+    const double *h1, *h2, *uc;
+    double *xc, *hb, *gs, *ys;
+    size_t nE;
+    bool wr;                          // the forward pass computed this column: its xu and hbar are written
+    __device__ __forceinline__ double h(int k) const { return 0.5 * (h1[k] + h2[k]); }
+    __device__ __forceinline__ double xu(int k) const { return xc[k]; }
+    __device__ __forceinline__ double un(int k) const { return uc[k]; }
+    __device__ __forceinline__ void putG(int k, double v) { gs[k * nE] = v; }
+    __device__ __forceinline__ double g(int k) const { return gs[k * nE]; }
+    __device__ __forceinline__ void putY(int k, double v) { ys[k * nE] = v; }
+    __device__ __forceinline__ double y(int k) const { return ys[k * nE]; }
+    __device__ __forceinline__ void putHbar(int k, double v) { if (wr) hb[k] = v; }
+    __device__ __forceinline__ void putXU(int k, double v) { if (wr) xc[k] = v; }
+};
+
+template <bool DRAG, bool STRESS, bool GRAD>
+__global__ __launch_bounds__(BLOCK) void k_mvadj_column(const MomVmixAdjArgs a)
+{
+    const int e = blockIdx.x * BLOCK + threadIdx.x;
+    if (e >= a.nE) return;
+    const int4 r = *reinterpret_cast<const int4 *>(a.ehdr + (size_t)e * 4);
+    int nw;
+    const int n = mvadj_depth<DRAG, STRESS, GRAD>(r.w, a.K, a.on, nw);
+    if (n == 0) return;
+    const size_t nEK = (size_t)a.nE * a.K, o = (size_t)e * a.K;
+    MvadjGlobalCol col{a.hn + (size_t)r.x * a.K, a.hn + (size_t)r.y * a.K, a.un + o, a.xu + o, a.hbar + o, a.scratch + e, a.scratch + nEK + e,
+                       (size_t)a.nE, nw > 0};
+    mvadj_column<DRAG, STRESS, GRAD>(col, n, a.dt * a.nu, a.dt * a.drag, STRESS ? a.dt * a.tau[e] : 0.0, a.dt, GRAD && a.Gtau ? a.Gtau + e : nullptr,
+                                     GRAD && a.Dnu ? a.Dnu + e : nullptr, GRAD && a.Dr ? a.Dr + e : nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The cell gather: xh[k,c] = xh[k,c] + 0.5 * (the sum, from 0.0, over the slots i of edgesOnCell[c] in ascending order whose edge the
+// forward pass computed and has k < n_e, of hbar[k,e]).  LPC lanes run along the contiguous column of a cell; an element no slot
+// reaches is not written; rows of hbar at and below an edge's depth are never read.  No atomics.
+// ------------------------------------------------------------------------------------------------
+template <bool DRAG, bool STRESS>
+__global__ __launch_bounds__(BLOCK) void k_mvadj_gather(const MomVmixAdjArgs a, const int lpc)
+{
+    const int t = blockIdx.x * BLOCK + threadIdx.x;
+    const int c = t / lpc, l = t - c * lpc;
+    if (c >= a.nC) return;
+    for (int k = l; k < a.K; k += lpc) {
+        double sum = 0.0;
+        bool any = false;
+        for (int i = 0; i < a.ME; ++i) {
+            const int e = a.eoc[(size_t)c * a.ME + i];
+            if (e < 0) continue;
+            if (k < mvmix_depth<DRAG, STRESS>(a.ehdr[(size_t)e * 4 + 3], a.K)) {
+                sum = sum + a.hbar[(size_t)e * a.K + k];
+                any = true;
+            }
+        }
+        if (any) a.xh[(size_t)c * a.K + k] = a.xh[(size_t)c * a.K + k] + 0.5 * sum;
+    }
+}
+
+template <bool DRAG, bool STRESS, bool GRAD>
+static hipError_t launch_mvadj_with(const MomVmixAdjArgs &a, const VmixKernel &k, hipStream_t s)
+{
+    if (k.form == 1) {
+        const size_t lds = mv_tile_lds(4, k.tc, a.K);        // k.lds + 12 * k.tc: the records take 16 bytes a column where vmix_kernel counts 4
+        if (lds > 64 * 1024)
+            if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_mvadj_tile<DRAG, STRESS, GRAD>)}, 80 * 1024); e != hipSuccess) return e;
+        hipLaunchKernelGGL((k_mvadj_tile<DRAG, STRESS, GRAD>), dim3((a.nE + k.tc - 1) / k.tc), dim3(MV_NT), lds, s, a, k.tc, a.K | 1,
+                           mv_magic((unsigned)a.K));
+    } else {
+        hipLaunchKernelGGL((k_mvadj_column<DRAG, STRESS, GRAD>), dim3((a.nE + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, a);
+    }
+    return hipGetLastError();
+}
+
+template <bool GRAD>
+static hipError_t launch_mvadj_grad(const MomVmixAdjArgs &a, const VmixKernel &k, hipStream_t s)
+{
+    const bool drag = a.drag != 0.0, stress = a.tau != nullptr;
+    return drag ? (stress ? launch_mvadj_with<true, true, GRAD>(a, k, s) : launch_mvadj_with<true, false, GRAD>(a, k, s))
+                : (stress ? launch_mvadj_with<false, true, GRAD>(a, k, s) : launch_mvadj_with<false, false, GRAD>(a, k, s));
+}
+
+int momentum_vmix_adjoint_form(int K, bool generic) { return vmix_kernel(K, generic, 4).form; }
+
+hipError_t launch_momentum_vmix_adjoint(const MomVmixAdjArgs &a, bool generic, hipStream_t s)
+{
+    const bool drag = a.drag != 0.0, stress = a.tau != nullptr, grad = a.Gtau || a.Dnu || a.Dr;
+    if (a.nE <= 0 || a.K < 1 || (!grad && (!a.on || (a.K < 2 && !drag && !stress)))) return hipSuccess;
+    if ((uint64_t)a.K * 64u >= (1ull << 32)) return hipErrorInvalidValue;
+    if (!a.xu || !a.un || !a.hn || !a.hbar) return hipErrorInvalidValue;
+    const VmixKernel k = vmix_kernel(a.K, generic, 4);
+    if (k.form == 2 && !a.scratch) return hipErrorInvalidValue;
+    return grad ? launch_mvadj_grad<true>(a, k, s) : launch_mvadj_grad<false>(a, k, s);
+}
+
+hipError_t launch_momentum_vmix_gather(const MomVmixAdjArgs &a, hipStream_t s)
+{
+    const bool drag = a.drag != 0.0, stress = a.tau != nullptr;
+    if (a.nC <= 0 || a.K < 1 || !a.on || (a.K < 2 && !drag && !stress)) return hipSuccess;
+    int lpc = 1;
+    while (lpc < a.K && lpc < 64) lpc *= 2;
+    const dim3 grid((unsigned)(((size_t)a.nC * lpc + BLOCK - 1) / BLOCK));
+    if (drag) {
+        if (stress) hipLaunchKernelGGL((k_mvadj_gather<true, true>), grid, dim3(BLOCK), 0, s, a, lpc);
+        else hipLaunchKernelGGL((k_mvadj_gather<true, false>), grid, dim3(BLOCK), 0, s, a, lpc);
+    } else {
+        if (stress) hipLaunchKernelGGL((k_mvadj_gather<false, true>), grid, dim3(BLOCK), 0, s, a, lpc);
+        else hipLaunchKernelGGL((k_mvadj_gather<false, false>), grid, dim3(BLOCK), 0, s, a, lpc);
+    }
+    return hipGetLastError();
 }
 
 }  // namespace moka

@@ -164,6 +164,10 @@ struct moka_state {
     // where they are (moka_state_optimize_placement refuses)
     int attached = 0;
     int dycoreTapes = 0;              // live moka_tape objects on this state (moka_set_nonlinear refuses while one exists)
+    // a live moka_forced_tape on this state (at most one; the moka_tape it embeds is counted here, not in dycoreTapes: the setters of the
+    // vertical momentum pass keep working beside it) and the steps it holds (moka_surface_stress_upload refuses while there are any)
+    int forcedTapes = 0;
+    int64_t forcedSteps = 0;
     std::vector<moka_placement_trial> placementLog;   // what the last moka_state_optimize_placement tried
     int64_t placementLaunches = 0;                    // ... and how many stage launches it issued (measurement bookkeeping)
 };

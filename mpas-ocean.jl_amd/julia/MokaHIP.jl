@@ -755,4 +755,65 @@ tracer_adjoint_path(t::TracerTape) = Int(ccall((:moka_tracer_adjoint_path, lib),
 # the same for the vertical pass of the last reverse step: 1 the tile form, 2 the column form, 0 none yet
 tracer_adjoint_vmix_path(t::TracerTape) = Int(ccall((:moka_tracer_adjoint_vmix_path, lib), Cint, (Ptr{Cvoid},), t.handle))
 
+# reverse mode through the forced RK4 step (include/moka_hip.h states the algebra): the gradient of a functional of the final state with
+# respect to the state at the start of the first recorded step and, when flagged before the first recorded step, with respect to the
+# surface stress (per edge), the vertical viscosity and the bottom drag.  Linear dycore, whole meshes, Float64.
+const FORCED_GRAD_STRESS = Cint(1)
+const FORCED_GRAD_VISCOSITY = Cint(2)
+const FORCED_GRAD_DRAG = Cint(4)
+mutable struct ForcedTape
+    handle::Ptr{Cvoid}
+    state::State
+end
+function ForcedTape(Prog::MProg, capacity::Integer)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    ref = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:moka_forced_tape_create, lib), Cint, (Ptr{Cvoid}, Int64, Ref{Ptr{Cvoid}}), s.handle, capacity, ref), s.backend.ctx)
+    t = ForcedTape(ref[], s)           # holds the state (hence mesh and context count) alive
+    retain!(s.backend)
+    s.tapes += 1
+    finalizer(t) do x
+        ccall((:moka_forced_tape_destroy, lib), Cvoid, (Ptr{Cvoid},), x.handle)
+        x.state.tapes -= 1
+        x.state.dead && x.state.tapes == 0 && destroy_state!(x.state)
+        release!(x.state.backend)
+    end
+    t
+end
+function step_rk4!(t::ForcedTape, dt)
+    check(ccall((:moka_step_rk4_forced_taped, lib), Cint, (Ptr{Cvoid}, Cdouble), t.handle, dt), t.state.backend.ctx)
+    device_changed!(t.state)
+end
+# what: a sum of FORCED_GRAD_*; only while no step is recorded
+function want_gradient!(t::ForcedTape, what::Integer, on::Bool = true)
+    check(ccall((:moka_forced_adjoint_want_gradient, lib), Cint, (Ptr{Cvoid}, Cint, Cint), t.handle, what, on ? 1 : 0), t.state.backend.ctx)
+end
+# seeds with d sum(ssh^2) at the current state -- or, with seed_u and seed_h, (nVertLevels, nEdges) and (nVertLevels, nCells), with those --
+# sweeps the tape backwards and fills d_u, d_h
+function gradient!(d_u::Array{Float64}, d_h::Array{Float64}, t::ForcedTape; seed_u = nothing, seed_h = nothing)
+    ctx = t.state.backend.ctx
+    if seed_u === nothing
+        check(ccall((:moka_forced_adjoint_seed_sum_sq_ssh, lib), Cint, (Ptr{Cvoid},), t.handle), ctx)
+    else
+        check(ccall((:moka_forced_adjoint_seed, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), t.handle, seed_u, seed_h), ctx)
+    end
+    check(ccall((:moka_forced_adjoint_sweep, lib), Cint, (Ptr{Cvoid},), t.handle), ctx)
+    check(ccall((:moka_forced_adjoint_download, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), t.handle, F_U, d_u), ctx)
+    check(ccall((:moka_forced_adjoint_download, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), t.handle, F_H, d_h), ctx)
+end
+# the per-edge density of one FORCED_GRAD_* bit into `out` (nEdges values; for the stress: d J / d tau_e itself)
+function forced_density!(out::Array{Float64}, t::ForcedTape, what::Integer)
+    check(ccall((:moka_forced_adjoint_density_download, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), t.handle, what, out), t.state.backend.ctx)
+    out
+end
+# d J / d nuV (FORCED_GRAD_VISCOSITY) or d J / d r (FORCED_GRAD_DRAG): the host sum of the density
+function forced_gradient(t::ForcedTape, what::Integer)
+    out = Ref{Float64}(0.0)
+    check(ccall((:moka_forced_adjoint_gradient, lib), Cint, (Ptr{Cvoid}, Cint, Ref{Float64}), t.handle, what, out), t.state.backend.ctx)
+    out[]
+end
+# 1 the tile form, 2 the column form of the last transposed vertical pass, 0 none yet
+forced_vmix_path(t::ForcedTape) = Int(ccall((:moka_forced_tape_vmix_path, lib), Cint, (Ptr{Cvoid},), t.handle))
+
 end # module

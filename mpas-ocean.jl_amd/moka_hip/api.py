@@ -30,7 +30,7 @@ __all__ = [
     "Clock", "OneTimeAlarm", "PeriodicAlarm", "Alarm", "advance", "isRinging", "reset", "stop", "changeTimeStep",
     "attachAlarm", "setCurrentTime", "ocn_setup_clock", "ocn_setup_mesh", "ocn_init", "write_netcdf",
     "ConfigRead", "ConfigGet", "GlobalConfig", "AdjointTape", "set_nonlinear", "REFERENCE_COMPAT", "prognostic_vars_best_placement",
-    "set_tracers", "Tracers", "TracerAdjointTape",
+    "set_tracers", "Tracers", "TracerAdjointTape", "ForcedAdjointTape",
     "set_vertical_mixing", "vertical_mixing", "momentum_vmix_path",
 ]
 
@@ -1037,6 +1037,91 @@ class TracerAdjointTape:
     def close(self):
         if self._h:
             _release(self, L.lib().moka_tracer_tape_destroy, self._h)
+            self._h = C.c_void_p()
+
+
+class ForcedAdjointTape:
+    """Reverse mode through the forced RK4 step (moka_forced_tape_*; include/moka_hip.h states the algebra): record RK4 steps of a
+    linear-dycore model whose vertical momentum pass (set_vertical_mixing) may be on, then turn d J / d (state after the last step)
+    into d J / d (state before the first recorded step) and, when flagged before the first recorded step, d J / d tau_e per edge,
+    d J / d nuV and d J / d r with their per-edge densities.  The parameters act identically in every recorded step."""
+
+    _BITS = {"surfaceStress": L.FORCED_GRAD_STRESS, "viscosity": L.FORCED_GRAD_VISCOSITY, "bottomDrag": L.FORCED_GRAD_DRAG}
+
+    def __init__(self, Prog: "PrognosticVars", capacity_steps: int):
+        self._state = Prog._state
+        self._ctx = self._state.mesh.backend._h
+        self._ushape = tuple(Prog.normalVelocity[-1].shape)
+        self._hshape = tuple(Prog.layerThickness[-1].shape)
+        self._want = 0
+        self._h = C.c_void_p()
+        L.check(L.lib().moka_forced_tape_create(self._state._h, int(capacity_steps), C.byref(self._h)), self._ctx)
+        _own(self, L.lib().moka_forced_tape_destroy, self._h, self._state, self._state.mesh, self._state.mesh.backend)
+        self._state._dependents.append(weakref.ref(self))
+
+    def step(self, timestep):
+        """One RK4 step of the model (bit for bit moka_step_rk4), recorded."""
+        L.check(L.lib().moka_step_rk4_forced_taped(self._h, float(np.asarray(timestep).reshape(-1)[0])), self._ctx)
+
+    def want_gradient(self, stress: bool = False, viscosity: bool = False, drag: bool = False):
+        """The set of parameter gradients the following sweeps accumulate; only while no step is recorded."""
+        want = (L.FORCED_GRAD_STRESS if stress else 0) | (L.FORCED_GRAD_VISCOSITY if viscosity else 0) | (L.FORCED_GRAD_DRAG if drag else 0)
+        if want:
+            L.check(L.lib().moka_forced_adjoint_want_gradient(self._h, want, 1), self._ctx)
+        if 7 & ~want:
+            L.check(L.lib().moka_forced_adjoint_want_gradient(self._h, 7 & ~want, 0), self._ctx)
+        self._want = want
+
+    def seed(self, u, h):
+        """X := (u, h), (nEdges, K) and (nCells, K) fields: the adjoint of the state after the last recorded step."""
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(self._ushape)
+        h = np.ascontiguousarray(h, dtype=np.float64).reshape(self._hshape)
+        L.check(L.lib().moka_forced_adjoint_seed(self._h, L.f64(u), L.f64(h)), self._ctx)
+
+    def sweep(self):
+        """Reverse over (and pop) every recorded step; the tape is then empty and reusable."""
+        L.check(L.lib().moka_forced_adjoint_sweep(self._h), self._ctx)
+
+    def density(self, what: str) -> np.ndarray:
+        """The per-edge density of "surfaceStress" (d J / d tau_e itself), "viscosity" or "bottomDrag", caller's edge numbering."""
+        out = np.empty(self._ushape[0], dtype=np.float64)
+        L.check(L.lib().moka_forced_adjoint_density_download(self._h, self._BITS[what], L.f64(out)), self._ctx)
+        return out
+
+    def download(self) -> dict:
+        """The adjoint state and the flagged parameter gradients as they stand."""
+        lib = L.lib()
+        out = {}
+        for name, fid, shape in (("normalVelocity", L.F_NORMAL_VELOCITY, self._ushape), ("layerThickness", L.F_LAYER_THICKNESS, self._hshape)):
+            a = np.empty(shape, dtype=np.float64)
+            L.check(lib.moka_forced_adjoint_download(self._h, fid, L.f64(a)), self._ctx)
+            out[name] = a
+        if self._want & L.FORCED_GRAD_STRESS:
+            out["surfaceStress"] = self.density("surfaceStress")
+        for name in ("viscosity", "bottomDrag"):
+            if self._want & self._BITS[name]:
+                v = C.c_double()
+                L.check(lib.moka_forced_adjoint_gradient(self._h, self._BITS[name], C.byref(v)), self._ctx)
+                out[name] = float(v.value)
+        return out
+
+    def gradient(self, seed=None) -> dict:
+        """Seeds -- with d sum(ssh^2) at the current state, or with seed = (u, h) -- sweeps the tape backwards (consuming it) and returns
+        normalVelocity, layerThickness and, when flagged, surfaceStress (per edge), viscosity and bottomDrag (scalars)."""
+        if seed is None:
+            L.check(L.lib().moka_forced_adjoint_seed_sum_sq_ssh(self._h), self._ctx)
+        else:
+            self.seed(*seed)
+        self.sweep()
+        return self.download()
+
+    def vmix_path(self) -> int:
+        """moka_forced_tape_vmix_path: 1 the tile form, 2 the column form of the last transposed pass, 0 none yet."""
+        return int(L.lib().moka_forced_tape_vmix_path(self._h))
+
+    def close(self):
+        if self._h:
+            _release(self, L.lib().moka_forced_tape_destroy, self._h)
             self._h = C.c_void_p()
 
 

@@ -19,6 +19,7 @@ ERR_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_ALLOC, ERR_UNSUPPORTED, ERR_COMM = -1, -2, 
 ORDER_DEFAULT, ORDER_NONE, ORDER_RCM, ORDER_RCB = 0, 1, 2, 3
 TRACER_GRAD_KAPPA, TRACER_GRAD_KAPPA4 = 1, 2       # moka_tracer_adjoint_want_diffusivity_gradient
 VGRAD_INTERFACE, VGRAD_CELL, VGRAD_PROFILE = 0, 1, 2    # moka_tracer_adjoint_vertical_density_download
+FORCED_GRAD_STRESS, FORCED_GRAD_VISCOSITY, FORCED_GRAD_DRAG = 1, 2, 4    # moka_forced_adjoint_want_gradient
 CELL, EDGE, VERTEX = 0, 1, 2
 (F_SSH, F_NORMAL_VELOCITY, F_LAYER_THICKNESS, F_LAYER_THICKNESS_EDGE, F_THICKNESS_FLUX,
  F_VELOCITY_DIV_CELL, F_RELATIVE_VORTICITY, F_TEND_NORMAL_VELOCITY, F_TEND_LAYER_THICKNESS) = range(9)
@@ -117,6 +118,9 @@ EXPORTS = [
     "moka_tracer_adjoint_vertical_density_download",
     "moka_tracer_tape_create", "moka_tracer_tape_destroy", "moka_step_rk4_tracer_taped", "moka_tracer_tape_steps",
     "moka_tracer_adjoint_seed", "moka_tracer_adjoint_sweep", "moka_tracer_adjoint_download", "moka_tracer_adjoint_path",
+    "moka_forced_tape_create", "moka_forced_tape_destroy", "moka_step_rk4_forced_taped", "moka_forced_adjoint_seed_sum_sq_ssh",
+    "moka_forced_adjoint_seed", "moka_forced_adjoint_sweep", "moka_forced_adjoint_download", "moka_forced_adjoint_want_gradient",
+    "moka_forced_adjoint_density_download", "moka_forced_adjoint_gradient", "moka_forced_tape_vmix_path",
 ]
 
 
@@ -293,6 +297,18 @@ def lib():
     L.moka_tracer_adjoint_want_vertical_gradient.argtypes = [vp, C.c_int32, C.c_int]
     L.moka_tracer_adjoint_vertical_gradient.argtypes = [vp, C.c_int32, C.POINTER(C.c_double)]
     L.moka_tracer_adjoint_vertical_density_download.argtypes = [vp, C.c_int32, C.c_int, vp]
+    L.moka_forced_tape_create.argtypes = [vp, C.c_int64, C.POINTER(vp)]
+    L.moka_forced_tape_destroy.argtypes = [vp]
+    L.moka_forced_tape_destroy.restype = None
+    L.moka_step_rk4_forced_taped.argtypes = [vp, C.c_double]
+    L.moka_forced_adjoint_seed_sum_sq_ssh.argtypes = [vp]
+    L.moka_forced_adjoint_seed.argtypes = [vp, vp, vp]
+    L.moka_forced_adjoint_sweep.argtypes = [vp]
+    L.moka_forced_adjoint_download.argtypes = [vp, C.c_int, vp]
+    L.moka_forced_adjoint_want_gradient.argtypes = [vp, C.c_int, C.c_int]
+    L.moka_forced_adjoint_density_download.argtypes = [vp, C.c_int, vp]
+    L.moka_forced_adjoint_gradient.argtypes = [vp, C.c_int, C.POINTER(C.c_double)]
+    L.moka_forced_tape_vmix_path.argtypes = [vp]
     L.moka_tape_create.argtypes = [vp, C.c_int64, C.POINTER(vp)]
     L.moka_tape_destroy.argtypes = [vp]
     L.moka_tape_destroy.restype = None
