@@ -694,6 +694,7 @@ int  moka_set_tracer_vertical_diffusion(moka_state *st, const double *kappaV);
 int  moka_tracer_vertical_diffusion(const moka_state *st, int32_t j, double *out);
 /* which kernel served the last vertical pass of this state: 1 the tile form (column tiles staged in LDS, a lane per column; nVertLevels
  * <= 105), 2 the column form (a lane per column from global memory: deeper columns, and kernel variant 3), 0 no vertical pass yet */
+/* moka_set_tracers (any count, 0 included) puts this answer, like that of moka_state_tracer_path, back to 0. */
 int  moka_state_tracer_vmix_path(const moka_state *st);
 /* A vertical diffusivity per interface and cell (default: none).  Tracer j may carry a field f_j >= 0 (m^2/s), laid out as every tracer
  * field and as D_j are: (nVertLevels, nCells) doubles, row k of a column the interface between levels k and k+1.  Rows

@@ -15,7 +15,12 @@ and the three kinds of reads, placement, kernel variants, tuning keys 4 / 8 / 9 
 B2): moka_set_tracers with a changing count, 0 included (the dycore then steps alone, also under key 7), tracer and dycore uploads,
 diffusivities, biharmonic coefficients and sources that come and go, RK4 / moka_run / advanceTimeLevels!, the nonlinear / Del2 /
 Del4 toggles, placement, reads of TendencyVars, and the tracer tape with its source and diffusivity gradients, coefficients and
-sources changing between taped steps.  Not covered: a tracer count that changes under a live tracer tape, halos and partitions
+sources changing between taped steps.  Machines C and D live in tests/call_sequences_vertical.py, on this module's Op, Obs, Model,
+TracerModel and TracerDevice: C, the forced dycore (configs C1-C4: moka_set_vertical_viscosity, moka_surface_stress_upload and
+their getters, the pass in RK4 steps and in moka_run's captured graph, Forward Euler behind a mixed step, moka_tape against the
+pass, every call of moka_forced_tape); D, tracers with the vertical passes (D1, D2: moka_set_tracer_vertical_diffusion, the
+moka_tracer_vertical_field_* calls and moka_tracer_adjoint_want_vertical_gradient with its views, beside a changing tracer count
+and the momentum pass).  Not covered by any machine: a tracer count that changes under a live tracer tape, halos and partitions
 (several processes).
 
 Replay a sequence on the CPU:   python tests/call_sequences.py A1 3 [--upto N]

@@ -67,9 +67,10 @@ def computed_depth(mlt, K, q, st, on):
     return np.where(keep & bool(on), nn, 0)
 
 
-def transposed_pass(mesh, mlt, XU, XH, un, hn, dt, nu, drag, tau, dens=None):
+def transposed_pass(mesh, mlt, XU, XH, un, hn, dt, nu, drag, tau, dens=None, depth_of=None):
     """One transposed pass on copies of XU (nEdges, K), XH (nCells, K); dens: {STRESS: G_tau, VISCOSITY: D_nu, DRAG: D_r} arrays of
-    nEdges, updated in place (absent keys are not wanted).  Returns (XU, XH)."""
+    nEdges, updated in place (absent keys are not wanted).  depth_of: another rule in the place of `computed_depth` (the call
+    sequences' mutant of it).  Returns (XU, XH)."""
     XU, XH = XU.copy(), XH.copy()
     dens = dens or {}
     K = XU.shape[1]
@@ -80,7 +81,7 @@ def transposed_pass(mesh, mlt, XU, XH, un, hn, dt, nu, drag, tau, dens=None):
     s = np.float64(dt) * np.float64(nu)
     q = np.float64(dt) * np.float64(drag) if drag != 0.0 else None
     st = mv.stress_on(tau, mlt)
-    nw = computed_depth(mlt, K, q, st, on)
+    nw = (depth_of or computed_depth)(mlt, K, q, st, on)
     nn = np.clip(np.asarray(mlt, dtype=np.int64), 0, K) if dens else nw
     hbar = np.full(XU.shape, np.nan)
     for n in np.unique(nn):
