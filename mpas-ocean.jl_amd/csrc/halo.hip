@@ -115,7 +115,7 @@ struct moka_halo {
     bool acquireFence = false;                // moka_halo_set_acquire: system-scope acquire in front of launches that read received rows
     bool overlapB = false;                    // boundary patches on the comm stream, in flight together with the interior launch
     bool overlapNow = false;                  // ... as the running step was begun
-    std::vector<void *> allocs;           // device allocations of this object
+    mk::DeviceAllocs mem;                 // device allocations of this object; mem.ctx: the state's context, valid after the state has gone
     bool counted = false;                 // st->attached includes this object
     // measurement (moka_halo_stats_enable / _read): where a distributed step spends its time on this rank
     bool statsOn = false;
@@ -158,12 +158,7 @@ int build_halo_map(moka_halo *hh, int nNbr, const int32_t *cells, const int64_t 
     *outN = (int64_t)map.size();
     *outDev = nullptr;
     if (map.empty()) return MOKA_OK;
-    void *d = nullptr;
-    HIPCHK(st->ctx, hipMalloc(&d, map.size() * sizeof(uint32_t)));
-    hh->allocs.push_back(d);
-    if (int rc = h2d(st->ctx, d, map.data(), map.size() * sizeof(uint32_t))) return rc;
-    *outDev = static_cast<uint32_t *>(d);
-    return MOKA_OK;
+    return hh->mem.upload(map, outDev);
 }
 
 // index (0..4) of the physical buffer set a LevelBufs currently names: 0/1 the two time levels as allocated, 2/3 the RK
@@ -240,12 +235,8 @@ int upload_peer_tab(moka_halo *h)
             d.ssh = static_cast<unsigned char *>(pl.mapped[3 * t + 2]) + (size_t)pl.dstCell * sb;
             tab[(size_t)t * h->nNbr + i] = d;
         }
-    if (!h->peerTab) {
-        void *d = nullptr;
-        HIPCHK(st->ctx, hipMalloc(&d, tab.size() * sizeof(PushDst)));
-        h->allocs.push_back(d);
-        h->peerTab = static_cast<PushDst *>(d);
-    }
+    if (!h->peerTab)
+        if (int rc = h->mem.alloc(&h->peerTab, tab.size())) return rc;
     if (int rc = h2d(st->ctx, h->peerTab, tab.data(), tab.size() * sizeof(PushDst))) return rc;
     h->tabDirty = false;
     return MOKA_OK;
@@ -368,6 +359,7 @@ int moka_halo_create(moka_state *st, int32_t nNeighbors, const int32_t *sendCell
     moka_halo *h = new (std::nothrow) moka_halo();
     if (!h) return fail(st->ctx, MOKA_ERR_ALLOC, "out of host memory");
     h->st = st;
+    h->mem.ctx = st->ctx;
     h->nNbr = nNeighbors;
     h->pBoundary = nPatchesBoundary; h->pOwned = nPatchesOwned;
     // The first launch of a stage holds exactly the boundary patches.  (Padding it with interior patches up to one full
@@ -421,14 +413,8 @@ int moka_halo_create(moka_state *st, int32_t nNeighbors, const int32_t *sendCell
                     rows.insert(rows.end(), {(uint32_t)p.edgeO2N[sendEdges[j]], (uint32_t)(j - sendEdgeOff[i]), (uint32_t)i | (2u << 16)});
             }
             h->nPushRows = (int64_t)rows.size() / 3;
-            if (!rows.empty()) {
-                void *d = nullptr;
-                hipError_t e = hipMalloc(&d, rows.size() * sizeof(uint32_t));
-                if (e != hipSuccess) { moka_halo_destroy(h); return fail(st->ctx, MOKA_ERR_ALLOC, "hipMalloc of the push row list failed"); }
-                h->allocs.push_back(d);
-                if ((rc = h2d(st->ctx, d, rows.data(), rows.size() * sizeof(uint32_t)))) { moka_halo_destroy(h); return rc; }
-                h->pushRows = static_cast<uint32_t *>(d);
-            }
+            if (!rows.empty())
+                if ((rc = h->mem.upload(rows, &h->pushRows))) { moka_halo_destroy(h); return rc; }
         }
     } catch (const std::bad_alloc &) {
         moka_halo_destroy(h);
@@ -448,10 +434,11 @@ int moka_halo_create(moka_state *st, int32_t nNeighbors, const int32_t *sendCell
 void moka_halo_destroy(moka_halo *h)
 {
     if (!h) return;
-    if (h->counted) state_detach(h->st, true);
-    (void)hipSetDevice(h->st->ctx->device);
-    (void)hipStreamSynchronize(h->st->ctx->stream);
-    (void)hipStreamSynchronize(h->st->ctx->comm);
+    if (h->counted) (void)state_detach(h->st, true);      // a state that has gone is not touched: everything below works with the cached context
+    moka_ctx *ctx = h->mem.ctx;
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipStreamSynchronize(ctx->comm);
     for (hipEvent_t e : h->stEv) (void)hipEventDestroy(e);
     for (PeerLink &pl : h->peers)
         if (pl.flagsDev && pl.ipc) (void)hipHostUnregister((void *)pl.flags);
@@ -471,7 +458,7 @@ void moka_halo_destroy(moka_halo *h)
     }
     if (h->evPush) (void)hipEventDestroy(h->evPush);
     for (hipEvent_t e : h->evB) if (e) (void)hipEventDestroy(e);
-    for (void *q : h->allocs) (void)hipFree(q);
+    h->mem.release_all();
     delete h;
 }
 

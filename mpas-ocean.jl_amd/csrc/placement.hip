@@ -46,7 +46,7 @@ void repoint(moka_state *st, double *oldp, double *newp)
     for (auto &b : st->rk) fix(b);
     fix(st->spare);
     for (auto &b : st->phys) fix(b);
-    for (void *&q : st->allocs) if (q == (void *)oldp) q = (void *)newp;
+    for (void *&q : st->mem.ptrs) if (q == (void *)oldp) q = (void *)newp;
 }
 
 struct Timer {

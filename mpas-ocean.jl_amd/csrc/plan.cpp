@@ -768,5 +768,5 @@ int moka_plan_array(const moka_plan *plan, int which, const void **data, int64_t
 
 }  // extern "C"
 
-// shared with api.hip
+// shared with api.hip (moka_mesh_info_get)
 namespace moka { void fill_mesh_info(const Plan &p, moka_mesh_info *info) { fill_info(p, info); } }

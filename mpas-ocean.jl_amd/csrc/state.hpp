@@ -1,8 +1,10 @@
-// state.hpp -- the objects behind the opaque handles of include/moka_hip.h and the helpers api.hip shares with halo.hip.
+// state.hpp -- the objects behind the opaque handles of include/moka_hip.h and the helpers the api*.hip files share with each other
+// and with halo.hip (the three tapes: tapes.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <utility>
@@ -32,11 +34,103 @@ struct moka_ctx {
     size_t bwBytes = 0;
 };
 
+namespace mk {
+
+int fail(moka_ctx *ctx, int code, const std::string &msg);
+// every host->device copy of the library: on the context's stream, then synchronised (see api.hip)
+int h2d(moka_ctx *ctx, void *dst, const void *src, size_t bytes);
+
+#define HIPCHK(ctx, call)                                                                          \
+    do {                                                                                           \
+        hipError_t _e = (call);                                                                    \
+        if (_e != hipSuccess)                                                                      \
+            return mk::fail(ctx, MOKA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_e)); \
+    } while (0)
+
+// The device memory a handle owns: every hipMalloc / hipFree of a mesh, a state, a tape or a halo happens here (the mesh's opBuf, the
+// context's probe buffers, placement.hip and inspect.hip manage transient memory of another kind).  A list of pointers, not a pool:
+// nothing is cached or reused.  Only rollback() synchronises: a caller that releases memory a launch may still read synchronises first.
+struct DeviceAllocs {
+    moka_ctx *ctx = nullptr;         // device and stream, set when the handle is created: a tape or halo reaches them after its state has gone
+    const char *owner = nullptr;     // "tape", ...: a failed hipMalloc is MOKA_ERR_ALLOC "<owner>: hipMalloc of N bytes: ..."; nullptr (mesh, state, halo): MOKA_ERR_HIP
+    std::vector<void *> ptrs;
+
+    int take(void **out, size_t bytes, bool zero)
+    {
+        void *d = nullptr;
+        const hipError_t e = hipMalloc(&d, std::max<size_t>(bytes, 16));
+        if (e != hipSuccess)
+            return fail(ctx, owner ? MOKA_ERR_ALLOC : MOKA_ERR_HIP,
+                        (owner ? std::string(owner) + ": " : std::string()) + "hipMalloc of " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
+        ptrs.push_back(d);
+        if (zero) HIPCHK(ctx, hipMemsetAsync(d, 0, bytes, ctx->stream));
+        *out = d;
+        return MOKA_OK;
+    }
+    // elems elements (at least 16 bytes), zeroed on the context's stream (KA.zeros).  elemBytes: the float arrays of an fp32-storage state
+    // sit behind double pointers
+    template <class T>
+    int alloc(T **out, size_t elems, size_t elemBytes = sizeof(T))
+    {
+        void *d = nullptr;
+        if (int rc = take(&d, elems * elemBytes, true)) return rc;
+        *out = static_cast<T *>(d);
+        return MOKA_OK;
+    }
+    // a copy of v (at least 16 bytes, no zero fill) through h2d; U is T or const T
+    template <class T, class U>
+    int upload(const std::vector<T> &v, U **out)
+    {
+        void *d = nullptr;
+        if (int rc = take(&d, v.size() * sizeof(T), false)) return rc;
+        if (int rc = h2d(ctx, d, v.data(), v.size() * sizeof(T))) return rc;
+        *out = static_cast<U *>(d);
+        return MOKA_OK;
+    }
+    size_t mark() const { return ptrs.size(); }
+    // back to mark(): the stream is synchronised (the zero fills), then what came since is freed, newest first
+    void rollback(size_t mark)
+    {
+        (void)hipStreamSynchronize(ctx->stream);
+        while (ptrs.size() > mark) { (void)hipFree(ptrs.back()); ptrs.pop_back(); }
+    }
+    // several arrays of doubles, all of them or none
+    int alloc_all(std::initializer_list<std::pair<double **, size_t>> what)
+    {
+        const size_t m = mark();
+        std::vector<double *> got;
+        for (auto &w : what) {
+            double *d = nullptr;
+            if (int rc = alloc(&d, w.second)) { rollback(m); return rc; }
+            got.push_back(d);
+        }
+        size_t i = 0;
+        for (auto &w : what) *w.first = got[i++];
+        return MOKA_OK;
+    }
+    // frees p and sets it to nullptr; a null p is left alone
+    template <class T>
+    void release(T *&p)
+    {
+        if (!p) return;
+        ptrs.erase(std::remove(ptrs.begin(), ptrs.end(), (void *)p), ptrs.end());
+        (void)hipFree((void *)p);
+        p = nullptr;
+    }
+    void release_all()
+    {
+        for (void *q : ptrs) (void)hipFree(q);
+        ptrs.clear();
+    }
+};
+
+}  // namespace mk
+
 struct moka_mesh {
     moka_ctx *ctx = nullptr;
     moka::Plan plan;          // host copy (permutations, sizes)
     moka::MeshDev dev{};
-    std::vector<void *> allocs;
+    mk::DeviceAllocs mem;
     int lpc = 1;
     bool colOk = false;       // byte-offset records exist (every field < 4 GiB)
     double *opBuf[4] = {nullptr, nullptr, nullptr, nullptr};   // operator scratch [0], [1], [3] / transfer staging [2], lazily sized
@@ -159,7 +253,7 @@ struct moka_state {
     double *momTau = nullptr, *momScratch = nullptr;
     bool momTauOn = false;
     int momVmixPath = 0;              // moka_state_momentum_vmix_path
-    std::vector<void *> allocs;
+    mk::DeviceAllocs mem;
     // objects that hold or have exported the addresses of this state's arrays (halos, tapes): while any exists the arrays stay
     // where they are (moka_state_optimize_placement refuses)
     int attached = 0;
@@ -176,19 +270,12 @@ namespace mk {
 
 using namespace moka;
 
-int fail(moka_ctx *ctx, int code, const std::string &msg);
 // Halos and tapes count themselves in moka_state.attached while they hold the state's addresses.  Handles may be destroyed in
 // any order (garbage-collected callers: a state can go before its tape), so the count is only touched while the state is alive.
 // halo = true: the object is a moka_halo (counted in moka_state.halos too)
 void state_attach(moka_state *st, bool halo = false);
-void state_detach(moka_state *st, bool halo = false);
-
-#define HIPCHK(ctx, call)                                                                          \
-    do {                                                                                           \
-        hipError_t _e = (call);                                                                    \
-        if (_e != hipSuccess)                                                                      \
-            return mk::fail(ctx, MOKA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_e)); \
-    } while (0)
+// false: the state has gone -- the caller skips every access to it and works with the context it cached (DeviceAllocs.ctx)
+bool state_detach(moka_state *st, bool halo = false);
 
 // The kernel choice of the linear stage launches.  The default stage kernels (launch_stage_rec2c*) may serve a Float64 state's
 // launches: kernel variant 0 (auto) or 11, 64 lanes per column, byte-offset records.  Whether they do depends on the patches too
@@ -210,9 +297,12 @@ inline bool mom_vmix_on(const moka_state *st) { return st->momNuV != 0.0 || st->
 // `form` of the nonlinear launchers: kernel variants 4 / 3 select the plainer forms of the nonlinear kernels too
 inline int nl_form(const moka_ctx *ctx) { return ctx->variant == 4 ? 1 : ctx->variant == 3 ? 3 : 0; }
 
-// every host->device copy of the library: on the context's stream, then synchronised (see api.hip)
-int h2d(moka_ctx *ctx, void *dst, const void *src, size_t bytes);
-int alloc_field(moka_state *st, double **out, size_t elems, size_t elemBytes = sizeof(double));
+// api.hip: the mesh's transfer staging and the row permutation between the caller's numbering and the device's
+int ensure_op_bufs(moka_mesh *m);
+const int32_t *perm_of(const moka_mesh *m, int kind);
+int put_rows(moka_mesh *m, double *dst, const double *host, int kind, int64_t n, int K, bool f32 = false);
+int get_rows(moka_mesh *m, double *host, const double *src, int kind, int64_t n, int K, bool f32 = false);
+// api_state.hip
 int ensure_rk_bufs(moka_state *st);
 int ensure_spare(moka_state *st);
 // the set a Forward-Euler step writes its new level to / the rotation that makes it the current level
@@ -225,7 +315,7 @@ StageArgs rk4_stage_args(moka_state *st, int s, double dt, const double *ssh0);
 LevelBufs &rk4_stage_output(moka_state *st, int s);
 int rk4_begin(moka_state *st, const double **ssh0);
 void rk4_end(moka_state *st);
-bool rk13_usable(const moka_state *st);       // the 13-stream RK4 form (moka_set_tuning key 7), see api.hip
+bool rk13_usable(const moka_state *st);       // the 13-stream RK4 form (moka_set_tuning key 7), see api_state.hip
 StageArgs rk13_stage_args(moka_state *st, int s, double dt, const double *ssh0);
 void rk13_end(moka_state *st);
 FeArgs fe_args(moka_state *st, int ops, int flags, double dt);
@@ -236,5 +326,14 @@ bool fe_stage_path(const moka_state *st, int flags);
 bool fe_lean(const moka_state *st, int flags);
 int fe_begin(moka_state *st, int flags);
 void fe_end(moka_state *st, int flags, bool stageKernel, bool lean, bool prevMode);
+// moka_step_rk4, and the same step recorded on `rec` (nullptr: not recorded); the vertical pass of the flow behind stage 4
+int step_rk4(moka_state *st, double dt, moka_tracer_tape *rec);
+int momentum_vmix(moka_state *st, double *u, const double *h, double dt);
+// api_tracers.hip: the tracer launch of RK4 stage s; the vertical pass, forwards and backwards; what it takes for tracer j
+hipError_t tracer_stage(moka_state *st, int s, const StageArgs &g);
+int tracer_vmix(moka_mesh *mm, moka_ctx *ctx, int nT, const double *h, double *x, const double *kv, const double *const *fld, double dt,
+                double *scratch, bool reverse, int *path, const int32_t *gslot = nullptr, const double *p_new = nullptr, double *D = nullptr);
+bool vfield_on(const moka_state *st, int j);
+double vmix_coefficient(const moka_state *st, const std::vector<double> &kv, int j);
 
 }  // namespace mk

@@ -3,6 +3,8 @@
 * No null-stream hipMemcpy / hipMemset in the library: its streams are non-blocking, so a null-stream copy is not ordered
   against work queued on them (the tape-list race of round 1, commit 6ebfa3e).  Every copy goes through the context's
   stream (h2d / hipMemcpyAsync / hipMemsetAsync).
+* Device memory has one owner: hipMalloc / hipFree occur in mk::DeviceAllocs (csrc/state.hpp), which every handle holds, and in
+  the few named places that manage transient memory of another kind.
 * The product never touches the oracle (test infrastructure) and has no environment-variable debug hooks.
 * The experimental stage kernels stay out of the default build.
 """
@@ -29,6 +31,43 @@ def test_no_null_stream_copies_in_the_library():
         for m in re.finditer(r"\bhipMem(cpy|set|cpyDtoH|cpyHtoD|cpyDtoD|cpyPeer)\s*\(", _code(p)):
             bad.append((os.path.basename(p), m.group(0)))
     assert not bad, bad
+
+
+# (file, enclosing function or struct) -> (hipMalloc calls, hipFree calls) outside comments.  Anything else is a hand-made allocator.
+DEVICE_MEMORY_SITES = {
+    ("state.hpp", "DeviceAllocs"): (1, 3),                 # the owner: take; rollback, release, release_all
+    ("api.hip", "moka_ctx_destroy"): (0, 1),               # the context's bandwidth-probe buffers
+    ("api.hip", "moka_bw_probe"): (1, 2),
+    ("api.hip", "moka_bw_probe_gather_big"): (1, 1),
+    ("api.hip", "ensure_op_bufs"): (1, 1),                 # the mesh's operator scratch / transfer staging, resized as a whole
+    ("api.hip", "moka_mesh_destroy"): (0, 1),              # ... and its release (the opBuf loop)
+    ("placement.hip", "moka_state_optimize_placement"): (2, 6),   # candidate arrays and saved copies of a placement search
+    ("inspect.hip", "moka_state_download_rows"): (2, 2),   # the row list and the gathered rows of one call
+}
+
+
+def _device_memory_sites():
+    """{(file, enclosing top-level function / struct): [hipMalloc calls, hipFree calls]} of csrc, comments left out.  The enclosing
+    definition is the last line before the call that starts in column 0 with a name and is no declaration."""
+    found = {}
+    for p in product_sources():
+        where = None
+        for line in _code(p).split("\n"):
+            if re.match(r"[A-Za-z_]", line) and not line.rstrip().endswith(";") and not re.match(r"(namespace|using|typedef|template)\b", line):
+                names = [n for n in re.findall(r"(\w+)\s*\(", line) if n != "__launch_bounds__"]
+                if line.startswith("struct"):
+                    where = re.match(r"struct\s+(\w+)", line).group(1)
+                elif names:
+                    where = names[0]
+            for k, name in enumerate(("hipMalloc", "hipFree")):
+                n = len(re.findall(r"\b%s\s*\(" % name, line))
+                if n:
+                    found.setdefault((os.path.basename(p), where), [0, 0])[k] += n
+    return {k: tuple(v) for k, v in found.items()}
+
+
+def test_device_memory_has_one_owner():
+    assert _device_memory_sites() == DEVICE_MEMORY_SITES
 
 
 def test_no_debug_environment_hooks_and_no_oracle_in_the_product():
