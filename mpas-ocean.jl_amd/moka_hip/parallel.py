@@ -262,6 +262,19 @@ def unpack_numpy(lm: LocalMesh, K: int, buf, ssh, u, h):
         pos += e.size * K
 
 
+def check_level_mask(mesh, K, max_level_edge_top):
+    """None, or maxLevelEdge.Top of the whole mesh as an int32 array: (mesh.nEdges,) integers in [0, K], else ValueError."""
+    if max_level_edge_top is None:
+        return None
+    mlt = np.asarray(max_level_edge_top)
+    if mlt.shape != (mesh.nEdges,) or not np.issubdtype(mlt.dtype, np.integer):
+        raise ValueError(f"max_level_edge_top: expected {mesh.nEdges} integers (one per edge of the whole mesh), "
+                         f"found shape {mlt.shape}, dtype {mlt.dtype}")
+    if mlt.size and (mlt.min() < 0 or mlt.max() > K):
+        raise ValueError(f"max_level_edge_top: values must lie in [0, {K}], found [{mlt.min()}, {mlt.max()}]")
+    return mlt.astype(np.int32)
+
+
 # ---------------------------------------------------------------------------------------------
 # device model
 # ---------------------------------------------------------------------------------------------
@@ -281,9 +294,11 @@ class DistributedModel:
     def __init__(self, mesh, ssh, u, h, rest, dt, backend, rank, world, ordering=0, patch_cells=0,
                  transport="nccl", part=None, group=None, state_bytes=8, exchange_lists=None, timeout_s=30.0, nonlinear=False,
                  placement_tries=24,
-                 visc_del2=0.0):
+                 visc_del2=0.0, max_level_edge_top=None):
         """exchange_lists(wants: {rank: obj}) -> {rank: obj}: all-to-all of small Python objects between the ranks
-        (default: torch.distributed.all_gather_object on `group`); LocalCluster passes None and calls finish() itself."""
+        (default: torch.distributed.all_gather_object on `group`); LocalCluster passes None and calls finish() itself.
+        max_level_edge_top: None (every column full) or maxLevelEdge.Top of the whole mesh, (mesh.nEdges,) integers in [0, K] in the
+        global edge numbering; every rank takes the rows of its local edges."""
         import torch
         import torch.distributed as dist
         self.torch, self.dist = torch, dist
@@ -292,6 +307,7 @@ class DistributedModel:
         self.timeout_s = float(timeout_s)
         K = np.asarray(u).reshape(mesh.nEdges, -1).shape[1]
         self.K, self.state_bytes = K, int(state_bytes)
+        mlt = check_level_mask(mesh, K, max_level_edge_top)
         self.part = partition_cells(mesh, world) if part is None else np.asarray(part, dtype=np.int32)
         # the optional nonlinear terms: a two-ring halo (their stencil reaches one ring further) carrying the vertex-side fields;
         # the whole local mesh is computed every stage (step_rk4_whole), the halo's share redundantly
@@ -300,6 +316,8 @@ class DistributedModel:
         rest = np.asarray(rest).reshape(mesh.nCells, -1)
         h_mesh = api.HorzMesh(lm.mesh)
         v_mesh = api.VerticalMesh(h_mesh, nVertLevels=K, restingThickness=rest[lm.cells_g], multilayer=True)
+        if mlt is not None:
+            v_mesh.maxLevelEdge.Top[:] = mlt[lm.edges_g]
         self.mesh = api.Mesh.__new__(api.Mesh)
         self.mesh.HorzMesh, self.mesh.VertMesh, self.mesh.backend = h_mesh, v_mesh, backend
         self.mesh.state_bytes = int(state_bytes)
@@ -567,7 +585,7 @@ class DistributedModel:
             finally:
                 self.transport = mine
             self.backend.synchronize()
-            return bool(np.array_equal(got, self.received_bytes()))
+            return bool(np.array_equal(got, self.received_bytes(), equal_nan=True))    # NaN below the sea floor travels too
         L.check(lib.moka_halo_pack(self._halo, 0, self.sendbuf.data_ptr()), self.backend._h)
         self.recvbuf.zero_()
         self.torch.cuda.synchronize()
@@ -582,7 +600,8 @@ class DistributedModel:
         finally:
             self.transport = mine
         self.backend.synchronize(); self.torch.cuda.synchronize()
-        return bool(self.torch.equal(got, self.recvbuf))
+        bits = self.torch.int32 if self.state_bytes == 4 else self.torch.int64         # by bits: a delivered NaN equals itself
+        return bool(self.torch.equal(got.view(bits), self.recvbuf.view(bits)))
 
     def _direct(self):
         return self.transport in ("ipc", "ipc-acq", "ipc-smo") and self.connected
@@ -890,7 +909,7 @@ def choose_transport(model, candidates, fallbacks, control_group, log=lambda msg
         if not reference:
             reference.append(run_steps("gloo", check_steps))
         got = run_steps(cand, check_steps)
-        return all(np.array_equal(a, b) for a, b in zip(got, reference[0]))
+        return all(np.array_equal(a, b, equal_nan=True) for a, b in zip(got, reference[0]))
 
     def works(cand):
         def setup():
@@ -953,15 +972,17 @@ class LocalCluster:
     send and receive buffers, ordered by stream events only."""
 
     def __init__(self, mesh, ssh, u, h, rest, dt, world, device=0, ordering=0, patch_cells=0, state_bytes=8, direct=True,
-                 devices=None, overlap=-1, nonlinear=False, visc_del2=0.0, part=None, placement_tries=1):
+                 devices=None, overlap=-1, nonlinear=False, visc_del2=0.0, part=None, placement_tries=1, max_level_edge_top=None):
         import torch
         self.torch, self.world = torch, world
+        max_level_edge_top = check_level_mask(mesh, np.asarray(u).reshape(mesh.nEdges, -1).shape[1], max_level_edge_top)
         devs = list(devices) if devices is not None else [device] * world
         self.backends = [api.MokaHIP(devs[r]) for r in range(world)]
         part = partition_cells(mesh, world) if part is None else np.asarray(part, dtype=np.int32)
         self.models = [DistributedModel(mesh, ssh, u, h, rest, dt, self.backends[r], r, world, ordering=ordering,
                                         patch_cells=patch_cells, transport="local", part=part, state_bytes=state_bytes,
-                                        nonlinear=nonlinear, visc_del2=visc_del2, placement_tries=placement_tries)
+                                        nonlinear=nonlinear, visc_del2=visc_del2, placement_tries=placement_tries,
+                                        max_level_edge_top=max_level_edge_top)
                        for r in range(world)]
         for r, m in enumerate(self.models):        # every rank learns the order its neighbours want their rows in
             m.finish({q: self.models[q]._wants[r] for q in m.lm.neighbors})

@@ -21,7 +21,8 @@ their getters, the pass in RK4 steps and in moka_run's captured graph, Forward E
 pass, every call of moka_forced_tape); D, tracers with the vertical passes (D1, D2: moka_set_tracer_vertical_diffusion, the
 moka_tracer_vertical_field_* calls and moka_tracer_adjoint_want_vertical_gradient with its views, beside a changing tracer count
 and the momentum pass).  Not covered by any machine: a tracer count that changes under a live tracer tape, halos and partitions
-(several processes).
+(several processes) -- their call order stays with test_partition_gloo.py; level masks and poisoned levels on a partition have a
+file of their own, test_gpu_partition_masks.py (cases and CPU emulation: partition_cases.py, test_partition_masks.py).
 
 Replay a sequence on the CPU:   python tests/call_sequences.py A1 3 [--upto N]
 
