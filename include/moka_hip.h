@@ -777,10 +777,9 @@ int  moka_tracer_has_vertical_field(const moka_state *st, int32_t j, int *out);
  * moka_step_fe, moka_run(MOKA_FORWARD_EULER), moka_tape_create, moka_halo_create and the moka_rk4_dist_* calls return
  * MOKA_ERR_UNSUPPORTED.  The first call that turns the pass on allocates the column form's scratch of 2 * nVertLevels * nEdges doubles;
  * no step allocates anything.  moka_state_optimize_placement neither times nor moves the new arrays.
- * Out of scope: reverse mode through the pass by a moka_tape handle (the operator depends on h_new, so the flow adjoint gains thickness terms;
- * the moka_forced_tape handle, below, carries them), a nuV field
- * per interface and edge, quadratic drag, closures (Richardson number, KPP), Forward Euler, fp32 storage, partitioned meshes, YAML keys
- * and NetCDF I/O, a time-dependent stress other than by a new upload between steps. */
+ * Out of scope: reverse mode through the pass by a moka_tape handle (the operator depends on h_new, so the flow adjoint gains thickness
+ * terms; the moka_forced_tape handle, below, carries them), quadratic drag, closures (Richardson number, KPP), Forward Euler, fp32
+ * storage, partitioned meshes, YAML keys and NetCDF I/O, a time-dependent stress other than by a new upload between steps. */
 int  moka_set_vertical_viscosity(moka_state *st, double nuV, double bottomDrag);
 /* the two scalars as they stand; MOKA_ERR_ARG for a NULL out-pointer */
 int  moka_vertical_viscosity(const moka_state *st, double *nuV, double *bottomDrag);
@@ -795,6 +794,41 @@ int  moka_has_surface_stress(const moka_state *st, int *out);
  * gathered from the two cell columns; nVertLevels <= 105), 2 the column form (a lane per edge from global memory: deeper columns,
  * nVertLevels == 1 and kernel variant 3), 0 no pass yet */
 int  moka_state_momentum_vmix_path(const moka_state *st);
+/* A vertical viscosity per interface and edge (default: none; MPAS-Ocean's vertViscTopOfEdge).  The state may carry a field f >= 0
+ * (m^2/s) in place of the one nuV: (nEdges, nVertLevels) doubles in the caller's numbering, like a normalVelocity upload; row k of an
+ * edge column is the interface between levels k and k+1.  With n_e = min(maxLevelEdgeTop[e], nVertLevels), rows k >= n_e - 1, row
+ * nVertLevels - 1 included, are never read -- by the host scan or on the device -- and may hold anything, NaN included.  The recipe
+ * of moka_set_vertical_viscosity changes in one operand,
+ *   s[k] = dt * f[k,e]                            (one product, rounded once)
+ *   w[k] = s[k] / (0.5 * (h[k] + h[k+1]))         k = 0 .. n-2
+ * and stays as it is, letter for letter, in d, R, the stress and drag lines, Solve and u_new = x + Solve(R).  While a field is present
+ * nuV is not read (the scalar is kept and acts again once the field is removed).
+ * Hence: a field that equals nuV at every active interface gives the bits of the scalar, forwards and backwards (dt * nuV is the same
+ * product); an interface with f == 0 decouples the column there (w == 0, g == 0, no pivot is lost: beta >= h > 0); A stays symmetric
+ * and strictly diagonally dominant for f >= 0, h > 0; the momentum budget, the contraction and the range property hold as stated
+ * above.
+ * A field whose active entries are all zero (found by the host scan of the upload) counts as nuV == 0.  "The pass is on" now reads:
+ * nuV != 0 that is not set aside by a field, or a field with a nonzero active entry, or r != 0, or a stress present in the sense above.
+ * Which columns are computed does not change.  A state that never uploads a field launches, allocates and records exactly what it did
+ * before.
+ * Kernels: the FIELD instances of both forms.  The tile form stages the tile's span of f into the column set that y[k] overwrites
+ * once s[k] is read: the same LDS, the same tiles, the same boundary (nVertLevels 105 / 106) and the same path values, one more
+ * coalesced read of nVertLevels * nEdges doubles.  The column form reads f from the edge's own column.
+ * host: NULL removes the field; on a state without one the call does nothing.  MOKA_ERR_ARG, with nothing changed, for a negative, NaN
+ * or infinite value at an active row (k < n_e - 1; inactive rows are not inspected).  MOKA_ERR_UNSUPPORTED where
+ * moka_set_vertical_viscosity returns it for a nonzero value (fp32 storage, a halo, a partitioned mesh, an existing moka_tape) -- a
+ * removal included when it would let a nuV != 0 act again (an all-zero field had set it aside while such an object was created): the
+ * field then stays --, and everything that is refused while the pass is on is refused when a field turned it on.  The call synchronises
+ * the stream before it replaces an array a launch may still read, and takes effect with the next RK4 step or moka_run -- a moka_run
+ * after the call never replays launches captured before it.  A field costs nVertLevels * nEdges doubles of device memory; the upload
+ * that turns the pass on allocates the column form's scratch.
+ * Out of scope: closures that would compute the field (Richardson number, KPP), fp32 storage, partitioned meshes, YAML keys and NetCDF
+ * I/O, and everything listed above. */
+int  moka_vertical_viscosity_field_upload(moka_state *st, const double *host);
+/* the field into host, (nEdges, nVertLevels) doubles (zeros when there is none); MOKA_ERR_ARG for a NULL host */
+int  moka_vertical_viscosity_field_download(moka_state *st, double *host);
+/* *out = 1 when a field is present (all-zero ones included), else 0; MOKA_ERR_ARG for a NULL out */
+int  moka_has_vertical_viscosity_field(const moka_state *st, int *out);
 
 /* ---- reverse mode of passive tracer transport over a frozen flow (extension) ---------------------------------------
  * Once the flow is given the tracer step above is linear in phi, so d J(phi_N) / d phi_0 is the exact transpose of a linear map.  It
@@ -1031,8 +1065,8 @@ int  moka_adjoint_download(moka_tape *t, int field, double *host);
  * moka_forced_adjoint_want_gradient with recorded steps.  The state must outlive the tape.
  * Usage: forced_tape_create -> [want_gradient] -> n x step_rk4_forced_taped -> seed -> sweep -> download / density_download / gradient.
  * Out of scope: the nonlinear, Del2 and Del4 dycores (no moka_tape covers them either), Forward Euler, the piecewise, partitioned
- * taping calls, fp32 storage, a time-dependent stress and a per-step split of the densities, second derivatives, a nuV field per
- * interface and edge, quadratic drag, coupling to the tracer tape, the 13-stream form for taped steps, YAML keys and NetCDF I/O. */
+ * taping calls, fp32 storage, a time-dependent stress and a per-step split of the densities, second derivatives, quadratic drag,
+ * coupling to the tracer tape, the 13-stream form for taped steps, YAML keys and NetCDF I/O. */
 typedef struct moka_forced_tape moka_forced_tape;
 int  moka_forced_tape_create(moka_state *st, int64_t capacity_steps, moka_forced_tape **out);
 void moka_forced_tape_destroy(moka_forced_tape *t);
@@ -1053,6 +1087,34 @@ int  moka_forced_adjoint_density_download(moka_forced_tape *t, int what, double 
 int  moka_forced_adjoint_gradient(moka_forced_tape *t, int what, double *out);
 /* which kernel served the last transposed pass: 1 the tile form, 2 the column form, 0 none yet */
 int  moka_forced_tape_vmix_path(const moka_forced_tape *t);
+/* The viscosity field in reverse mode.  A step recorded while a field (moka_vertical_viscosity_field_upload) was in force is
+ * reversed with that field: w[k] = s[k] / hm[k], s[k] = dt * f[k,e], in both places where the transposed recipe forms w -- the
+ * elimination, and the ascending P / Rn lines; everything else is as written above.  G_tau, D_r and D_nu keep their formulas, with z
+ * from the field's solve; with a field in force D_nu and its host sum are the directional derivative along the all-ones field.
+ * The density DF (flagged by moka_forced_adjoint_want_viscosity_field_gradient, a call of its own: `what` of
+ * moka_forced_adjoint_want_gradient keeps its three bits) has the layout of the field.  Per reversed step with dt != 0.0, per edge
+ * with n >= 2 and per k = 0 .. n-2, each operation rounded once:
+ *   DF[k,e] = DF[k,e] - dt * (de[k] / hm[k])
+ * Rows k >= n_e - 1 of DF are never written: they keep the zeros of the seed.  DF[k,e] is d J / d f[k,e] for a field that acts in
+ * every recorded step; at a scalar nuV it is the sensitivity to a depth-dependent viscosity at the uniform value the run used, and
+ * sum_k DF[k,e] equals D_nu[e] up to the order of summation; without the pass it is the derivative at zero.  As for the other
+ * densities, columns the forward pass skipped are then solved for the densities alone and write neither XU nor hbar: X after a sweep
+ * with DF flagged has the bits of an unflagged one.  The flag may change only while no step is recorded (MOKA_ERR_ARG otherwise);
+ * the first flag allocates nVertLevels * nEdges doubles; a download without the flag is MOKA_ERR_ARG; every seed zeroes DF.
+ * Tape: moka_step_rk4_forced_taped keeps a device copy of the field a step ran with -- nVertLevels * nEdges doubles, taken device
+ * to device on the context's stream ahead of the step's first launch, and only when the field was uploaded or removed since the
+ * tape's newest copy.  The copies are released when a sweep has emptied the tape and when the tape is destroyed.  Unlike the stress,
+ * a field upload is therefore allowed while steps are recorded.  A tape whose steps never saw a field and never flags DF allocates,
+ * records and launches what it did before.
+ * Kernels: steps recorded with a field run the FIELD instances, which keep f in a fifth column set for the whole column
+ * (vmix_kernel(K, generic, 5): tiles of 64 columns for nVertLevels <= 15, of 32 for <= 63 -- 81,152 bytes at most -- the column form
+ * from 64); steps recorded without one keep the four-set instances and their boundary at 79 / 80, with DF flagged or not.
+ * moka_forced_tape_vmix_path reports the form that ran.  DF in the tile form: the lane leaves dt * (de[k] / hm[k]) in the slot of h[k],
+ * free by then, and the rows k < n - 1 of every solved column are taken off the tile's span of DF, coalesced; in the column form the
+ * lane updates its own rows k < n - 1.  No other row of DF is read or written.  Both forms and the numpy twin agree bit for bit.
+ * host: (nEdges, nVertLevels) doubles in the caller's numbering. */
+int  moka_forced_adjoint_want_viscosity_field_gradient(moka_forced_tape *t, int on);
+int  moka_forced_adjoint_viscosity_field_density_download(moka_forced_tape *t, double *host);
 
 #ifdef __cplusplus
 }

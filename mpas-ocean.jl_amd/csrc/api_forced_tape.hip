@@ -54,14 +54,24 @@ int moka_step_rk4_forced_taped(moka_forced_tape *ft, double dt)
     if ((int64_t)ft->steps.size() >= ft->capacity) return fail(st->ctx, MOKA_ERR_ARG, "forced tape is full");
     const bool on = mom_vmix_on(st);
     if (on && dt < 0.0) return fail(st->ctx, MOKA_ERR_ARG, "vertical momentum mixing: dt must be >= 0 (the implicit solve is not reversible in time)");
-    const bool rec = on || ft->want != 0;
+    const bool rec = on || ft->want != 0 || ft->wantF;
     HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
     const size_t nEK = (size_t)p.K * p.nE, nCK = (size_t)p.K * p.nC;
     if (rec && !ft->unRec)
         if (int rc = ft->mem.alloc_all({{&ft->unRec, nEK * (size_t)ft->capacity}, {&ft->hnRec, nCK * (size_t)ft->capacity}, {&ft->hbar, nEK}, {&ft->scratch, 2 * nEK}}))
             return rc;
-    if (int rc = moka_step_rk4_taped(ft->inner, dt)) return rc;
+    // the viscosity field the step is about to run with: a copy of its own when the tape's newest one is of another generation,
+    // allocated and taken ahead of the step's first launch (a step that fails afterwards leaves a copy the next step uses)
+    const double *fld = on ? mom_vmix_field(st) : nullptr;
     hipStream_t s = st->ctx->stream;
+    if (fld && (ft->vfCopies.empty() || ft->vfGen != st->momVfGen)) {
+        double *copy = nullptr;
+        if (int rc = ft->mem.alloc(&copy, nEK)) return rc;
+        ft->vfCopies.push_back(copy);
+        ft->vfGen = st->momVfGen;
+        HIPCHK(st->ctx, hipMemcpyAsync(copy, fld, nEK * sizeof(double), hipMemcpyDeviceToDevice, s));
+    }
+    if (int rc = moka_step_rk4_taped(ft->inner, dt)) return rc;
     if (on && dt != 0.0)         // the split step of moka_step_rk4, on the same two arrays (rk4_end has made them the current level)
         if (int rc = momentum_vmix(st, st->lev[1].u, st->lev[1].h, dt)) return rc;
     const size_t i = ft->steps.size();
@@ -69,7 +79,7 @@ int moka_step_rk4_forced_taped(moka_forced_tape *ft, double dt)
         HIPCHK(st->ctx, hipMemcpyAsync(ft->unRec + nEK * i, st->lev[1].u, nEK * sizeof(double), hipMemcpyDeviceToDevice, s));
         HIPCHK(st->ctx, hipMemcpyAsync(ft->hnRec + nCK * i, st->lev[1].h, nCK * sizeof(double), hipMemcpyDeviceToDevice, s));
     }
-    ft->steps.push_back({rec, on, st->momTau && st->momTauOn, st->momNuV, st->momDrag});
+    ft->steps.push_back({rec, on, st->momTau && st->momTauOn, mom_vmix_nu(st), st->momDrag, fld ? (int32_t)ft->vfCopies.size() - 1 : -1});
     ++st->forcedSteps;
     return MOKA_OK;
 }
@@ -78,6 +88,10 @@ static int forced_zero_densities(moka_forced_tape *ft)
 {
     for (double *d : ft->dens)
         if (d) HIPCHK(ft->st->ctx, hipMemsetAsync(d, 0, (size_t)ft->st->mesh->plan.nE * sizeof(double), ft->st->ctx->stream));
+    if (ft->wantF) {
+        const Plan &p = ft->st->mesh->plan;
+        HIPCHK(ft->st->ctx, hipMemsetAsync(ft->densF, 0, (size_t)p.K * p.nE * sizeof(double), ft->st->ctx->stream));
+    }
     return MOKA_OK;
 }
 
@@ -134,15 +148,22 @@ int moka_forced_adjoint_sweep(moka_forced_tape *ft)
             a.Gtau = (ft->want & MOKA_FORCED_GRAD_STRESS) ? ft->dens[0] : nullptr;
             a.Dnu = (ft->want & MOKA_FORCED_GRAD_VISCOSITY) ? ft->dens[1] : nullptr;
             a.Dr = (ft->want & MOKA_FORCED_GRAD_DRAG) ? ft->dens[2] : nullptr;
-            const bool launched = ft->want != 0 || (r.on && !(p.K < 2 && r.drag == 0.0 && !a.tau));
+            a.fld = r.vf >= 0 ? ft->vfCopies[(size_t)r.vf] : nullptr;
+            a.DF = ft->wantF ? ft->densF : nullptr;
+            const bool launched = ft->want != 0 || ft->wantF || (r.on && !(p.K < 2 && r.drag == 0.0 && !a.tau));
             HIPCHK(st->ctx, launch_momentum_vmix_adjoint(a, generic, st->ctx->stream));
             HIPCHK(st->ctx, launch_momentum_vmix_gather(a, st->ctx->stream));
-            if (launched) ft->path = momentum_vmix_adjoint_form(p.K, generic);
+            if (launched) ft->path = momentum_vmix_adjoint_form(p.K, generic, a.fld != nullptr);
         }
         for (int sg = 4; sg >= 1; --sg)
             if (int rc = rk4_reverse_stage(t, sg)) return rc;
         ft->steps.pop_back();
         --st->forcedSteps;
+    }
+    if (!ft->vfCopies.empty()) {        // the tape is empty: the field copies go once the last launch that reads one has finished
+        HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));
+        for (double *&c : ft->vfCopies) ft->mem.release(c);
+        ft->vfCopies.clear();
     }
     return MOKA_OK;
 }
@@ -191,6 +212,30 @@ int moka_forced_adjoint_density_download(moka_forced_tape *ft, int what, double 
     if (b < 0 || !(ft->want & what)) return fail(ft->st->ctx, MOKA_ERR_ARG, "forced tape: what must be one flagged MOKA_FORCED_GRAD_* bit");
     HIPCHK(ft->st->ctx, hipSetDevice(ft->st->ctx->device));
     return get_rows(ft->st->mesh, host, ft->dens[b], MOKA_EDGE, ft->st->mesh->plan.nE, 1);
+}
+
+int moka_forced_adjoint_want_viscosity_field_gradient(moka_forced_tape *ft, int on)
+{
+    if (!ft) return fail(nullptr, MOKA_ERR_ARG, "forced tape is NULL");
+    moka_state *st = ft->st;
+    if (!ft->steps.empty()) return fail(st->ctx, MOKA_ERR_ARG, "forced tape: gradients are flagged while no step is recorded");
+    if (on && !ft->densF) {
+        HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+        const Plan &p = st->mesh->plan;
+        if (int rc = ft->mem.alloc(&ft->densF, (size_t)p.K * p.nE)) return rc;
+        HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));
+    }
+    ft->wantF = on != 0;
+    return MOKA_OK;
+}
+
+int moka_forced_adjoint_viscosity_field_density_download(moka_forced_tape *ft, double *host)
+{
+    if (!ft || !host) return fail(ft ? ft->st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    if (!ft->wantF) return fail(ft->st->ctx, MOKA_ERR_ARG, "forced tape: the viscosity field gradient is not flagged");
+    const Plan &p = ft->st->mesh->plan;
+    HIPCHK(ft->st->ctx, hipSetDevice(ft->st->ctx->device));
+    return get_rows(ft->st->mesh, host, ft->densF, MOKA_EDGE, p.nE, p.K);
 }
 
 int moka_forced_adjoint_gradient(moka_forced_tape *ft, int what, double *out)

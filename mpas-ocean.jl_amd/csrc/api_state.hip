@@ -490,7 +490,8 @@ int momentum_vmix(moka_state *st, double *u, const double *h, double dt)
     MomVmixArgs a{};
     a.nE = p.nE; a.K = p.K; a.ehdr = st->mesh->dev.ehdr; a.u = u; a.h = h;
     a.tau = st->momTau && st->momTauOn ? st->momTau : nullptr;
-    a.dt = dt; a.nu = st->momNuV; a.drag = st->momDrag; a.scratch = st->momScratch;
+    a.dt = dt; a.nu = mom_vmix_nu(st); a.drag = st->momDrag; a.scratch = st->momScratch;
+    a.fld = mom_vmix_field(st);
     if (p.K < 2 && a.drag == 0.0 && !a.tau) return MOKA_OK;      // one level and the viscosity alone: no column has anything to do
     const bool generic = st->ctx->variant == 3;
     HIPCHK(st->ctx, launch_momentum_vmix(a, generic, st->ctx->stream));
@@ -1150,6 +1151,67 @@ int moka_has_surface_stress(const moka_state *st, int *out)
 {
     if (!st || !out) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
     *out = st->momTau ? 1 : 0;
+    return MOKA_OK;
+}
+
+int moka_vertical_viscosity_field_upload(moka_state *st, const double *host)
+{
+    if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
+    const Plan &p = st->mesh->plan;
+    bool on = false;                     // the host scan: the interfaces k < n_e - 1 of every edge column, and nothing else
+    for (int e = 0; host && e < p.nE; ++e) {
+        const double *col = host + (size_t)p.edgeN2O[e] * p.K;
+        const int n = std::min(p.ehdr[(size_t)e * 4 + 3], p.K);
+        for (int k = 0; k < n - 1; ++k) {
+            if (!(col[k] >= 0.0) || !std::isfinite(col[k]))
+                return fail(st->ctx, MOKA_ERR_ARG, "vertical viscosity field: every value at an active interface must be finite and >= 0");
+            on = on || col[k] != 0.0;
+        }
+    }
+    if (!host && !st->momVf) return MOKA_OK;      // nothing to remove: the call of a state that never had a field does nothing at all
+    // a removal lets the scalar act again: with nuV != 0 it asks for what moka_set_vertical_viscosity(nuV != 0) asks for (a field whose
+    // active entries are all zero had set that nuV aside, and a moka_tape or a halo may have been created meanwhile)
+    if (host || st->momNuV != 0.0)
+        if (int rc = mom_vmix_supported(st)) return rc;
+    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));      // no launch is reading the old array
+    if (!host) {
+        st->mem.release(st->momVf);
+        st->momVfOn = false;
+        ++st->momVfGen;
+        return MOKA_OK;
+    }
+    if (on)
+        if (int rc = mom_vmix_scratch(st)) return rc;
+    double *fresh = nullptr;             // the new field goes into an array of its own: a failure leaves the old one in force
+    if (int rc = st->mem.alloc(&fresh, (size_t)p.K * p.nE)) return rc;
+    if (int rc = put_rows(st->mesh, fresh, host, MOKA_EDGE, p.nE, p.K)) {
+        (void)hipStreamSynchronize(st->ctx->stream);
+        st->mem.release(fresh);
+        return rc;
+    }
+    st->mem.release(st->momVf);
+    st->momVf = fresh; st->momVfOn = on;
+    ++st->momVfGen;
+    return MOKA_OK;
+}
+
+int moka_vertical_viscosity_field_download(moka_state *st, double *host)
+{
+    if (!st || !host) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    const Plan &p = st->mesh->plan;
+    if (!st->momVf) {
+        std::fill(host, host + (size_t)p.K * p.nE, 0.0);
+        return MOKA_OK;
+    }
+    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    return get_rows(st->mesh, host, st->momVf, MOKA_EDGE, p.nE, p.K);
+}
+
+int moka_has_vertical_viscosity_field(const moka_state *st, int *out)
+{
+    if (!st || !out) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    *out = st->momVf ? 1 : 0;
     return MOKA_OK;
 }
 

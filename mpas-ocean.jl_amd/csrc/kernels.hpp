@@ -321,7 +321,8 @@ struct VmixArgs {
 };
 // The kernel that serves the pass (tracer_vmix.hip holds the LDS formula): form 1 = k_vmix_tile over tiles of `tc` columns with `lds`
 // bytes of dynamic LDS, form 2 = k_vmix_column.  generic: the caller asks for form 2 (kernel variant 3).  sets: the column sets a
-// resident column takes in LDS, 3 for the forward and the plain reverse pass, 4 for the gradient instances.
+// resident column takes in LDS, 3 for the forward and the plain reverse pass, 4 for the gradient instances (and the transposed momentum
+// pass), 5 for the transposed momentum pass of a step that ran with a viscosity field.
 struct VmixKernel {
     int form;
     size_t lds;
@@ -344,6 +345,8 @@ struct MomVmixArgs {
     const double *tau;            // (nE) surface stress over rho0 in device edge numbering; nullptr: none (the instances without it)
     double dt, nu, drag;          // drag == 0.0: the instances without it
     double *scratch;              // 2 * K * nE doubles: g and y of the column form (the tile form keeps them in LDS)
+    const double *fld;            // (K, nE) viscosity per interface and edge (moka_vertical_viscosity_field_upload): the FIELD instances,
+                                  // s[k] = dt * fld[k,e] and nu is not read; nullptr: the scalar instances
 };
 // the form vmix_kernel(K, generic, 3) gives the pass: 1 = k_mvmix_tile, 2 = k_mvmix_column
 int momentum_vmix_form(int K, bool generic);
@@ -366,8 +369,10 @@ struct MomVmixAdjArgs {
     double *hbar;                 // (K, nE) work array
     double *scratch;              // 2 * K * nE doubles: g and y of the column form
     double *Gtau, *Dnu, *Dr;
+    const double *fld;            // the field the step ran with (nullptr: the scalar nu): the FIELD instances, five column sets a tile
+    double *DF;                   // (K, nE) density of the field, rows k < n - 1 of a solved column (nullptr: not wanted)
 };
-int momentum_vmix_adjoint_form(int K, bool generic);            // vmix_kernel(K, generic, 4).form
+int momentum_vmix_adjoint_form(int K, bool generic, bool field);            // vmix_kernel(K, generic, field ? 5 : 4).form
 hipError_t launch_momentum_vmix_adjoint(const MomVmixAdjArgs &a, bool generic, hipStream_t s);
 hipError_t launch_momentum_vmix_gather(const MomVmixAdjArgs &a, hipStream_t s);
 

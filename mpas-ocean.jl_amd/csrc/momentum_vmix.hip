@@ -19,10 +19,12 @@ namespace moka {
 //     h(k), x(k)             the edge thickness and u*, read once each, in ascending k
 //     putG / g, putY / y     the sweep's two work columns
 //     emit(k, inc)           u[k] = u[k] + inc
+//     s(k)                   FIELD only: dt * f[k,e], read once, before putY(k) (the tile keeps f in the set y overwrites)
 // n == 1 (instances with DRAG or STRESS only): y[0] = R[0] / d[0] with d[0] = h[0] (+ q) and R[0] = 0.0 (+ b) (- q * x[0]).
-// Levels k >= n are never touched.
+// Levels k >= n are never touched.  FIELD (moka_vertical_viscosity_field_upload): s[k] = dt * f[k,e] per interface k <= n - 2 in place
+// of the one s; rows k >= n - 1 of f are never read.  An instance without it is the scalar one, operation for operation.
 // ------------------------------------------------------------------------------------------------
-template <bool DRAG, bool STRESS, class C>
+template <bool DRAG, bool STRESS, bool FIELD, class C>
 __device__ __forceinline__ void mvmix_column(C &c, const int n, const double s, const double q, const double b)
 {
     double hk = c.h(0), xk = c.x(0);
@@ -35,7 +37,7 @@ __device__ __forceinline__ void mvmix_column(C &c, const int n, const double s, 
         return;
     }
     double hn = c.h(1), xn = c.x(1), xm = 0.0;
-    double w = s / (0.5 * (hk + hn));               // w[0]
+    double w = (FIELD ? c.s(0) : s) / (0.5 * (hk + hn));      // w[0]
     double beta = hk + w;                           // d[0]
     double r = w * (xn - xk);
     if (STRESS) r = r + b;
@@ -49,7 +51,7 @@ __device__ __forceinline__ void mvmix_column(C &c, const int n, const double s, 
         double d;
         if (k < n - 1) {
             hn = c.h(k + 1); xn = c.x(k + 1);
-            w = s / (0.5 * (hk + hn));
+            w = (FIELD ? c.s(k) : s) / (0.5 * (hk + hn));
             d = (hk + wp) + w;
             r = wp * (xm - xk) + w * (xn - xk);
         } else {
@@ -82,7 +84,8 @@ __device__ __forceinline__ int mvmix_depth(const int mlt, const int K)
 // Form 1, tile.  A workgroup of one wave takes te consecutive edges (device numbering): their te * K doubles of u are one contiguous
 // span, staged as the tracer tile stages a field -- 16-byte lanes, MV_U loads in flight per lane -- into set 1 of three column sets in
 // LDS, a column cs = K | 1 doubles apart (odd: the lanes of a ds_read_b64 / ds_write_b64 group hit distinct banks):
-//     set 0: h_e, its slot k taking g[k] once h[k] and h[k+1] sit in registers | set 1: u | set 2: y
+//     set 0: h_e, its slot k taking g[k] once h[k] and h[k+1] sit in registers | set 1: u | set 2: y (FIELD: f, its slot k taking y[k]
+//     once s[k] is read -- one more coalesced read of the span, no LDS beyond the scalar tile's)
 // Set 0 does not exist as an array: for every element (column, k) of the tile with k < n a lane reads h_new[k,c1] and h_new[k,c2] and
 // stores 0.5 * (a + b).  The edges' ehdr records {c1, c2, -, maxLevelEdgeTop} come in with one 16-byte load per edge and stay in LDS
 // behind the sets (16 bytes per column, where the tracer tile keeps 4: the tile's LDS is vmix_kernel's plus 12 * te bytes, which no
@@ -97,6 +100,8 @@ constexpr int MV_U = 8;               // 16-byte loads a lane has in flight per 
 
 struct MvmixTileCol {
     double *hs, *xs, *ys;             // the lane's column in the sets
+    double dt;
+    __device__ __forceinline__ double s(int k) const { return dt * ys[k]; }        // FIELD: f[k] sits in the slot y[k] takes next
     __device__ __forceinline__ double h(int k) const { return hs[k]; }
     __device__ __forceinline__ double x(int k) const { return xs[k]; }
     __device__ __forceinline__ void putG(int k, double v) { hs[k] = v; }
@@ -207,7 +212,35 @@ __device__ __forceinline__ void mv_store_span(const double *const S, double *con
     }
 }
 
-template <bool DRAG, bool STRESS>
+// mv_sub_span: G[k,e] = G[k,e] - S[k,e] for the rows k < hd.w - 1 of a column (the interfaces of the solved rows); no other row of the
+// span is read or written
+__device__ __forceinline__ void mv_sub_span(const double *const S, double *const G, const int4 *const hd, const unsigned nEl, const int tid,
+                                            const unsigned magic, const unsigned K, const unsigned cs)
+{
+    const bool vec = (reinterpret_cast<uintptr_t>(G) & 15) == 0;
+    for (unsigned i0 = 2u * tid; i0 < nEl; i0 += 2u * MV_NT) {
+        const unsigned e = i0;
+        unsigned ca, cb = 0;
+        const unsigned qA = mv_slot(e, magic, K, cs, ca);
+        const bool okA = (int)(e - ca * K) < hd[ca].w - 1;
+        bool okB = false;
+        unsigned qB = 0;
+        if (e + 1 < nEl) {
+            qB = mv_slot(e + 1, magic, K, cs, cb);
+            okB = (int)(e + 1 - cb * K) < hd[cb].w - 1;
+        }
+        if (vec && okA && okB) {
+            double2 o = *reinterpret_cast<const double2 *>(G + e);
+            o.x = o.x - S[qA]; o.y = o.y - S[qB];
+            *reinterpret_cast<double2 *>(G + e) = o;
+        } else {
+            if (okA) G[e] = G[e] - S[qA];
+            if (okB) G[e + 1] = G[e + 1] - S[qB];
+        }
+    }
+}
+
+template <bool DRAG, bool STRESS, bool FIELD>
 __global__ __launch_bounds__(MV_NT) void k_mvmix_tile(const MomVmixArgs a, const int te, const int cs, const unsigned magic)
 {
     extern __shared__ __align__(16) unsigned char mv_smem[];
@@ -229,12 +262,13 @@ __global__ __launch_bounds__(MV_NT) void k_mvmix_tile(const MomVmixArgs a, const
     }
     double *const uG = a.u + sp.base;
     mv_stage_span(X, uG, sp.nEl, tid, magic, K, cs);            // u: the span as it lies
+    if (FIELD) mv_stage_span(Y, a.fld + sp.base, sp.nEl, tid, magic, K, cs);       // f into the set of y: rows k >= n - 1 lie there unread
     __syncthreads();                                            // the records are in place
     mv_gather_h(H, a.h, hd, sp.nEl, tid, magic, K, cs);         // h_e: gathered from the two cell columns of every edge, active levels only
     __syncthreads();
     if (n > 0) {
-        MvmixTileCol col{H + (size_t)tid * cs, X + (size_t)tid * cs, Y + (size_t)tid * cs};
-        mvmix_column<DRAG, STRESS>(col, n, a.dt * a.nu, a.dt * a.drag, b);
+        MvmixTileCol col{H + (size_t)tid * cs, X + (size_t)tid * cs, Y + (size_t)tid * cs, a.dt};
+        mvmix_column<DRAG, STRESS, FIELD>(col, n, a.dt * a.nu, a.dt * a.drag, b);
     }
     __syncthreads();
     mv_store_span<false>(X, uG, hd, sp.nEl, tid, magic, K, cs); // back: the rows k < n of a column only
@@ -249,6 +283,9 @@ struct MvmixGlobalCol {
     double *uc;                       // the edge's column of u
     double *gs, *ys;                  // scratch: element k at [k * nE]
     size_t nE;
+    const double *fc;                 // FIELD: the edge's column of f
+    double dt;
+    __device__ __forceinline__ double s(int k) const { return dt * fc[k]; }
     __device__ __forceinline__ double h(int k) const { return 0.5 * (h1[k] + h2[k]); }
     __device__ __forceinline__ double x(int k) const { return uc[k]; }
     __device__ __forceinline__ void putG(int k, double v) { gs[k * nE] = v; }
@@ -258,7 +295,7 @@ struct MvmixGlobalCol {
     __device__ __forceinline__ void emit(int k, double inc) { uc[k] = uc[k] + inc; }
 };
 
-template <bool DRAG, bool STRESS>
+template <bool DRAG, bool STRESS, bool FIELD>
 __global__ __launch_bounds__(BLOCK) void k_mvmix_column(const MomVmixArgs a)
 {
     const int e = blockIdx.x * BLOCK + threadIdx.x;
@@ -267,21 +304,22 @@ __global__ __launch_bounds__(BLOCK) void k_mvmix_column(const MomVmixArgs a)
     const int n = mvmix_depth<DRAG, STRESS>(r.w, a.K);
     if (n == 0) return;
     const size_t nEK = (size_t)a.nE * a.K;
-    MvmixGlobalCol col{a.h + (size_t)r.x * a.K, a.h + (size_t)r.y * a.K, a.u + (size_t)e * a.K, a.scratch + e, a.scratch + nEK + e, (size_t)a.nE};
-    mvmix_column<DRAG, STRESS>(col, n, a.dt * a.nu, a.dt * a.drag, STRESS ? a.dt * a.tau[e] : 0.0);
+    MvmixGlobalCol col{a.h + (size_t)r.x * a.K, a.h + (size_t)r.y * a.K, a.u + (size_t)e * a.K, a.scratch + e, a.scratch + nEK + e, (size_t)a.nE,
+                       FIELD ? a.fld + (size_t)e * a.K : nullptr, a.dt};
+    mvmix_column<DRAG, STRESS, FIELD>(col, n, a.dt * a.nu, a.dt * a.drag, STRESS ? a.dt * a.tau[e] : 0.0);
 }
 
-template <bool DRAG, bool STRESS>
+template <bool DRAG, bool STRESS, bool FIELD>
 static hipError_t launch_mvmix_with(const MomVmixArgs &a, const VmixKernel &k, hipStream_t s)
 {
     if (k.form == 1) {
         const size_t lds = k.lds + 12 * (size_t)k.tc;       // the records take 16 bytes a column where vmix_kernel counts 4
         if (lds > 64 * 1024)
-            if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_mvmix_tile<DRAG, STRESS>)}, 80 * 1024); e != hipSuccess) return e;
+            if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_mvmix_tile<DRAG, STRESS, FIELD>)}, 80 * 1024); e != hipSuccess) return e;
         const unsigned magic = mv_magic((unsigned)a.K);
-        hipLaunchKernelGGL((k_mvmix_tile<DRAG, STRESS>), dim3((a.nE + k.tc - 1) / k.tc), dim3(MV_NT), lds, s, a, k.tc, a.K | 1, magic);
+        hipLaunchKernelGGL((k_mvmix_tile<DRAG, STRESS, FIELD>), dim3((a.nE + k.tc - 1) / k.tc), dim3(MV_NT), lds, s, a, k.tc, a.K | 1, magic);
     } else {
-        hipLaunchKernelGGL((k_mvmix_column<DRAG, STRESS>), dim3((a.nE + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, a);
+        hipLaunchKernelGGL((k_mvmix_column<DRAG, STRESS, FIELD>), dim3((a.nE + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, a);
     }
     return hipGetLastError();
 }
@@ -295,8 +333,11 @@ hipError_t launch_momentum_vmix(const MomVmixArgs &a, bool generic, hipStream_t 
     if ((uint64_t)a.K * 64u >= (1ull << 32)) return hipErrorInvalidValue;
     const VmixKernel k = vmix_kernel(a.K, generic, 3);
     if (k.form == 2 && !a.scratch) return hipErrorInvalidValue;
-    return drag ? (stress ? launch_mvmix_with<true, true>(a, k, s) : launch_mvmix_with<true, false>(a, k, s))
-                : (stress ? launch_mvmix_with<false, true>(a, k, s) : launch_mvmix_with<false, false>(a, k, s));
+    if (a.fld)
+        return drag ? (stress ? launch_mvmix_with<true, true, true>(a, k, s) : launch_mvmix_with<true, false, true>(a, k, s))
+                    : (stress ? launch_mvmix_with<false, true, true>(a, k, s) : launch_mvmix_with<false, false, true>(a, k, s));
+    return drag ? (stress ? launch_mvmix_with<true, true, false>(a, k, s) : launch_mvmix_with<true, false, false>(a, k, s))
+                : (stress ? launch_mvmix_with<false, true, false>(a, k, s) : launch_mvmix_with<false, false, false>(a, k, s));
 }
 
 // ================================================================================================
@@ -309,10 +350,13 @@ hipError_t launch_momentum_vmix(const MomVmixArgs &a, bool generic, hipStream_t 
 //     h(k), xu(k), un(k)     edge thickness, the adjoint's right-hand side (read once, before putY(k)), the recorded u_new
 //     putG / g, putY / y     the sweep's two work columns; y[k] takes z[k]
 //     putHbar, putXU         the results (an accessor of a column the forward pass skipped drops them)
+//     s(k)                   FIELD only: dt * f[k,e] of the recorded step's field, read in both sweeps (the tile keeps f in a set of its own)
+//     putDF(k, v)            GRAD with wdf only: DF[k,e] = DF[k,e] - v, v = dt * (de[k] / hm[k]), k <= n - 2, called once h(k + 1) is read
+// FIELD: s[k] = dt * f[k,e] in both places where w is formed; everything else as written.
 // ================================================================================================
-template <bool DRAG, bool STRESS, bool GRAD, class C>
+template <bool DRAG, bool STRESS, bool GRAD, bool FIELD, class C>
 __device__ __forceinline__ void mvadj_column(C &c, const int n, const double s, const double q, const double b, const double dt,
-                                             double *const gt, double *const dn, double *const dr)
+                                             double *const gt, double *const dn, double *const dr, const bool wdf)
 {
     double hk = c.h(0);
     if (n == 1) {
@@ -330,7 +374,7 @@ __device__ __forceinline__ void mvadj_column(C &c, const int n, const double s, 
         return;
     }
     double hn = c.h(1);
-    double w = s / (0.5 * (hk + hn));               // w[0]
+    double w = (FIELD ? c.s(0) : s) / (0.5 * (hk + hn));      // w[0]
     double beta = hk + w;                           // d[0]
     double y = c.xu(0) / beta;
     c.putY(0, y);
@@ -342,7 +386,7 @@ __device__ __forceinline__ void mvadj_column(C &c, const int n, const double s, 
         double d;
         if (k < n - 1) {
             hn = c.h(k + 1);
-            w = s / (0.5 * (hk + hn));
+            w = (FIELD ? c.s(k) : s) / (0.5 * (hk + hn));
             d = (hk + wp) + w;
         } else {
             d = hk + wp;
@@ -362,10 +406,11 @@ __device__ __forceinline__ void mvadj_column(C &c, const int n, const double s, 
     hk = c.h(0); hn = c.h(1);
     double zk = z0, zn = c.y(1), uk = c.un(0), un = c.un(1), um = 0.0;
     double hm = 0.5 * (hk + hn);
-    w = s / hm;
+    w = (FIELD ? c.s(0) : s) / hm;
     double de = (zk - zn) * (uk - un);
     double P = (w / hm) * de, sum = 0.0;
     if (GRAD) sum = sum + de / hm;
+    if (GRAD && wdf) c.putDF(0, dt * (de / hm));
     double r = w * (un - uk);
     if (STRESS) r = r + b;
     c.putHbar(0, 0.5 * P - zk * (r / hk));
@@ -377,10 +422,11 @@ __device__ __forceinline__ void mvadj_column(C &c, const int n, const double s, 
         if (k < n - 1) {
             hn = c.h(k + 1); un = c.un(k + 1); zn = c.y(k + 1);
             hm = 0.5 * (hk + hn);
-            w = s / hm;
+            w = (FIELD ? c.s(k) : s) / hm;
             de = (zk - zn) * (uk - un);
             P = (w / hm) * de;
             if (GRAD) sum = sum + de / hm;
+            if (GRAD && wdf) c.putDF(k, dt * (de / hm));
             r = wp * (um - uk) + w * (un - uk);
             hb = 0.5 * (Pp + P) - zk * (r / hk);
         } else {
@@ -412,9 +458,18 @@ __device__ __forceinline__ int mvadj_depth(const int mlt, const int K, const int
 //     set 0: h_e | set 1: xu, its slot k taking y[k], then z[k], then h[k] * z[k] | set 2: g, its slot k taking hbar[k] | set 3: un
 // -- and the record {c1, c2, nw, n}.  xu and un are staged as spans, h_e gathered for the rows k < n, xu and hbar go back as spans,
 // rows k < nw only.  vmix_kernel(K, generic, 4) holds the choice of te: at most 32 * 79 * 8 * 4 + 16 * 32 = 81,408 bytes a tile.
+// FIELD: w is formed in two sweeps and every slot of the four sets is rewritten in between, so f of the recorded step is staged into
+// a fifth set and stays there: vmix_kernel(K, generic, 5), 64-column tiles to K = 15, 32-column tiles to K = 63 (81,152 bytes).
+// DF (a.DF != nullptr, with or without FIELD): the lane leaves dt * (de[k] / hm[k]) in slot k of set 0 -- free once the ascending sweep
+// holds h[k] and h[k+1] in registers -- and mv_sub_span takes the rows k < n - 1 of the set off the span of DF, coalesced, as xu and
+// hbar go back.  A lane that wrote its own column of DF would issue one 8-byte store per level, K doubles apart from its neighbour's.
 // ------------------------------------------------------------------------------------------------
 struct MvadjTileCol {
     double *hs, *xs, *gs, *us;
+    const double *fs;                 // FIELD: the fifth set
+    double dt;
+    __device__ __forceinline__ double s(int k) const { return dt * fs[k]; }
+    __device__ __forceinline__ void putDF(int k, double v) { hs[k] = v; }          // h[k] and h[k+1] sit in registers: mv_sub_span takes it from here
     __device__ __forceinline__ double h(int k) const { return hs[k]; }
     __device__ __forceinline__ double xu(int k) const { return xs[k]; }
     __device__ __forceinline__ double un(int k) const { return us[k]; }
@@ -426,13 +481,14 @@ struct MvadjTileCol {
     __device__ __forceinline__ void putXU(int k, double v) { xs[k] = v; }
 };
 
-template <bool DRAG, bool STRESS, bool GRAD>
+template <bool DRAG, bool STRESS, bool GRAD, bool FIELD>
 __global__ __launch_bounds__(MV_NT) void k_mvadj_tile(const MomVmixAdjArgs a, const int te, const int cs, const unsigned magic)
 {
     extern __shared__ __align__(16) unsigned char mv_smem[];
     const size_t set = (size_t)te * cs;
     double *const H = reinterpret_cast<double *>(mv_smem), *const X = H + set, *const Gs = X + set, *const U = Gs + set;
-    int4 *const hd = reinterpret_cast<int4 *>(U + set);                    // (4 te cs) doubles in, te even: 16-byte aligned
+    double *const Fs = FIELD ? U + set : nullptr;                          // FIELD only: the fifth set
+    int4 *const hd = reinterpret_cast<int4 *>(U + (FIELD ? 2 : 1) * set);  // (4 or 5 te cs) doubles in, te even: 16-byte aligned
     const int tid = threadIdx.x, K = a.K;
     const MvSpan sp = mv_span(blockIdx.x, te, a.nE, K);
     int n = 0;
@@ -451,19 +507,21 @@ __global__ __launch_bounds__(MV_NT) void k_mvadj_tile(const MomVmixAdjArgs a, co
     }
     mv_stage_span(X, a.xu + sp.base, sp.nEl, tid, magic, K, cs);
     mv_stage_span(U, a.un + sp.base, sp.nEl, tid, magic, K, cs);
+    if (FIELD) mv_stage_span(Fs, a.fld + sp.base, sp.nEl, tid, magic, K, cs);
     __syncthreads();
     mv_gather_h(H, a.hn, hd, sp.nEl, tid, magic, K, cs);
     __syncthreads();
     if (n > 0) {
         const size_t o = (size_t)tid * cs;
         const int e = sp.e0 + tid;
-        MvadjTileCol col{H + o, X + o, Gs + o, U + o};
-        mvadj_column<DRAG, STRESS, GRAD>(col, n, a.dt * a.nu, a.dt * a.drag, b, a.dt, GRAD && a.Gtau ? a.Gtau + e : nullptr,
-                                         GRAD && a.Dnu ? a.Dnu + e : nullptr, GRAD && a.Dr ? a.Dr + e : nullptr);
+        MvadjTileCol col{H + o, X + o, Gs + o, U + o, FIELD ? Fs + o : nullptr, a.dt};
+        mvadj_column<DRAG, STRESS, GRAD, FIELD>(col, n, a.dt * a.nu, a.dt * a.drag, b, a.dt, GRAD && a.Gtau ? a.Gtau + e : nullptr,
+                                                GRAD && a.Dnu ? a.Dnu + e : nullptr, GRAD && a.Dr ? a.Dr + e : nullptr, GRAD && a.DF);
     }
     __syncthreads();
     mv_store_span<true>(X, a.xu + sp.base, hd, sp.nEl, tid, magic, K, cs);
     mv_store_span<true>(Gs, a.hbar + sp.base, hd, sp.nEl, tid, magic, K, cs);
+    if (GRAD && a.DF) mv_sub_span(H, a.DF + sp.base, hd, sp.nEl, tid, magic, K, cs);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -474,6 +532,11 @@ struct MvadjGlobalCol {
     double *xc, *hb, *gs, *ys;
     size_t nE;
     bool wr;                          // the forward pass computed this column: its xu and hbar are written
+    const double *fc;                 // FIELD: the edge's column of f
+    double *df;                       // ... and of DF (nullptr: not wanted)
+    double dt;
+    __device__ __forceinline__ double s(int k) const { return dt * fc[k]; }
+    __device__ __forceinline__ void putDF(int k, double v) { df[k] = df[k] - v; }
     __device__ __forceinline__ double h(int k) const { return 0.5 * (h1[k] + h2[k]); }
     __device__ __forceinline__ double xu(int k) const { return xc[k]; }
     __device__ __forceinline__ double un(int k) const { return uc[k]; }
@@ -485,7 +548,7 @@ struct MvadjGlobalCol {
     __device__ __forceinline__ void putXU(int k, double v) { if (wr) xc[k] = v; }
 };
 
-template <bool DRAG, bool STRESS, bool GRAD>
+template <bool DRAG, bool STRESS, bool GRAD, bool FIELD>
 __global__ __launch_bounds__(BLOCK) void k_mvadj_column(const MomVmixAdjArgs a)
 {
     const int e = blockIdx.x * BLOCK + threadIdx.x;
@@ -496,9 +559,10 @@ __global__ __launch_bounds__(BLOCK) void k_mvadj_column(const MomVmixAdjArgs a)
     if (n == 0) return;
     const size_t nEK = (size_t)a.nE * a.K, o = (size_t)e * a.K;
     MvadjGlobalCol col{a.hn + (size_t)r.x * a.K, a.hn + (size_t)r.y * a.K, a.un + o, a.xu + o, a.hbar + o, a.scratch + e, a.scratch + nEK + e,
-                       (size_t)a.nE, nw > 0};
-    mvadj_column<DRAG, STRESS, GRAD>(col, n, a.dt * a.nu, a.dt * a.drag, STRESS ? a.dt * a.tau[e] : 0.0, a.dt, GRAD && a.Gtau ? a.Gtau + e : nullptr,
-                                     GRAD && a.Dnu ? a.Dnu + e : nullptr, GRAD && a.Dr ? a.Dr + e : nullptr);
+                       (size_t)a.nE, nw > 0, FIELD ? a.fld + o : nullptr, GRAD && a.DF ? a.DF + o : nullptr, a.dt};
+    mvadj_column<DRAG, STRESS, GRAD, FIELD>(col, n, a.dt * a.nu, a.dt * a.drag, STRESS ? a.dt * a.tau[e] : 0.0, a.dt,
+                                            GRAD && a.Gtau ? a.Gtau + e : nullptr, GRAD && a.Dnu ? a.Dnu + e : nullptr,
+                                            GRAD && a.Dr ? a.Dr + e : nullptr, GRAD && a.DF);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -527,40 +591,43 @@ __global__ __launch_bounds__(BLOCK) void k_mvadj_gather(const MomVmixAdjArgs a, 
     }
 }
 
-template <bool DRAG, bool STRESS, bool GRAD>
+template <bool DRAG, bool STRESS, bool GRAD, bool FIELD>
 static hipError_t launch_mvadj_with(const MomVmixAdjArgs &a, const VmixKernel &k, hipStream_t s)
 {
     if (k.form == 1) {
-        const size_t lds = mv_tile_lds(4, k.tc, a.K);        // k.lds + 12 * k.tc: the records take 16 bytes a column where vmix_kernel counts 4
+        const size_t lds = mv_tile_lds(FIELD ? 5 : 4, k.tc, a.K);        // k.lds + 12 * k.tc: the records take 16 bytes a column where vmix_kernel counts 4
         if (lds > 64 * 1024)
-            if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_mvadj_tile<DRAG, STRESS, GRAD>)}, 80 * 1024); e != hipSuccess) return e;
-        hipLaunchKernelGGL((k_mvadj_tile<DRAG, STRESS, GRAD>), dim3((a.nE + k.tc - 1) / k.tc), dim3(MV_NT), lds, s, a, k.tc, a.K | 1,
+            if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_mvadj_tile<DRAG, STRESS, GRAD, FIELD>)}, 80 * 1024); e != hipSuccess) return e;
+        hipLaunchKernelGGL((k_mvadj_tile<DRAG, STRESS, GRAD, FIELD>), dim3((a.nE + k.tc - 1) / k.tc), dim3(MV_NT), lds, s, a, k.tc, a.K | 1,
                            mv_magic((unsigned)a.K));
     } else {
-        hipLaunchKernelGGL((k_mvadj_column<DRAG, STRESS, GRAD>), dim3((a.nE + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, a);
+        hipLaunchKernelGGL((k_mvadj_column<DRAG, STRESS, GRAD, FIELD>), dim3((a.nE + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, a);
     }
     return hipGetLastError();
 }
 
-template <bool GRAD>
+template <bool GRAD, bool FIELD>
 static hipError_t launch_mvadj_grad(const MomVmixAdjArgs &a, const VmixKernel &k, hipStream_t s)
 {
     const bool drag = a.drag != 0.0, stress = a.tau != nullptr;
-    return drag ? (stress ? launch_mvadj_with<true, true, GRAD>(a, k, s) : launch_mvadj_with<true, false, GRAD>(a, k, s))
-                : (stress ? launch_mvadj_with<false, true, GRAD>(a, k, s) : launch_mvadj_with<false, false, GRAD>(a, k, s));
+    return drag ? (stress ? launch_mvadj_with<true, true, GRAD, FIELD>(a, k, s) : launch_mvadj_with<true, false, GRAD, FIELD>(a, k, s))
+                : (stress ? launch_mvadj_with<false, true, GRAD, FIELD>(a, k, s) : launch_mvadj_with<false, false, GRAD, FIELD>(a, k, s));
 }
 
-int momentum_vmix_adjoint_form(int K, bool generic) { return vmix_kernel(K, generic, 4).form; }
+// the one place that decides the kernel of a transposed pass: four column sets, five when the step ran with a field
+static VmixKernel mvadj_kernel(int K, bool generic, bool field) { return vmix_kernel(K, generic, field ? 5 : 4); }
+int momentum_vmix_adjoint_form(int K, bool generic, bool field) { return mvadj_kernel(K, generic, field).form; }
 
 hipError_t launch_momentum_vmix_adjoint(const MomVmixAdjArgs &a, bool generic, hipStream_t s)
 {
-    const bool drag = a.drag != 0.0, stress = a.tau != nullptr, grad = a.Gtau || a.Dnu || a.Dr;
+    const bool drag = a.drag != 0.0, stress = a.tau != nullptr, grad = a.Gtau || a.Dnu || a.Dr || a.DF;
     if (a.nE <= 0 || a.K < 1 || (!grad && (!a.on || (a.K < 2 && !drag && !stress)))) return hipSuccess;
     if ((uint64_t)a.K * 64u >= (1ull << 32)) return hipErrorInvalidValue;
     if (!a.xu || !a.un || !a.hn || !a.hbar) return hipErrorInvalidValue;
-    const VmixKernel k = vmix_kernel(a.K, generic, 4);
+    const VmixKernel k = mvadj_kernel(a.K, generic, a.fld != nullptr);
     if (k.form == 2 && !a.scratch) return hipErrorInvalidValue;
-    return grad ? launch_mvadj_grad<true>(a, k, s) : launch_mvadj_grad<false>(a, k, s);
+    if (a.fld) return grad ? launch_mvadj_grad<true, true>(a, k, s) : launch_mvadj_grad<false, true>(a, k, s);
+    return grad ? launch_mvadj_grad<true, false>(a, k, s) : launch_mvadj_grad<false, false>(a, k, s);
 }
 
 hipError_t launch_momentum_vmix_gather(const MomVmixAdjArgs &a, hipStream_t s)

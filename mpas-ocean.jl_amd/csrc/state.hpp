@@ -252,6 +252,12 @@ struct moka_state {
     double momNuV = 0.0, momDrag = 0.0;
     double *momTau = nullptr, *momScratch = nullptr;
     bool momTauOn = false;
+    // the viscosity field (moka_vertical_viscosity_field_upload): (K, nE) in device edge numbering, nullptr: none, and the pass takes
+    // momNuV; momVfOn: it has a nonzero value at an active interface (the host scan of the upload) -- one that has none counts as
+    // nuV == 0.  momVfGen takes a new value with every upload and removal: a forced tape compares it with that of its newest copy.
+    double *momVf = nullptr;
+    bool momVfOn = false;
+    uint64_t momVfGen = 0;
     int momVmixPath = 0;              // moka_state_momentum_vmix_path
     mk::DeviceAllocs mem;
     // objects that hold or have exported the addresses of this state's arrays (halos, tapes): while any exists the arrays stay
@@ -292,8 +298,15 @@ inline MeshDev launch_bounds(const moka_mesh *mm)
     dev.maxOwnE = std::max(mm->plan.maxOwnELaunch, 1); dev.maxOwnC = std::max(mm->plan.maxOwnCLaunch, 1);
     return dev;
 }
-// is the vertical momentum pass on: some coefficient nonzero, or a stress with a nonzero entry at an edge that has an active level
-inline bool mom_vmix_on(const moka_state *st) { return st->momNuV != 0.0 || st->momDrag != 0.0 || (st->momTau && st->momTauOn); }
+// is the vertical momentum pass on: some coefficient nonzero (a field sets nuV aside and counts when an active entry is nonzero), or a
+// stress with a nonzero entry at an edge that has an active level
+inline bool mom_vmix_on(const moka_state *st)
+{
+    return (st->momVf ? st->momVfOn : st->momNuV != 0.0) || st->momDrag != 0.0 || (st->momTau && st->momTauOn);
+}
+// what the pass takes for the viscosity: the field that is on, else the scalar -- 0.0 under a field whose active entries are all zero
+inline const double *mom_vmix_field(const moka_state *st) { return st->momVf && st->momVfOn ? st->momVf : nullptr; }
+inline double mom_vmix_nu(const moka_state *st) { return st->momVf ? 0.0 : st->momNuV; }
 // `form` of the nonlinear launchers: kernel variants 4 / 3 select the plainer forms of the nonlinear kernels too
 inline int nl_form(const moka_ctx *ctx) { return ctx->variant == 4 ? 1 : ctx->variant == 3 ? 3 : 0; }
 

@@ -85,7 +85,8 @@ struct moka_tape {
 
 struct ForcedStep {
     bool rec, on, stress;        // u_new / h_new were recorded; the pass ran; with the stress
-    double nu, drag;
+    double nu, drag;             // nu: what the pass took (0.0 under a field)
+    int32_t vf;                  // the copy in moka_forced_tape.vfCopies of the field the step ran with, -1: the scalar nu
 };
 
 struct moka_forced_tape {
@@ -95,6 +96,12 @@ struct moka_forced_tape {
     double *unRec = nullptr, *hnRec = nullptr;       // capacity x (K, nE) / (K, nC): the new level of every step that recorded it
     double *hbar = nullptr, *scratch = nullptr;      // (K, nE); 2 x (K, nE): the column form's g and y.  All four come with the first step that records.
     double *dens[3] = {nullptr, nullptr, nullptr};   // G_tau, D_nu, D_r (nE each), allocated by the flag
+    // the viscosity field: DF (K, nE), allocated by its flag; one (K, nE) copy per field the recorded steps ran with, taken when the
+    // state's generation differs from that of the newest copy, released when a sweep has emptied the tape and at destroy
+    double *densF = nullptr;
+    bool wantF = false;
+    std::vector<double *> vfCopies;
+    uint64_t vfGen = 0;
     int want = 0;                                    // MOKA_FORCED_GRAD_* bits
     std::vector<ForcedStep> steps;
     int path = 0;                                    // moka_forced_tape_vmix_path

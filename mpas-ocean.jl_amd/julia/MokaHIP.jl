@@ -580,6 +580,26 @@ function set_vertical_mixing!(Prog::MProg; viscosity::Real = 0.0, bottom_drag::R
     p = surface_stress === nothing ? Ptr{Float64}(C_NULL) : pointer(surface_stress)
     GC.@preserve surface_stress check(ccall((:moka_surface_stress_upload, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), s.handle, p), s.backend.ctx)
 end
+# A viscosity per interface and edge (moka_vertical_viscosity_field_upload): `field` (nVertLevels, nEdges), row k of an edge column the
+# interface between levels k and k + 1, rows at and below an edge's deepest interface never read; nothing removes it and the scalar
+# viscosity acts again.  Takes effect with the next RK4 step.
+function set_vertical_viscosity_field!(Prog::MProg, field::Union{Matrix{Float64}, Nothing})
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    p = field === nothing ? Ptr{Float64}(C_NULL) : pointer(field)
+    GC.@preserve field check(ccall((:moka_vertical_viscosity_field_upload, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), s.handle, p), s.backend.ctx)
+end
+# the viscosity field as it stands, (nVertLevels, nEdges), or nothing when there is none
+function vertical_viscosity_field(Prog::MProg)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    has = Ref{Cint}(0)
+    check(ccall((:moka_has_vertical_viscosity_field, lib), Cint, (Ptr{Cvoid}, Ref{Cint}), s.handle, has), s.backend.ctx)
+    has[] == 0 && return nothing
+    out = Matrix{Float64}(undef, size(Prog.normalVelocity[end])...)
+    check(ccall((:moka_vertical_viscosity_field_download, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), s.handle, out), s.backend.ctx)
+    out
+end
 # (viscosity, bottom_drag, surface_stress) as they stand; the stress is nothing when there is none
 function vertical_mixing(Prog::MProg)
     s = Prog.ssh[end].state
@@ -805,6 +825,14 @@ end
 # the per-edge density of one FORCED_GRAD_* bit into `out` (nEdges values; for the stress: d J / d tau_e itself)
 function forced_density!(out::Array{Float64}, t::ForcedTape, what::Integer)
     check(ccall((:moka_forced_adjoint_density_download, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), t.handle, what, out), t.state.backend.ctx)
+    out
+end
+# the density of a viscosity field, d J / d f[k,e]: flagged only while no step is recorded; `out` (nVertLevels, nEdges)
+function want_viscosity_field_gradient!(t::ForcedTape, on::Bool = true)
+    check(ccall((:moka_forced_adjoint_want_viscosity_field_gradient, lib), Cint, (Ptr{Cvoid}, Cint), t.handle, on ? 1 : 0), t.state.backend.ctx)
+end
+function forced_viscosity_field_density!(out::Array{Float64}, t::ForcedTape)
+    check(ccall((:moka_forced_adjoint_viscosity_field_density_download, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), t.handle, out), t.state.backend.ctx)
     out
 end
 # d J / d nuV (FORCED_GRAD_VISCOSITY) or d J / d r (FORCED_GRAD_DRAG): the host sum of the density

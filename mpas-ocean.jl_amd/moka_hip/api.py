@@ -31,7 +31,7 @@ __all__ = [
     "attachAlarm", "setCurrentTime", "ocn_setup_clock", "ocn_setup_mesh", "ocn_init", "write_netcdf",
     "ConfigRead", "ConfigGet", "GlobalConfig", "AdjointTape", "set_nonlinear", "REFERENCE_COMPAT", "prognostic_vars_best_placement",
     "set_tracers", "Tracers", "TracerAdjointTape", "ForcedAdjointTape",
-    "set_vertical_mixing", "vertical_mixing", "momentum_vmix_path",
+    "set_vertical_mixing", "vertical_mixing", "vertical_viscosity_field", "momentum_vmix_path",
 ]
 
 MokaError = L.MokaError
@@ -595,22 +595,43 @@ def set_nonlinear(Prog: "PrognosticVars", on: bool = True, visc_del2: float = 0.
                 Prog._state.mesh.backend._h)
 
 
-def set_vertical_mixing(Prog: "PrognosticVars", viscosity: float = 0.0, bottom_drag: float = 0.0, surface_stress=None):
+def set_vertical_mixing(Prog: "PrognosticVars", viscosity: float = 0.0, bottom_drag: float = 0.0, surface_stress=None, viscosity_field=None):
     """Implicit vertical mixing of momentum behind every RK4 step (moka_set_vertical_viscosity, moka_surface_stress_upload; an
     extension, default off; include/moka_hip.h states the recipe).  `viscosity`: nuV >= 0 in m^2/s; `bottom_drag`: a linear drag
     r >= 0 in m/s on the deepest active level of every edge; `surface_stress`: None, or one value tau / rho0 (m^2/s^2) per edge along
-    the edge normal, in the mesh's edge order.  All three are replaced by a call: zeros and None switch the pass off.  They take effect
-    with the next RK4 step or run_steps."""
+    the edge normal, in the mesh's edge order; `viscosity_field`: None, or an (nEdges, nVertLevels) array of nuV >= 0 per interface and
+    edge (moka_vertical_viscosity_field_upload: row k of an edge column is the interface between levels k and k + 1, rows at and below
+    the deepest interface are never read), which sets `viscosity` aside while it is there.  All four are replaced by a call: zeros and
+    None switch the pass off.  They take effect with the next RK4 step or run_steps."""
     st = Prog._state
     h = st.mesh.backend._h
-    L.check(L.lib().moka_set_vertical_viscosity(st._h, float(viscosity), float(bottom_drag)), h)
-    tau = None
+    tau = fld = None                     # both arrays are checked before the first call: a bad shape changes nothing
     if surface_stress is not None:
         tau = np.ascontiguousarray(surface_stress, dtype=np.float64).reshape(-1)
         nE = st.mesh.HorzMesh.data.nEdges
         if tau.size != nE:
             raise ValueError(f"surface_stress: {tau.size} values for {nE} edges")
+    if viscosity_field is not None:
+        fld = np.ascontiguousarray(viscosity_field, dtype=np.float64)
+        shape = tuple(Prog.normalVelocity[-1].shape)
+        if fld.shape != shape:
+            raise ValueError(f"viscosity_field: shape {fld.shape}, expected {shape}")
+    L.check(L.lib().moka_set_vertical_viscosity(st._h, float(viscosity), float(bottom_drag)), h)
     L.check(L.lib().moka_surface_stress_upload(st._h, None if tau is None else tau.ctypes.data), h)
+    L.check(L.lib().moka_vertical_viscosity_field_upload(st._h, None if fld is None else fld.ctypes.data), h)
+
+
+def vertical_viscosity_field(Prog: "PrognosticVars"):
+    """The viscosity field as it stands, (nEdges, nVertLevels), or None when there is none."""
+    st = Prog._state
+    h = st.mesh.backend._h
+    has = C.c_int(0)
+    L.check(L.lib().moka_has_vertical_viscosity_field(st._h, C.byref(has)), h)
+    if not has.value:
+        return None
+    fld = np.empty(tuple(Prog.normalVelocity[-1].shape), dtype=np.float64)
+    L.check(L.lib().moka_vertical_viscosity_field_download(st._h, L.f64(fld)), h)
+    return fld
 
 
 def vertical_mixing(Prog: "PrognosticVars"):
@@ -1054,6 +1075,7 @@ class ForcedAdjointTape:
         self._ushape = tuple(Prog.normalVelocity[-1].shape)
         self._hshape = tuple(Prog.layerThickness[-1].shape)
         self._want = 0
+        self._want_field = False
         self._h = C.c_void_p()
         L.check(L.lib().moka_forced_tape_create(self._state._h, int(capacity_steps), C.byref(self._h)), self._ctx)
         _own(self, L.lib().moka_forced_tape_destroy, self._h, self._state, self._state.mesh, self._state.mesh.backend)
@@ -1063,14 +1085,18 @@ class ForcedAdjointTape:
         """One RK4 step of the model (bit for bit moka_step_rk4), recorded."""
         L.check(L.lib().moka_step_rk4_forced_taped(self._h, float(np.asarray(timestep).reshape(-1)[0])), self._ctx)
 
-    def want_gradient(self, stress: bool = False, viscosity: bool = False, drag: bool = False):
-        """The set of parameter gradients the following sweeps accumulate; only while no step is recorded."""
+    def want_gradient(self, stress: bool = False, viscosity: bool = False, drag: bool = False, viscosity_field: bool = False):
+        """The set of parameter gradients the following sweeps accumulate; only while no step is recorded.  `viscosity_field`: the
+        density d J / d f[k,e] of a viscosity per interface and edge, "viscosityField"."""
         want = (L.FORCED_GRAD_STRESS if stress else 0) | (L.FORCED_GRAD_VISCOSITY if viscosity else 0) | (L.FORCED_GRAD_DRAG if drag else 0)
         if want:
             L.check(L.lib().moka_forced_adjoint_want_gradient(self._h, want, 1), self._ctx)
         if 7 & ~want:
             L.check(L.lib().moka_forced_adjoint_want_gradient(self._h, 7 & ~want, 0), self._ctx)
         self._want = want
+        if bool(viscosity_field) != self._want_field:
+            L.check(L.lib().moka_forced_adjoint_want_viscosity_field_gradient(self._h, 1 if viscosity_field else 0), self._ctx)
+            self._want_field = bool(viscosity_field)
 
     def seed(self, u, h):
         """X := (u, h), (nEdges, K) and (nCells, K) fields: the adjoint of the state after the last recorded step."""
@@ -1083,7 +1109,12 @@ class ForcedAdjointTape:
         L.check(L.lib().moka_forced_adjoint_sweep(self._h), self._ctx)
 
     def density(self, what: str) -> np.ndarray:
-        """The per-edge density of "surfaceStress" (d J / d tau_e itself), "viscosity" or "bottomDrag", caller's edge numbering."""
+        """The per-edge density of "surfaceStress" (d J / d tau_e itself), "viscosity" or "bottomDrag", caller's edge numbering;
+        "viscosityField": (nEdges, nVertLevels), d J / d f[k,e], rows at and below an edge's deepest interface zero."""
+        if what == "viscosityField":
+            out = np.empty(self._ushape, dtype=np.float64)
+            L.check(L.lib().moka_forced_adjoint_viscosity_field_density_download(self._h, L.f64(out)), self._ctx)
+            return out
         out = np.empty(self._ushape[0], dtype=np.float64)
         L.check(L.lib().moka_forced_adjoint_density_download(self._h, self._BITS[what], L.f64(out)), self._ctx)
         return out
@@ -1103,6 +1134,8 @@ class ForcedAdjointTape:
                 v = C.c_double()
                 L.check(lib.moka_forced_adjoint_gradient(self._h, self._BITS[name], C.byref(v)), self._ctx)
                 out[name] = float(v.value)
+        if self._want_field:
+            out["viscosityField"] = self.density("viscosityField")
         return out
 
     def gradient(self, seed=None) -> dict:

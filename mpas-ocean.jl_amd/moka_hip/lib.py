@@ -111,6 +111,7 @@ EXPORTS = [
     "moka_tracer_vertical_field_upload", "moka_tracer_vertical_field_download", "moka_tracer_has_vertical_field",
     "moka_set_vertical_viscosity", "moka_vertical_viscosity", "moka_surface_stress_upload", "moka_surface_stress_download",
     "moka_has_surface_stress", "moka_state_momentum_vmix_path",
+    "moka_vertical_viscosity_field_upload", "moka_vertical_viscosity_field_download", "moka_has_vertical_viscosity_field",
     "moka_tracer_adjoint_want_source_gradient", "moka_tracer_adjoint_source_download",
     "moka_tracer_adjoint_want_diffusivity_gradient", "moka_tracer_adjoint_diffusivity_gradient",
     "moka_tracer_adjoint_diffusivity_density_download",
@@ -121,6 +122,7 @@ EXPORTS = [
     "moka_forced_tape_create", "moka_forced_tape_destroy", "moka_step_rk4_forced_taped", "moka_forced_adjoint_seed_sum_sq_ssh",
     "moka_forced_adjoint_seed", "moka_forced_adjoint_sweep", "moka_forced_adjoint_download", "moka_forced_adjoint_want_gradient",
     "moka_forced_adjoint_density_download", "moka_forced_adjoint_gradient", "moka_forced_tape_vmix_path",
+    "moka_forced_adjoint_want_viscosity_field_gradient", "moka_forced_adjoint_viscosity_field_density_download",
 ]
 
 
@@ -289,6 +291,9 @@ def lib():
     L.moka_surface_stress_download.argtypes = [vp, vp]
     L.moka_has_surface_stress.argtypes = [vp, C.POINTER(C.c_int)]
     L.moka_state_momentum_vmix_path.argtypes = [vp]
+    L.moka_vertical_viscosity_field_upload.argtypes = [vp, vp]
+    L.moka_vertical_viscosity_field_download.argtypes = [vp, vp]
+    L.moka_has_vertical_viscosity_field.argtypes = [vp, C.POINTER(C.c_int)]
     L.moka_tracer_adjoint_want_source_gradient.argtypes = [vp, C.c_int32, C.c_int]
     L.moka_tracer_adjoint_source_download.argtypes = [vp, C.c_int32, vp]
     L.moka_tracer_adjoint_want_diffusivity_gradient.argtypes = [vp, C.c_int32, C.c_int, C.c_int]
@@ -309,6 +314,8 @@ def lib():
     L.moka_forced_adjoint_density_download.argtypes = [vp, C.c_int, vp]
     L.moka_forced_adjoint_gradient.argtypes = [vp, C.c_int, C.POINTER(C.c_double)]
     L.moka_forced_tape_vmix_path.argtypes = [vp]
+    L.moka_forced_adjoint_want_viscosity_field_gradient.argtypes = [vp, C.c_int]
+    L.moka_forced_adjoint_viscosity_field_density_download.argtypes = [vp, vp]
     L.moka_tape_create.argtypes = [vp, C.c_int64, C.POINTER(vp)]
     L.moka_tape_destroy.argtypes = [vp]
     L.moka_tape_destroy.restype = None

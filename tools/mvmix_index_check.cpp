@@ -1,5 +1,6 @@
 // Host check of the index bookkeeping of the vertical momentum pass's tile forms (csrc/mvmix_index.hpp: mv_span, mv_slot, mv_magic,
-// mv_tile_lds) at the set counts in use -- 3 (forward) and 4 (transposed pass).  Stand-alone; meant for the host sanitizers:
+// mv_tile_lds) at the set counts in use -- 3 (forward, with or without a viscosity field), 4 (transposed pass) and 5 (transposed pass
+// of a step that ran with a field: both tile widths, every K up to 64).  Stand-alone; meant for the host sanitizers:
 //     c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I mpas-ocean.jl_amd/csrc tools/mvmix_index_check.cpp -o /tmp/mvmix_index_check
 //     /tmp/mvmix_index_check
 // For every K and a few edge counts it walks every tile as the kernels do: each element of the span goes to its slot of each column
@@ -29,7 +30,9 @@ static int tile_columns(int K, int sets)
 int main()
 {
     long tiles = 0, elems = 0;
-    for (int sets : {3, 4})
+    if (tile_columns(15, 5) != 64 || tile_columns(16, 5) != 32 || tile_columns(63, 5) != 32 || tile_columns(64, 5) != 0 ||
+        mv_tile_lds(5, 32, 63) != 81152) { std::printf("the five-set boundaries moved\n"); return 1; }
+    for (int sets : {3, 4, 5})
         for (int K = 2; K <= 110; ++K) {
             const int te = tile_columns(K, sets);
             if (!te) continue;
