@@ -778,7 +778,7 @@ int  moka_tracer_has_vertical_field(const moka_state *st, int32_t j, int *out);
  * MOKA_ERR_UNSUPPORTED.  The first call that turns the pass on allocates the column form's scratch of 2 * nVertLevels * nEdges doubles;
  * no step allocates anything.  moka_state_optimize_placement neither times nor moves the new arrays.
  * Out of scope: reverse mode through the pass by a moka_tape handle (the operator depends on h_new, so the flow adjoint gains thickness
- * terms; the moka_forced_tape handle, below, carries them), quadratic drag, closures (Richardson number, KPP), Forward Euler, fp32
+ * terms; the moka_forced_tape handle, below, carries them), closures (Richardson number, KPP), Forward Euler, fp32
  * storage, partitioned meshes, YAML keys and NetCDF I/O, a time-dependent stress other than by a new upload between steps. */
 int  moka_set_vertical_viscosity(moka_state *st, double nuV, double bottomDrag);
 /* the two scalars as they stand; MOKA_ERR_ARG for a NULL out-pointer */
@@ -829,6 +829,55 @@ int  moka_vertical_viscosity_field_upload(moka_state *st, const double *host);
 int  moka_vertical_viscosity_field_download(moka_state *st, double *host);
 /* *out = 1 when a field is present (all-zero ones included), else 0; MOKA_ERR_ARG for a NULL out */
 int  moka_has_vertical_viscosity_field(const moka_state *st, int *out);
+/* Quadratic bottom drag (default: off; MPAS-Ocean's config_use_implicit_bottom_drag).  One more scalar per state, Cd >= 0
+ * (dimensionless): the drag coefficient of an edge becomes r + Cd * sp[e], sp[e] the speed sqrt(KE[c1] + KE[c2]) of u* at the edge's
+ * bottom level, KE the kinetic-energy stencil of the nonlinear dycore.  For an edge e the pass computes, with
+ * n = min(maxLevelEdgeTop[e], nVertLevels) >= 1, kb = n - 1, x = u* (the new level's normalVelocity as stage 4 left it),
+ * (c1, c2) = cellsOnEdge[e], kc[e'] = 0.25 * dcEdge[e'] * dvEdge[e'] (two products, left to right) and invArea[c] = 1 / areaCell[c]
+ * (MOKA_PA_INVAREA), every operation rounded once, nothing contracted:
+ *   for c in (c1, c2):
+ *       acc = 0.0
+ *       for slot i of edgesOnCell[:, c] in slot order, e' = edgesOnCell[i, c]:
+ *           if min(maxLevelEdgeTop[e'], nVertLevels) > kb:         (else the term is omitted and u[kb,e'] is NOT read)
+ *               acc = acc + (kc[e'] * x[kb,e']) * x[kb,e']
+ *       KE_c = acc * invArea[c]
+ *   sp[e] = sqrt(KE_c1 + KE_c2)                                     (correctly rounded)
+ *   rq    = r + Cd * sp[e]
+ *   q_e   = dt * rq
+ * and the recipe of moka_set_vertical_viscosity runs letter for letter with q_e where it has q:
+ *   d[n-1] = d[n-1] + q_e;      R[n-1] = R[n-1] - q_e * x[n-1]
+ * "Drag on" now reads r != 0 or Cd != 0: that decides the drag lines, the n == 1 columns and "the pass is on".
+ * Hence: Cd == 0 launches, allocates and records exactly what the state did before -- no speed launch, no new array; with Cd != 0
+ * and u* == 0 in the stencil sp == 0 and r + 0.0 gives the bits of the linear pass; q_e >= 0, so symmetry, diagonal dominance, the
+ * contraction and the range property hold as stated above; the column momentum obeys sum_k h u_new - sum_k h u* = dt tau -
+ * q_e u_new[n-1] to round-off; levels k >= n of any edge are still never read, the gather of the speed included.  On a uniform flow U
+ * over a flat bottom of depth h with nuV == 0, r == 0 and one level, sp == |U| and 1 / u_new = 1 / u* + dt Cd / h (for u* > 0): the
+ * steps sample the exact solution of du/dt = -Cd |u| u / h.
+ * Kernels: sp comes from a launch of its own in front of the pass (the pass overwrites u in place, tile by tile, and the stencil of an
+ * edge reaches into other tiles): one lane per edge, the sums in slot order in registers, no atomics; any nVertLevels, any maxEdges,
+ * every kernel variant.  sp[e] = 0.0 for edges with n == 0.  The pass runs its QD instances, which read sp[e] where the others take the
+ * one q; tiles, LDS, the 105 / 106 boundary and the path values are those of the linear drag.  Both launches are issued by the step on
+ * its stream and replayed by moka_run's graph; a moka_run after the call never replays launches captured before it.  The first call
+ * with Cd != 0 allocates nEdges doubles for sp (and the column form's scratch, and uploads kc where the mesh has not); no step
+ * allocates anything.
+ * MOKA_ERR_ARG, with nothing changed, for a negative, NaN or infinite Cd and NULL pointers.  MOKA_ERR_UNSUPPORTED for Cd != 0 where
+ * moka_set_vertical_viscosity returns it for a nonzero value (fp32 storage, a halo, a partitioned mesh, an existing moka_tape) and
+ * while a moka_forced_tape of the state exists; everything that is refused while the pass is on is refused when Cd turned it on, and
+ * moka_forced_tape_create and moka_step_rk4_forced_taped return MOKA_ERR_UNSUPPORTED while Cd != 0 (q_e depends on u* through a
+ * horizontal stencil: the transposed pass would no longer be column-local).  The tracer tape is unaffected.
+ * Out of scope: reverse mode of the flow through this drag, a Cd field per edge or cell, Forward Euler, fp32 storage, partitioned
+ * meshes, YAML keys and NetCDF I/O. */
+int  moka_set_quadratic_bottom_drag(moka_state *st, double cd);
+/* Cd as it stands; MOKA_ERR_ARG for a NULL out-pointer */
+int  moka_quadratic_bottom_drag(const moka_state *st, double *cd);
+/* the sp the last pass of this state used into host, nEdges doubles in the caller's edge numbering; zeros when that pass ran without
+ * Cd or none has run; MOKA_ERR_ARG for a NULL host */
+int  moka_bottom_speed_download(moka_state *st, double *host);
+/* sp of the recipe above from normalVelocity of time level 0 (previous) or 1 (current) into host (nEdges doubles, the caller's
+ * numbering), synchronously and without a step, by the kernel the step launches: a diagnostic of the bottom stress Cd * sp * u.  Any
+ * Float64 state on a whole mesh, whatever Cd is; MOKA_ERR_UNSUPPORTED for fp32 storage, a halo or a partitioned mesh; MOKA_ERR_ARG for
+ * another time level or a NULL host. */
+int  moka_bottom_speed(moka_state *st, int time_level, double *host);
 
 /* ---- reverse mode of passive tracer transport over a frozen flow (extension) ---------------------------------------
  * Once the flow is given the tracer step above is linear in phi, so d J(phi_N) / d phi_0 is the exact transpose of a linear map.  It
@@ -1065,8 +1114,9 @@ int  moka_adjoint_download(moka_tape *t, int field, double *host);
  * moka_forced_adjoint_want_gradient with recorded steps.  The state must outlive the tape.
  * Usage: forced_tape_create -> [want_gradient] -> n x step_rk4_forced_taped -> seed -> sweep -> download / density_download / gradient.
  * Out of scope: the nonlinear, Del2 and Del4 dycores (no moka_tape covers them either), Forward Euler, the piecewise, partitioned
- * taping calls, fp32 storage, a time-dependent stress and a per-step split of the densities, second derivatives, quadratic drag,
- * coupling to the tracer tape, the 13-stream form for taped steps, YAML keys and NetCDF I/O. */
+ * taping calls, fp32 storage, a time-dependent stress and a per-step split of the densities, second derivatives, the quadratic drag
+ * (moka_forced_tape_create and moka_step_rk4_forced_taped return MOKA_ERR_UNSUPPORTED while Cd != 0, and
+ * moka_set_quadratic_bottom_drag refuses a nonzero Cd while a forced tape exists), coupling to the tracer tape, the 13-stream form for taped steps, YAML keys and NetCDF I/O. */
 typedef struct moka_forced_tape moka_forced_tape;
 int  moka_forced_tape_create(moka_state *st, int64_t capacity_steps, moka_forced_tape **out);
 void moka_forced_tape_destroy(moka_forced_tape *t);

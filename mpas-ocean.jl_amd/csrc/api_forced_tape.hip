@@ -26,6 +26,8 @@ int moka_forced_tape_create(moka_state *st, int64_t capacity_steps, moka_forced_
     if (st->halos > 0) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "forced tape: not on a state with a halo");
     if (p.nPatchesLaunch != p.nPatches) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "forced tape: whole (unpartitioned) meshes only");
     if (st->dycoreTapes > 0) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "forced tape: a moka_tape of this state exists");
+    if (st->momCd != 0.0)
+        return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "forced tape: no reverse mode through the quadratic bottom drag (moka_set_quadratic_bottom_drag(st, 0) first)");
     moka_forced_tape *ft = new (std::nothrow) moka_forced_tape();
     if (!ft) return fail(st->ctx, MOKA_ERR_ALLOC, "out of host memory");
     if (int rc = tape_create(st, capacity_steps, &ft->inner, true)) { delete ft; return rc; }     // fp32, nonlinear, tracers, a forced tape
@@ -52,6 +54,8 @@ int moka_step_rk4_forced_taped(moka_forced_tape *ft, double dt)
     moka_state *st = ft->st;
     const Plan &p = st->mesh->plan;
     if ((int64_t)ft->steps.size() >= ft->capacity) return fail(st->ctx, MOKA_ERR_ARG, "forced tape is full");
+    if (st->momCd != 0.0)        // (the setter refuses a nonzero value beside a forced tape: kept for a state that gains another path to it)
+        return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "forced tape: no reverse mode through the quadratic bottom drag");
     const bool on = mom_vmix_on(st);
     if (on && dt < 0.0) return fail(st->ctx, MOKA_ERR_ARG, "vertical momentum mixing: dt must be >= 0 (the implicit solve is not reversible in time)");
     const bool rec = on || ft->want != 0 || ft->wantF;

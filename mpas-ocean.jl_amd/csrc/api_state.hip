@@ -480,8 +480,21 @@ void rk13_end(moka_state *st)
     st->lazyPu = st->lazyPh = nullptr; st->lazyOwner = nullptr;
 }
 
+// the bottom-speed launch over the whole mesh: u a (K, nE) field, sp nE doubles (keCoef is on the device: ensure_ke_coef)
+static MomSpeedArgs bottom_speed_args(const moka_state *st, const double *u, double *sp)
+{
+    const Plan &p = st->mesh->plan;
+    const MeshDev &d = st->mesh->dev;
+    MomSpeedArgs a{};
+    a.nE = p.nE; a.K = p.K; a.ME = p.ME;
+    a.ehdr = d.ehdr; a.eoc = d.eoc; a.mltc = d.mltc; a.keCoef = d.keCoef; a.invArea = d.invArea;
+    a.u = u; a.sp = sp;
+    return a;
+}
+
 // The vertical pass of the flow (implicit vertical mixing of momentum with a surface stress and a bottom drag, include/moka_hip.h): behind
-// stage 4 on the new level's normalVelocity and layerThickness, through the same two pointers in the 16- and the 13-stream form.  The
+// stage 4 on the new level's normalVelocity and layerThickness, through the same two pointers in the 16- and the 13-stream form; with
+// Cd != 0 the bottom-speed launch goes in front of it.  The
 // caller skips it while the pass is off and when dt == 0.0.  Launches only: nothing is allocated, synchronised or read back, so a
 // captured step replays it.
 int momentum_vmix(moka_state *st, double *u, const double *h, double dt)
@@ -492,8 +505,14 @@ int momentum_vmix(moka_state *st, double *u, const double *h, double dt)
     a.tau = st->momTau && st->momTauOn ? st->momTau : nullptr;
     a.dt = dt; a.nu = mom_vmix_nu(st); a.drag = st->momDrag; a.scratch = st->momScratch;
     a.fld = mom_vmix_field(st);
-    if (p.K < 2 && a.drag == 0.0 && !a.tau) return MOKA_OK;      // one level and the viscosity alone: no column has anything to do
+    const bool qd = st->momCd != 0.0;
+    if (p.K < 2 && a.drag == 0.0 && !qd && !a.tau) return MOKA_OK;      // one level and the viscosity alone: no column has anything to do
     const bool generic = st->ctx->variant == 3;
+    if (qd) {       // the quadratic drag: the bottom speed of u*, before the pass overwrites u
+        HIPCHK(st->ctx, launch_momentum_bottom_speed(bottom_speed_args(st, u, st->momSpeed), st->ctx->stream));
+        a.speed = st->momSpeed; a.cd = st->momCd;
+    }
+    st->momSpeedUsed = qd;
     HIPCHK(st->ctx, launch_momentum_vmix(a, generic, st->ctx->stream));
     st->momVmixPath = momentum_vmix_form(p.K, generic);
     return MOKA_OK;
@@ -1213,6 +1232,70 @@ int moka_has_vertical_viscosity_field(const moka_state *st, int *out)
     if (!st || !out) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
     *out = st->momVf ? 1 : 0;
     return MOKA_OK;
+}
+
+// ---- the quadratic bottom drag (include/moka_hip.h: the recipe; momentum_vmix.hip: k_mvmix_bottom_speed and the QD instances) ----
+// keCoef on the device: meshes with the nonlinear arrays upload it when they are created, the others when a state first asks
+static int ensure_ke_coef(moka_mesh *m)
+{
+    if (m->dev.keCoef) return MOKA_OK;
+    return m->mem.upload(m->plan.keCoef, &m->dev.keCoef);
+}
+
+int moka_set_quadratic_bottom_drag(moka_state *st, double cd)
+{
+    if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
+    if (!(cd >= 0.0) || !std::isfinite(cd))
+        return fail(st->ctx, MOKA_ERR_ARG, "vertical momentum mixing: the quadratic drag coefficient must be finite and >= 0");
+    if (cd != 0.0) {
+        if (int rc = mom_vmix_supported(st)) return rc;
+        if (st->forcedTapes > 0)
+            return fail(st->ctx, MOKA_ERR_UNSUPPORTED,
+                        "vertical momentum mixing: no quadratic drag while a moka_forced_tape of this state exists (reverse mode does not cover it)");
+        HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+        if (int rc = mom_vmix_scratch(st)) return rc;
+        if (int rc = ensure_ke_coef(st->mesh)) return rc;
+        if (!st->momSpeed) {
+            if (int rc = st->mem.alloc(&st->momSpeed, (size_t)st->mesh->plan.nE)) return rc;
+            HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));
+        }
+    }
+    st->momCd = cd;      // (a kernel argument of the next step's launches: moka_run captures its graph anew in every call)
+    return MOKA_OK;
+}
+
+int moka_quadratic_bottom_drag(const moka_state *st, double *cd)
+{
+    if (!st || !cd) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    *cd = st->momCd;
+    return MOKA_OK;
+}
+
+int moka_bottom_speed_download(moka_state *st, double *host)
+{
+    if (!st || !host) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    const Plan &p = st->mesh->plan;
+    if (!st->momSpeed || !st->momSpeedUsed) {
+        std::fill(host, host + (size_t)p.nE, 0.0);
+        return MOKA_OK;
+    }
+    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    return get_rows(st->mesh, host, st->momSpeed, MOKA_EDGE, p.nE, 1);
+}
+
+int moka_bottom_speed(moka_state *st, int time_level, double *host)
+{
+    if (!st || !host) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    const Plan &p = st->mesh->plan;
+    if (time_level != 0 && time_level != 1) return fail(st->ctx, MOKA_ERR_ARG, "time_level must be 0 (previous) or 1 (current)");
+    if (st->f32) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "bottom speed: Float64 states only");
+    if (st->halos > 0 || p.nPatchesLaunch != p.nPatches) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "bottom speed: whole (unpartitioned) meshes only");
+    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    if (int rc = ensure_ke_coef(st->mesh)) return rc;
+    if (int rc = ensure_op_bufs(st->mesh)) return rc;
+    double *sp = st->mesh->opBuf[0];         // operator scratch; get_rows stages through opBuf[2]
+    HIPCHK(st->ctx, launch_momentum_bottom_speed(bottom_speed_args(st, st->lev[time_level].u, sp), st->ctx->stream));
+    return get_rows(st->mesh, host, sp, MOKA_EDGE, p.nE, 1);
 }
 
 int moka_state_momentum_vmix_path(const moka_state *st) { return st ? st->momVmixPath : 0; }

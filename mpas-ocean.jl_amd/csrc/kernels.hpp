@@ -347,10 +347,30 @@ struct MomVmixArgs {
     double *scratch;              // 2 * K * nE doubles: g and y of the column form (the tile form keeps them in LDS)
     const double *fld;            // (K, nE) viscosity per interface and edge (moka_vertical_viscosity_field_upload): the FIELD instances,
                                   // s[k] = dt * fld[k,e] and nu is not read; nullptr: the scalar instances
+    const double *speed;          // (nE) bottom speed sp[e] of u* (launch_momentum_bottom_speed) and the quadratic drag coefficient: with
+    double cd;                    // speed != nullptr && cd != 0.0 the QD instances, q = dt * (drag + cd * speed[e]) per lane and the drag
+                                  // lines are on whatever drag is; else the instances with the one q = dt * drag
 };
 // the form vmix_kernel(K, generic, 3) gives the pass: 1 = k_mvmix_tile, 2 = k_mvmix_column
 int momentum_vmix_form(int K, bool generic);
 hipError_t launch_momentum_vmix(const MomVmixArgs &a, bool generic, hipStream_t s);
+
+// ---- the bottom speed of the quadratic drag (moka_set_quadratic_bottom_drag, moka_bottom_speed; momentum_vmix.hip) ----
+// One lane per edge, a launch of its own in front of the pass (which overwrites u tile by tile while an edge's stencil reaches into
+// other tiles).  Per edge with n = min(maxLevelEdgeTop[e], K) >= 1 and kb = n - 1 (the recipe of include/moka_hip.h):
+//   KE_c = (the sum, from 0.0, over the slots i of edgesOnCell[c] in slot order whose edge e' has min(maxLevelEdgeTop[e'], K) > kb, of
+//          (keCoef[e'] * u[kb,e']) * u[kb,e']) * invArea[c];     sp[e] = sqrt(KE_c1 + KE_c2)
+// sp[e] = 0.0 for n == 0.  u[kb,e'] of a slot that fails the depth test is not read.
+struct MomSpeedArgs {
+    int nE, K, ME;
+    const int32_t *ehdr;          // (4, nE) c1, c2, -, maxLevelEdgeTop
+    const int32_t *eoc, *mltc;    // (ME, nC) edges of a cell, -1 = none; maxLevelEdgeTop of that edge, 0 = none
+    const double *keCoef;         // (nE) 0.25 * dcEdge * dvEdge
+    const double *invArea;        // (nC)
+    const double *u;              // (K, nE)
+    double *sp;                   // (nE)
+};
+hipError_t launch_momentum_bottom_speed(const MomSpeedArgs &a, hipStream_t s);
 
 // ---- the transposed pass (moka_forced_tape; momentum_vmix.hip) ----
 // At the head of a reversed step, per edge column the forward pass computed with these switches (the recipe of include/moka_hip.h):

@@ -85,7 +85,7 @@ struct Plan {
     std::vector<int32_t> cov;      // nV*VD  cellsOnVertex
     std::vector<double>  kite;     // nV*VD  kiteAreasOnVertex
     std::vector<double>  invAreaTri, fVertex;   // nV
-    std::vector<double>  keCoef, invDc;         // nE  0.25*dcEdge*dvEdge ; 1/dcEdge
+    std::vector<double>  keCoef, invDc;         // nE  0.25*dcEdge*dvEdge (always formed: the quadratic bottom drag reads it too) ; 1/dcEdge
     std::vector<double>  keoc;     // nC*ME  keCoef of the cell's edge in slot i (0 for padding): no dependent load in the kernels
     std::vector<int32_t> rowVoe;   // 2 per entry of rowEdge: verticesOnEdge of that row's edge (patch row lists only)
     // k_stage_nl5: pvList[pvStart[q] .. pvStart[q+1]) = the distinct vertices of patch q's own edges and of their edgesOnEdge;

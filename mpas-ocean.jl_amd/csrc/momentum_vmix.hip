@@ -1,6 +1,7 @@
-// momentum_vmix.hip -- implicit vertical mixing of momentum with a surface stress and a linear bottom drag (gfx950;
-// moka_set_vertical_viscosity / moka_surface_stress_upload, NOT in the reference): one tridiagonal solve per edge column behind stage 4
-// of an RK4 step, on the new normalVelocity over the new layerThickness.  Second half of the file: the transpose of that pass for
+// momentum_vmix.hip -- implicit vertical mixing of momentum with a surface stress and a linear and a quadratic bottom drag (gfx950;
+// moka_set_vertical_viscosity / moka_surface_stress_upload / moka_set_quadratic_bottom_drag, NOT in the reference): one tridiagonal
+// solve per edge column behind stage 4 of an RK4 step, on the new normalVelocity over the new layerThickness, the bottom speed of the
+// quadratic drag gathered by a launch in front of it.  Second half of the file: the transpose of that pass for
 // moka_forced_tape (reverse mode through the forced step), in the same two forms, and the cell gather of its thickness terms.
 #include "kernels_common.hpp"
 #include "mvmix_index.hpp"
@@ -240,7 +241,77 @@ __device__ __forceinline__ void mv_sub_span(const double *const S, double *const
     }
 }
 
-template <bool DRAG, bool STRESS, bool FIELD>
+// ------------------------------------------------------------------------------------------------
+// The bottom speed of the quadratic drag (moka_set_quadratic_bottom_drag; the recipe of include/moka_hip.h): a launch of its own in
+// front of the pass, which overwrites u tile by tile while the stencil of an edge reaches into other tiles.  One lane per edge in
+// device numbering: the edges of a patch are numbered together, so the lanes of a wave share their cells' eoc / mltc rows and most of
+// the u[kb,e'] they gather -- about one new line of u per edge, element-granular 8-byte requests served from L2.  A lane loads its two
+// cells' eoc and mltc rows (mltc[c,i] = maxLevelEdgeTop of the edge in slot i, 0 for an empty slot: the depth test without a dependent
+// read of that edge's ehdr), then keCoef[e'] and u[kb,e'] of the slots that pass the test, all in flight together; the two sums run
+// afterwards in slot order, in registers: no atomics, no shuffles, one summation order.  u[kb,e'] of a slot that fails the test is
+// not read.  Any K, any maxEdges <= MS_ME, every kernel variant.
+// ------------------------------------------------------------------------------------------------
+constexpr int MS_ME = 8;              // the slots of a cell the gfx950 kernels support (moka_mesh_create refuses more)
+
+__global__ __launch_bounds__(BLOCK) void k_mvmix_bottom_speed(const MomSpeedArgs a)
+{
+    const int e = blockIdx.x * BLOCK + threadIdx.x;
+    if (e >= a.nE) return;
+    const int4 r = *reinterpret_cast<const int4 *>(a.ehdr + (size_t)e * 4);
+    const int n = min(r.w, a.K);
+    if (n < 1) {
+        a.sp[e] = 0.0;
+        return;
+    }
+    const int kb = n - 1;
+    int ee[2][MS_ME];
+    bool ok[2][MS_ME];
+    double kc[2][MS_ME], x[2][MS_ME];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const size_t row = (size_t)(j ? r.y : r.x) * a.ME;
+#pragma unroll
+        for (int i = 0; i < MS_ME; ++i) {
+            ee[j][i] = i < a.ME ? a.eoc[row + i] : -1;
+            ok[j][i] = i < a.ME && ee[j][i] >= 0 && min(a.mltc[row + i], a.K) > kb;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < MS_ME; ++i) {
+            kc[j][i] = ok[j][i] ? a.keCoef[ee[j][i]] : 0.0;
+            x[j][i] = ok[j][i] ? a.u[(size_t)ee[j][i] * a.K + kb] : 0.0;
+        }
+    double ke[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 0; i < MS_ME; ++i)
+            if (ok[j][i]) acc = acc + (kc[j][i] * x[j][i]) * x[j][i];
+        ke[j] = acc * a.invArea[j ? r.y : r.x];
+    }
+    a.sp[e] = sqrt(ke[0] + ke[1]);       // (llvm.sqrt.f64: correctly rounded on gfx950 -- v_rsq_f64, two Goldschmidt steps, two fma corrections)
+}
+
+hipError_t launch_momentum_bottom_speed(const MomSpeedArgs &a, hipStream_t s)
+{
+    if (a.nE <= 0 || a.K < 1) return hipSuccess;
+    if (a.ME > MS_ME || !a.ehdr || !a.eoc || !a.mltc || !a.keCoef || !a.invArea || !a.u || !a.sp) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_mvmix_bottom_speed, dim3((a.nE + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+// QD (the quadratic drag): q = dt * (drag + cd * speed[e]) per lane where the other instances take the one q = dt * drag; DRAG is on
+// with it, and mvmix_column is what it is.
+template <bool QD>
+__device__ __forceinline__ double mvmix_q(const MomVmixArgs &a, const int e)
+{
+    return QD ? a.dt * (a.drag + a.cd * a.speed[e]) : a.dt * a.drag;
+}
+
+template <bool DRAG, bool STRESS, bool FIELD, bool QD>
 __global__ __launch_bounds__(MV_NT) void k_mvmix_tile(const MomVmixArgs a, const int te, const int cs, const unsigned magic)
 {
     extern __shared__ __align__(16) unsigned char mv_smem[];
@@ -249,13 +320,14 @@ __global__ __launch_bounds__(MV_NT) void k_mvmix_tile(const MomVmixArgs a, const
     const int tid = threadIdx.x, K = a.K;
     const MvSpan sp = mv_span(blockIdx.x, te, a.nE, K);
     int n = 0;
-    double b = 0.0;
+    double b = 0.0, q = mvmix_q<false>(a, 0);
     if (tid < te) {
         int4 r = make_int4(0, 0, 0, 0);
         if (tid < sp.ncol) {
             r = *reinterpret_cast<const int4 *>(a.ehdr + (size_t)(sp.e0 + tid) * 4);
             n = mvmix_depth<DRAG, STRESS>(r.w, K);
             if (STRESS && n > 0) b = a.dt * a.tau[sp.e0 + tid];
+            if (QD && n > 0) q = mvmix_q<true>(a, sp.e0 + tid);
         }
         r.w = n;
         hd[tid] = r;
@@ -268,7 +340,7 @@ __global__ __launch_bounds__(MV_NT) void k_mvmix_tile(const MomVmixArgs a, const
     __syncthreads();
     if (n > 0) {
         MvmixTileCol col{H + (size_t)tid * cs, X + (size_t)tid * cs, Y + (size_t)tid * cs, a.dt};
-        mvmix_column<DRAG, STRESS, FIELD>(col, n, a.dt * a.nu, a.dt * a.drag, b);
+        mvmix_column<DRAG, STRESS, FIELD>(col, n, a.dt * a.nu, q, b);
     }
     __syncthreads();
     mv_store_span<false>(X, uG, hd, sp.nEl, tid, magic, K, cs); // back: the rows k < n of a column only
@@ -295,7 +367,7 @@ struct MvmixGlobalCol {
     __device__ __forceinline__ void emit(int k, double inc) { uc[k] = uc[k] + inc; }
 };
 
-template <bool DRAG, bool STRESS, bool FIELD>
+template <bool DRAG, bool STRESS, bool FIELD, bool QD>
 __global__ __launch_bounds__(BLOCK) void k_mvmix_column(const MomVmixArgs a)
 {
     const int e = blockIdx.x * BLOCK + threadIdx.x;
@@ -306,38 +378,42 @@ __global__ __launch_bounds__(BLOCK) void k_mvmix_column(const MomVmixArgs a)
     const size_t nEK = (size_t)a.nE * a.K;
     MvmixGlobalCol col{a.h + (size_t)r.x * a.K, a.h + (size_t)r.y * a.K, a.u + (size_t)e * a.K, a.scratch + e, a.scratch + nEK + e, (size_t)a.nE,
                        FIELD ? a.fld + (size_t)e * a.K : nullptr, a.dt};
-    mvmix_column<DRAG, STRESS, FIELD>(col, n, a.dt * a.nu, a.dt * a.drag, STRESS ? a.dt * a.tau[e] : 0.0);
+    mvmix_column<DRAG, STRESS, FIELD>(col, n, a.dt * a.nu, mvmix_q<QD>(a, e), STRESS ? a.dt * a.tau[e] : 0.0);
 }
 
-template <bool DRAG, bool STRESS, bool FIELD>
+template <bool DRAG, bool STRESS, bool FIELD, bool QD>
 static hipError_t launch_mvmix_with(const MomVmixArgs &a, const VmixKernel &k, hipStream_t s)
 {
     if (k.form == 1) {
         const size_t lds = k.lds + 12 * (size_t)k.tc;       // the records take 16 bytes a column where vmix_kernel counts 4
         if (lds > 64 * 1024)
-            if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_mvmix_tile<DRAG, STRESS, FIELD>)}, 80 * 1024); e != hipSuccess) return e;
+            if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_mvmix_tile<DRAG, STRESS, FIELD, QD>)}, 80 * 1024); e != hipSuccess) return e;
         const unsigned magic = mv_magic((unsigned)a.K);
-        hipLaunchKernelGGL((k_mvmix_tile<DRAG, STRESS, FIELD>), dim3((a.nE + k.tc - 1) / k.tc), dim3(MV_NT), lds, s, a, k.tc, a.K | 1, magic);
+        hipLaunchKernelGGL((k_mvmix_tile<DRAG, STRESS, FIELD, QD>), dim3((a.nE + k.tc - 1) / k.tc), dim3(MV_NT), lds, s, a, k.tc, a.K | 1, magic);
     } else {
-        hipLaunchKernelGGL((k_mvmix_column<DRAG, STRESS, FIELD>), dim3((a.nE + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, a);
+        hipLaunchKernelGGL((k_mvmix_column<DRAG, STRESS, FIELD, QD>), dim3((a.nE + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, a);
     }
     return hipGetLastError();
 }
 
 int momentum_vmix_form(int K, bool generic) { return vmix_kernel(K, generic, 3).form; }
 
+template <bool STRESS, bool FIELD>
+static hipError_t launch_mvmix_drag(const MomVmixArgs &a, const VmixKernel &k, hipStream_t s)
+{
+    if (a.speed && a.cd != 0.0) return launch_mvmix_with<true, STRESS, FIELD, true>(a, k, s);
+    return a.drag != 0.0 ? launch_mvmix_with<true, STRESS, FIELD, false>(a, k, s) : launch_mvmix_with<false, STRESS, FIELD, false>(a, k, s);
+}
+
 hipError_t launch_momentum_vmix(const MomVmixArgs &a, bool generic, hipStream_t s)
 {
-    const bool drag = a.drag != 0.0, stress = a.tau != nullptr;
+    const bool drag = a.drag != 0.0 || (a.speed && a.cd != 0.0), stress = a.tau != nullptr;
     if (a.nE <= 0 || a.K < 1 || (a.K < 2 && !drag && !stress)) return hipSuccess;
     if ((uint64_t)a.K * 64u >= (1ull << 32)) return hipErrorInvalidValue;
     const VmixKernel k = vmix_kernel(a.K, generic, 3);
     if (k.form == 2 && !a.scratch) return hipErrorInvalidValue;
-    if (a.fld)
-        return drag ? (stress ? launch_mvmix_with<true, true, true>(a, k, s) : launch_mvmix_with<true, false, true>(a, k, s))
-                    : (stress ? launch_mvmix_with<false, true, true>(a, k, s) : launch_mvmix_with<false, false, true>(a, k, s));
-    return drag ? (stress ? launch_mvmix_with<true, true, false>(a, k, s) : launch_mvmix_with<true, false, false>(a, k, s))
-                : (stress ? launch_mvmix_with<false, true, false>(a, k, s) : launch_mvmix_with<false, false, false>(a, k, s));
+    if (a.fld) return stress ? launch_mvmix_drag<true, true>(a, k, s) : launch_mvmix_drag<false, true>(a, k, s);
+    return stress ? launch_mvmix_drag<true, false>(a, k, s) : launch_mvmix_drag<false, false>(a, k, s);
 }
 
 // ================================================================================================

@@ -485,6 +485,13 @@ int build_plan(const moka_mesh_desc *d, Plan &p)
                 p.kite[IX(j, vn, VD)] = d->kiteAreasOnVertex[IX(j, vo, VD)];
             }
         }
+    } else {
+        // keCoef alone, for the bottom speed of the quadratic drag (uploaded when a state first asks for it)
+        p.keCoef.resize(nE);
+        for (int en = 0; en < nE; ++en) {
+            const int eo = p.edgeN2O[en];
+            p.keCoef[en] = 0.25 * d->dcEdge[eo] * d->dvEdge[eo];
+        }
     }
 
     // ---- packed byte-offset records of the column kernel ----

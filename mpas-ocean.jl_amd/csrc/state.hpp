@@ -259,6 +259,12 @@ struct moka_state {
     bool momVfOn = false;
     uint64_t momVfGen = 0;
     int momVmixPath = 0;              // moka_state_momentum_vmix_path
+    // the quadratic bottom drag (moka_set_quadratic_bottom_drag): the coefficient; the bottom speed sp[e] in device edge numbering,
+    // allocated by the first call that sets Cd != 0 and kept (nullptr: never set); momSpeedUsed: the last pass ran with it
+    // (moka_bottom_speed_download hands out zeros otherwise)
+    double momCd = 0.0;
+    double *momSpeed = nullptr;
+    bool momSpeedUsed = false;
     mk::DeviceAllocs mem;
     // objects that hold or have exported the addresses of this state's arrays (halos, tapes): while any exists the arrays stay
     // where they are (moka_state_optimize_placement refuses)
@@ -298,11 +304,11 @@ inline MeshDev launch_bounds(const moka_mesh *mm)
     dev.maxOwnE = std::max(mm->plan.maxOwnELaunch, 1); dev.maxOwnC = std::max(mm->plan.maxOwnCLaunch, 1);
     return dev;
 }
-// is the vertical momentum pass on: some coefficient nonzero (a field sets nuV aside and counts when an active entry is nonzero), or a
+// is the vertical momentum pass on: some coefficient nonzero, Cd included (a field sets nuV aside and counts when an active entry is nonzero), or a
 // stress with a nonzero entry at an edge that has an active level
 inline bool mom_vmix_on(const moka_state *st)
 {
-    return (st->momVf ? st->momVfOn : st->momNuV != 0.0) || st->momDrag != 0.0 || (st->momTau && st->momTauOn);
+    return (st->momVf ? st->momVfOn : st->momNuV != 0.0) || st->momDrag != 0.0 || st->momCd != 0.0 || (st->momTau && st->momTauOn);
 }
 // what the pass takes for the viscosity: the field that is on, else the scalar -- 0.0 under a field whose active entries are all zero
 inline const double *mom_vmix_field(const moka_state *st) { return st->momVf && st->momVfOn ? st->momVf : nullptr; }

@@ -612,6 +612,36 @@ function vertical_mixing(Prog::MProg)
     check(ccall((:moka_surface_stress_download, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), s.handle, tau), s.backend.ctx)
     (nu[], r[], tau)
 end
+# The quadratic bottom drag (moka_set_quadratic_bottom_drag): `cd` >= 0, dimensionless; the drag coefficient of an edge becomes
+# r + cd * the speed of the flow at its bottom level.  0 switches it off.  Takes effect with the next RK4 step.
+function set_quadratic_drag!(Prog::MProg, cd::Real)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    check(ccall((:moka_set_quadratic_bottom_drag, lib), Cint, (Ptr{Cvoid}, Float64), s.handle, cd), s.backend.ctx)
+end
+function quadratic_drag(Prog::MProg)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    cd = Ref{Float64}(0.0)
+    check(ccall((:moka_quadratic_bottom_drag, lib), Cint, (Ptr{Cvoid}, Ref{Float64}), s.handle, cd), s.backend.ctx)
+    cd[]
+end
+# the bottom speed of the quadratic drag's recipe from normalVelocity of a time level (1 current, 0 previous), nEdges values, without a step
+function bottom_speed(Prog::MProg; time_level::Integer = 1)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    sp = Vector{Float64}(undef, size(Prog.normalVelocity[end], 2))
+    check(ccall((:moka_bottom_speed, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), s.handle, time_level, sp), s.backend.ctx)
+    sp
+end
+# the bottom speed the last vertical pass used (zeros when it ran without a quadratic drag)
+function last_bottom_speed(Prog::MProg)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    sp = Vector{Float64}(undef, size(Prog.normalVelocity[end], 2))
+    check(ccall((:moka_bottom_speed_download, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), s.handle, sp), s.backend.ctx)
+    sp
+end
 # 1 the tile form, 2 the column form of the momentum pass served the last step, 0 none yet
 function momentum_vmix_path(Prog::MProg)
     s = Prog.ssh[end].state

@@ -32,6 +32,7 @@ __all__ = [
     "ConfigRead", "ConfigGet", "GlobalConfig", "AdjointTape", "set_nonlinear", "REFERENCE_COMPAT", "prognostic_vars_best_placement",
     "set_tracers", "Tracers", "TracerAdjointTape", "ForcedAdjointTape",
     "set_vertical_mixing", "vertical_mixing", "vertical_viscosity_field", "momentum_vmix_path",
+    "quadratic_drag", "bottom_speed", "last_bottom_speed",
 ]
 
 MokaError = L.MokaError
@@ -595,14 +596,16 @@ def set_nonlinear(Prog: "PrognosticVars", on: bool = True, visc_del2: float = 0.
                 Prog._state.mesh.backend._h)
 
 
-def set_vertical_mixing(Prog: "PrognosticVars", viscosity: float = 0.0, bottom_drag: float = 0.0, surface_stress=None, viscosity_field=None):
+def set_vertical_mixing(Prog: "PrognosticVars", viscosity: float = 0.0, bottom_drag: float = 0.0, surface_stress=None, viscosity_field=None,
+                        quadratic_drag: float = 0.0):
     """Implicit vertical mixing of momentum behind every RK4 step (moka_set_vertical_viscosity, moka_surface_stress_upload; an
     extension, default off; include/moka_hip.h states the recipe).  `viscosity`: nuV >= 0 in m^2/s; `bottom_drag`: a linear drag
     r >= 0 in m/s on the deepest active level of every edge; `surface_stress`: None, or one value tau / rho0 (m^2/s^2) per edge along
     the edge normal, in the mesh's edge order; `viscosity_field`: None, or an (nEdges, nVertLevels) array of nuV >= 0 per interface and
     edge (moka_vertical_viscosity_field_upload: row k of an edge column is the interface between levels k and k + 1, rows at and below
-    the deepest interface are never read), which sets `viscosity` aside while it is there.  All four are replaced by a call: zeros and
-    None switch the pass off.  They take effect with the next RK4 step or run_steps."""
+    the deepest interface are never read), which sets `viscosity` aside while it is there; `quadratic_drag`: Cd >= 0, dimensionless
+    (moka_set_quadratic_bottom_drag: the drag coefficient of an edge becomes r + Cd * the speed of the flow at its bottom level).  All
+    five are replaced by a call: zeros and None switch the pass off.  They take effect with the next RK4 step or run_steps."""
     st = Prog._state
     h = st.mesh.backend._h
     tau = fld = None                     # both arrays are checked before the first call: a bad shape changes nothing
@@ -617,6 +620,7 @@ def set_vertical_mixing(Prog: "PrognosticVars", viscosity: float = 0.0, bottom_d
         if fld.shape != shape:
             raise ValueError(f"viscosity_field: shape {fld.shape}, expected {shape}")
     L.check(L.lib().moka_set_vertical_viscosity(st._h, float(viscosity), float(bottom_drag)), h)
+    L.check(L.lib().moka_set_quadratic_bottom_drag(st._h, float(quadratic_drag)), h)
     L.check(L.lib().moka_surface_stress_upload(st._h, None if tau is None else tau.ctypes.data), h)
     L.check(L.lib().moka_vertical_viscosity_field_upload(st._h, None if fld is None else fld.ctypes.data), h)
 
@@ -646,6 +650,31 @@ def vertical_mixing(Prog: "PrognosticVars"):
     tau = np.empty(st.mesh.HorzMesh.data.nEdges, dtype=np.float64)
     L.check(L.lib().moka_surface_stress_download(st._h, L.f64(tau)), h)
     return nu.value, r.value, tau
+
+
+def quadratic_drag(Prog: "PrognosticVars") -> float:
+    """Cd of the quadratic bottom drag as it stands (moka_quadratic_bottom_drag)."""
+    cd = C.c_double(0.0)
+    L.check(L.lib().moka_quadratic_bottom_drag(Prog._state._h, C.byref(cd)), Prog._state.mesh.backend._h)
+    return cd.value
+
+
+def bottom_speed(Prog: "PrognosticVars", time_level: int = 1):
+    """The bottom speed sp[e] of the quadratic drag's recipe from normalVelocity of `time_level` (1 current, 0 previous), nEdges
+    values, computed on the device without a step (moka_bottom_speed)."""
+    st = Prog._state
+    sp = np.empty(st.mesh.HorzMesh.data.nEdges, dtype=np.float64)
+    L.check(L.lib().moka_bottom_speed(st._h, int(time_level), L.f64(sp)), st.mesh.backend._h)
+    return sp
+
+
+def last_bottom_speed(Prog: "PrognosticVars"):
+    """The bottom speed the last vertical pass used, nEdges values; zeros when it ran without a quadratic drag
+    (moka_bottom_speed_download)."""
+    st = Prog._state
+    sp = np.empty(st.mesh.HorzMesh.data.nEdges, dtype=np.float64)
+    L.check(L.lib().moka_bottom_speed_download(st._h, L.f64(sp)), st.mesh.backend._h)
+    return sp
 
 
 def momentum_vmix_path(Prog: "PrognosticVars") -> int:

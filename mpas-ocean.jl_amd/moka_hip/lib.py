@@ -112,6 +112,7 @@ EXPORTS = [
     "moka_set_vertical_viscosity", "moka_vertical_viscosity", "moka_surface_stress_upload", "moka_surface_stress_download",
     "moka_has_surface_stress", "moka_state_momentum_vmix_path",
     "moka_vertical_viscosity_field_upload", "moka_vertical_viscosity_field_download", "moka_has_vertical_viscosity_field",
+    "moka_set_quadratic_bottom_drag", "moka_quadratic_bottom_drag", "moka_bottom_speed_download", "moka_bottom_speed",
     "moka_tracer_adjoint_want_source_gradient", "moka_tracer_adjoint_source_download",
     "moka_tracer_adjoint_want_diffusivity_gradient", "moka_tracer_adjoint_diffusivity_gradient",
     "moka_tracer_adjoint_diffusivity_density_download",
@@ -294,6 +295,10 @@ def lib():
     L.moka_vertical_viscosity_field_upload.argtypes = [vp, vp]
     L.moka_vertical_viscosity_field_download.argtypes = [vp, vp]
     L.moka_has_vertical_viscosity_field.argtypes = [vp, C.POINTER(C.c_int)]
+    L.moka_set_quadratic_bottom_drag.argtypes = [vp, C.c_double]
+    L.moka_quadratic_bottom_drag.argtypes = [vp, C.POINTER(C.c_double)]
+    L.moka_bottom_speed_download.argtypes = [vp, vp]
+    L.moka_bottom_speed.argtypes = [vp, C.c_int, vp]
     L.moka_tracer_adjoint_want_source_gradient.argtypes = [vp, C.c_int32, C.c_int]
     L.moka_tracer_adjoint_source_download.argtypes = [vp, C.c_int32, vp]
     L.moka_tracer_adjoint_want_diffusivity_gradient.argtypes = [vp, C.c_int32, C.c_int, C.c_int]

@@ -352,6 +352,37 @@ def diagnostic_compute(Mesh: RefMesh, Diag, Prog, backend: Backend):
     s.version += 1
 
 
+# ---- extension (not in the reference): the quadratic bottom drag of RungeKutta4 steps, include/moka_hip.h -------------
+def set_quadratic_drag(Prog, Mesh: RefMesh, cd: float, backend: Backend):
+    """moka_set_quadratic_bottom_drag: Cd >= 0, dimensionless; behind every RungeKutta4 step the deepest active level of every edge is
+    damped implicitly with the coefficient Cd * (the speed of the flow there).  0 switches it off."""
+    s = state_of(Prog, None, None, Mesh, backend)
+    L.check(L.lib().moka_set_quadratic_bottom_drag(s.handle, float(cd)), backend._h)
+
+
+def quadratic_drag(Prog, Mesh: RefMesh, backend: Backend) -> float:
+    s = state_of(Prog, None, None, Mesh, backend)
+    cd = C.c_double(0.0)
+    L.check(L.lib().moka_quadratic_bottom_drag(s.handle, C.byref(cd)), backend._h)
+    return cd.value
+
+
+def bottom_speed(Prog, Mesh: RefMesh, backend: Backend, time_level: int = 1) -> np.ndarray:
+    """moka_bottom_speed: the bottom speed of normalVelocity of a time level (1 current, 0 previous), nEdges values, without a step."""
+    s = state_of(Prog, None, None, Mesh, backend)
+    sp = np.empty(Mesh.data.nEdges, dtype=np.float64)
+    L.check(L.lib().moka_bottom_speed(s.handle, int(time_level), L.f64(sp)), backend._h)
+    return sp
+
+
+def last_bottom_speed(Prog, Mesh: RefMesh, backend: Backend) -> np.ndarray:
+    """moka_bottom_speed_download: the bottom speed the last vertical pass used (zeros when it ran without a quadratic drag)."""
+    s = state_of(Prog, None, None, Mesh, backend)
+    sp = np.empty(Mesh.data.nEdges, dtype=np.float64)
+    L.check(L.lib().moka_bottom_speed_download(s.handle, L.f64(sp)), backend._h)
+    return sp
+
+
 def ocn_run_loop(*args, backend: Backend):
     """run_loop.jl:8-22 verbatim (it needs no method of its own in the shim) and the (sumCPU, sumGPU, ...) form :26-45."""
     want_sum = len(args) == 11

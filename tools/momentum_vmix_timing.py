@@ -13,7 +13,11 @@ run: the copy rate of moka_bw_probe and the pass's bytes at that rate -- u in an
 moka_forced_tape (moka_forced_adjoint_sweep over one recorded step: the transposed pass, the cell gather and the four transposed RK
 stages) with the pass off, with the scalar nuV (four column sets a tile) and with the field (five), DF flagged in a fourth leg.
 
-    python3 tools/momentum_vmix_timing.py [--small] [--field] [--adjoint] [--rounds R] [--steps N] [--out FILE]"""
+--quadratic adds the legs of the quadratic bottom drag (moka_set_quadratic_bottom_drag; Cd with dt Cd sp / hm = 1/2 at the rms speed of
+the state): "lin" (nuV + r, the linear drag the others are read against), "qd" (nuV + Cd), "qdlin" (nuV + r + Cd), "qdall" (+ stress);
+the step then issues the bottom-speed launch in front of the pass.
+
+    python3 tools/momentum_vmix_timing.py [--small] [--field] [--quadratic] [--adjoint] [--rounds R] [--steps N] [--out FILE]"""
 import argparse
 import datetime as dt
 import json
@@ -35,6 +39,7 @@ ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--steps", type=int, default=5)
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--field", action="store_true")
+ap.add_argument("--quadratic", action="store_true")
 ap.add_argument("--adjoint", action="store_true")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
@@ -58,6 +63,12 @@ if args.field:
     fld = (nu * np.linspace(4.0, 0.25, K)[None, :] * np.random.default_rng(2).uniform(0.5, 1.5, (mesh.nEdges, 1))).copy()
     LEGS += (("fld", 0, {"viscosity_field": fld}), ("fldall", 0, {"viscosity_field": fld, "bottom_drag": drag, "surface_stress": tau}),
              ("fld3", 3, {"viscosity_field": fld}), ("fldall3", 3, {"viscosity_field": fld, "bottom_drag": drag, "surface_stress": tau}))
+if args.quadratic:
+    cd = drag / max(float(np.sqrt(np.mean(u ** 2))), 1e-30)
+    for v, sfx in ((0, ""), (3, "3")):
+        LEGS += (("lin" + sfx, v, {"viscosity": nu, "bottom_drag": drag}), ("qd" + sfx, v, {"viscosity": nu, "quadratic_drag": cd}),
+                 ("qdlin" + sfx, v, {"viscosity": nu, "bottom_drag": drag, "quadratic_drag": cd}),
+                 ("qdall" + sfx, v, {"viscosity": nu, "bottom_drag": drag, "surface_stress": tau, "quadratic_drag": cd}))
 ms = {name: [] for name, _, _ in LEGS}
 paths = {}
 for _ in range(args.rounds):
@@ -80,7 +91,7 @@ bw = b.bw_probe()
 nC, nE = mesh.nCells, mesh.nEdges
 bound = (2 * nE + nC) * K * 8 / (bw.get("copy_GBs") * 1e9) * 1e3
 rows = []
-extra = ("fld", "fldall") if args.field else ()
+extra = (("fld", "fldall") if args.field else ()) + (("lin", "qd", "qdlin", "qdall") if args.quadratic else ())
 for form, off, legs in (("tile", "off", ("nu", "all") + extra), ("column", "off3", ("nu3", "all3") + tuple(x + "3" for x in extra))):
     for leg in legs:
         p = med(ms[leg]) - med(ms[off])
