@@ -862,11 +862,13 @@ int  moka_has_vertical_viscosity_field(const moka_state *st, int *out);
  * allocates anything.
  * MOKA_ERR_ARG, with nothing changed, for a negative, NaN or infinite Cd and NULL pointers.  MOKA_ERR_UNSUPPORTED for Cd != 0 where
  * moka_set_vertical_viscosity returns it for a nonzero value (fp32 storage, a halo, a partitioned mesh, an existing moka_tape) and
- * while a moka_forced_tape of the state exists; everything that is refused while the pass is on is refused when Cd turned it on, and
- * moka_forced_tape_create and moka_step_rk4_forced_taped return MOKA_ERR_UNSUPPORTED while Cd != 0 (q_e depends on u* through a
- * horizontal stencil: the transposed pass would no longer be column-local).  The tracer tape is unaffected.
+ * while a moka_forced_tape made by moka_forced_tape_create exists; everything that is refused while the pass is on is refused when Cd
+ * turned it on, and moka_forced_tape_create, and moka_step_rk4_forced_taped on such a tape, return MOKA_ERR_UNSUPPORTED while Cd != 0.
+ * Reverse mode of the flow through this drag is the business of a tape made by moka_forced_tape_create_quadratic (below), beside
+ * which any Cd is accepted at any time.  The tracer tape is unaffected.
  * Out of scope: reverse mode of the flow through this drag, a Cd field per edge or cell, Forward Euler, fp32 storage, partitioned
- * meshes, YAML keys and NetCDF I/O. */
+ * meshes, YAML keys and NetCDF I/O -- "reverse mode" meaning moka_tape and a tape of moka_forced_tape_create here: the one tape that
+ * differentiates the flow through this drag is that of moka_forced_tape_create_quadratic. */
 int  moka_set_quadratic_bottom_drag(moka_state *st, double cd);
 /* Cd as it stands; MOKA_ERR_ARG for a NULL out-pointer */
 int  moka_quadratic_bottom_drag(const moka_state *st, double *cd);
@@ -1115,8 +1117,9 @@ int  moka_adjoint_download(moka_tape *t, int field, double *host);
  * Usage: forced_tape_create -> [want_gradient] -> n x step_rk4_forced_taped -> seed -> sweep -> download / density_download / gradient.
  * Out of scope: the nonlinear, Del2 and Del4 dycores (no moka_tape covers them either), Forward Euler, the piecewise, partitioned
  * taping calls, fp32 storage, a time-dependent stress and a per-step split of the densities, second derivatives, the quadratic drag
- * (moka_forced_tape_create and moka_step_rk4_forced_taped return MOKA_ERR_UNSUPPORTED while Cd != 0, and
- * moka_set_quadratic_bottom_drag refuses a nonzero Cd while a forced tape exists), coupling to the tracer tape, the 13-stream form for taped steps, YAML keys and NetCDF I/O. */
+ * on a tape of this call (moka_forced_tape_create and moka_step_rk4_forced_taped return MOKA_ERR_UNSUPPORTED while Cd != 0, and
+ * moka_set_quadratic_bottom_drag refuses a nonzero Cd while such a tape exists: moka_forced_tape_create_quadratic, below, is the tape
+ * that carries it), coupling to the tracer tape, the 13-stream form for taped steps, YAML keys and NetCDF I/O. */
 typedef struct moka_forced_tape moka_forced_tape;
 int  moka_forced_tape_create(moka_state *st, int64_t capacity_steps, moka_forced_tape **out);
 void moka_forced_tape_destroy(moka_forced_tape *t);
@@ -1165,6 +1168,56 @@ int  moka_forced_tape_vmix_path(const moka_forced_tape *t);
  * host: (nEdges, nVertLevels) doubles in the caller's numbering. */
 int  moka_forced_adjoint_want_viscosity_field_gradient(moka_forced_tape *t, int on);
 int  moka_forced_adjoint_viscosity_field_density_download(moka_forced_tape *t, double *host);
+/* The quadratic bottom drag in reverse mode.  moka_forced_tape_create_quadratic behaves as moka_forced_tape_create, every refusal
+ * included (a halo, a partitioned mesh, an existing moka_tape or moka_forced_tape, fp32 storage, the nonlinear terms, tracers), except
+ * that it accepts a state with any Cd and marks the tape "quadratic": moka_step_rk4_forced_taped on it accepts Cd != 0 and records
+ * the step's Cd beside nuV and r, so Cd may change between recorded steps, and moka_set_quadratic_bottom_drag accepts a nonzero Cd
+ * beside it (a state has at most one forced tape: the setter refuses beside a plain one, with the error text it always had).  A
+ * quadratic tape on a state whose Cd stays 0, without the flag below, allocates, records and launches what a plain one does.
+ * The transposed recipe, for a recorded step with Cd != 0 and dt != 0.0, notation as above, us the recorded u*, sp the recorded
+ * bottom speed of the step, kb_e = n_e - 1, every operation rounded once, nothing contracted, in this order:
+ *   q_e    = dt * (r + Cd * sp[e])            the forward's expression on the recorded sp: its bits; it stands for q in d[n-1] and Rn[n-1],
+ *                                             and the drag lines are on whatever r is (every column with n >= 1 is a computed column)
+ *   z, hbar, XU, the cell gather, G_tau, D_nu, D_r, DF   as written above, with q_e
+ *   t      = z[n-1] * un[n-1]                 once per column, n == 1 included                    (q-bar_e = -t)
+ *   M[e]   = (0.0 - (dt * Cd) * t) / sp[e]    where sp[e] > 0, else 0.0;  0.0 for edges with n == 0   (sp-bar_e / sp_e)
+ * and then, per edge e' with n' = n_e' >= 1 and per level k that is the bottom level kb_e of some edge e in a slot of edgesOnCell of
+ * c1 or c2 of e' with n_e >= 1 and kb_e < n':
+ *   a_j    = 0.0; for the slots i of cell c_j in ascending order with kb_e == k: a_j = a_j + M[e]            j = 1, 2
+ *   g      = a_1 * invArea[c1] + a_2 * invArea[c2]
+ *   XU[k,e'] = XU[k,e'] + (kc[e'] * us[k,e']) * g
+ * which is the transpose of the bottom-speed stencil: sp_e^2 = KE_c1[kb_e] + KE_c2[kb_e] has d sp_e / d u*[k,e'] = kc[e'] u*[k,e']
+ * (invArea[c1] [e' in c1] + invArea[c2] [e' in c2]) / sp_e for k == kb_e < n_e'.  The edge e' sits in both its cells' slot lists and
+ * is counted in both, as in the forward.  sp does not depend on h: XH gets no new term.  sp_e == 0 is the kink of the square root,
+ * where the speed has no derivative: M[e] = 0.0 there, the subgradient that keeps a resting bottom layer at rest; with it a state
+ * whose bottom flow is exactly zero gives XU the bits of the linear-drag transpose with r alone.  Rows k >= n_e' of XU and us are
+ * never read or written, and M and us of a slot that fails the test are not read: NaN there does not travel.
+ * The density of Cd (moka_forced_adjoint_want_quadratic_drag_gradient, a call of its own: `what` of
+ * moka_forced_adjoint_want_gradient keeps its three bits; MOKA_ERR_UNSUPPORTED on a tape of moka_forced_tape_create, MOKA_ERR_ARG with
+ * recorded steps; the first flag allocates nEdges doubles and uploads kc where the mesh has not): per reversed step with dt != 0.0
+ * and per edge with n >= 1,
+ *   D_cd[e] = D_cd[e] - (dt * t) * sp[e]
+ * also in steps recorded with Cd == 0, where q = dt * r, the switches are the step's own, no M is formed and the stencil's
+ * transpose is not launched: the derivative at zero.  As for the other densities, the columns the forward pass skipped are then
+ * solved for the density alone.  d J / d Cd = sum_e D_cd[e], summed as the other scalar gradients are; every seed zeroes D_cd.
+ * The tape records, device to device on the state's stream: sp (nEdges doubles) of a step with Cd != 0 -- a copy of the sp the pass
+ * used -- or with the flag set -- then moka's bottom-speed launch runs on u* straight into the tape's record and writes no state
+ * memory; and u* (nVertLevels * nEdges doubles) of a step with Cd != 0, taken between stage 4 and the pass.  Each array is allocated
+ * by the first step that needs it, ahead of that step's first launch: capacity * (nVertLevels + 1) * nEdges doubles more than a
+ * plain tape in all, and nEdges for M.
+ * Kernels: the transposed pass runs QD instances of its two forms (M and sp are per-lane scalars: tiles, LDS, the 79 / 80 and 63 / 64
+ * boundaries and the path values do not change); the stencil's transpose is a gather with the bottom-speed kernel's shape, one lane
+ * per edge e', the grouping by level a predicate scan in registers, distinct levels distinct elements of the lane's own column: no
+ * atomics, one summation order; any nVertLevels, any maxEdges, every kernel variant.  Both forms and the numpy twin agree bit for bit.
+ * host: nEdges doubles in the caller's numbering; *out: the host sum.  A download or gradient without the flag is MOKA_ERR_ARG.
+ * Out of scope: a Cd field, a per-step split of the density, second derivatives, a smoothed square root at sp == 0. */
+int  moka_forced_tape_create_quadratic(moka_state *st, int64_t capacity_steps, moka_forced_tape **out);
+int  moka_forced_adjoint_want_quadratic_drag_gradient(moka_forced_tape *t, int on);
+int  moka_forced_adjoint_quadratic_drag_density_download(moka_forced_tape *t, double *host);
+int  moka_forced_adjoint_quadratic_drag_gradient(moka_forced_tape *t, double *out);
+/* how many device arrays the handle owns itself (those of the moka_tape it embeds not counted), 0 for NULL: what the lazy allocations
+ * above can be checked by -- a quadratic tape whose steps saw no Cd and no flag reports what a plain one does */
+int64_t moka_forced_tape_device_arrays(const moka_forced_tape *t);
 
 #ifdef __cplusplus
 }

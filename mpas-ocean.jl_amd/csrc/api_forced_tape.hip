@@ -16,9 +16,9 @@
 // ---------------------------------------------------------------------------------------------
 using namespace mk;
 
-extern "C" {
-
-int moka_forced_tape_create(moka_state *st, int64_t capacity_steps, moka_forced_tape **out)
+// quadratic: the tape of moka_forced_tape_create_quadratic, which carries the quadratic drag; a plain one refuses a state with Cd != 0
+// and is counted in forcedPlainTapes, where moka_set_quadratic_bottom_drag looks
+static int forced_tape_create(moka_state *st, int64_t capacity_steps, moka_forced_tape **out, bool quadratic)
 {
     if (!st || !out || capacity_steps < 0) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "bad argument");
     *out = nullptr;
@@ -26,7 +26,7 @@ int moka_forced_tape_create(moka_state *st, int64_t capacity_steps, moka_forced_
     if (st->halos > 0) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "forced tape: not on a state with a halo");
     if (p.nPatchesLaunch != p.nPatches) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "forced tape: whole (unpartitioned) meshes only");
     if (st->dycoreTapes > 0) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "forced tape: a moka_tape of this state exists");
-    if (st->momCd != 0.0)
+    if (!quadratic && st->momCd != 0.0)
         return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "forced tape: no reverse mode through the quadratic bottom drag (moka_set_quadratic_bottom_drag(st, 0) first)");
     moka_forced_tape *ft = new (std::nothrow) moka_forced_tape();
     if (!ft) return fail(st->ctx, MOKA_ERR_ALLOC, "out of host memory");
@@ -35,15 +35,31 @@ int moka_forced_tape_create(moka_state *st, int64_t capacity_steps, moka_forced_
     ft->st = st;
     ft->mem.ctx = st->ctx; ft->mem.owner = "forced tape";
     ft->capacity = capacity_steps;
+    ft->quadratic = quadratic;
+    if (!quadratic) { ++st->forcedPlainTapes; ft->countedPlain = true; }
     *out = ft;
     return MOKA_OK;
+}
+
+extern "C" {
+
+int moka_forced_tape_create(moka_state *st, int64_t capacity_steps, moka_forced_tape **out)
+{
+    return forced_tape_create(st, capacity_steps, out, false);
+}
+
+int moka_forced_tape_create_quadratic(moka_state *st, int64_t capacity_steps, moka_forced_tape **out)
+{
+    return forced_tape_create(st, capacity_steps, out, true);
 }
 
 void moka_forced_tape_destroy(moka_forced_tape *ft)
 {
     if (!ft) return;
-    if (tape_destroy(ft->inner))                     // synchronises the stream
+    if (tape_destroy(ft->inner)) {                   // synchronises the stream
         ft->st->forcedSteps -= (int64_t)ft->steps.size();
+        if (ft->countedPlain) --ft->st->forcedPlainTapes;
+    }
     ft->mem.release_all();
     delete ft;
 }
@@ -54,16 +70,23 @@ int moka_step_rk4_forced_taped(moka_forced_tape *ft, double dt)
     moka_state *st = ft->st;
     const Plan &p = st->mesh->plan;
     if ((int64_t)ft->steps.size() >= ft->capacity) return fail(st->ctx, MOKA_ERR_ARG, "forced tape is full");
-    if (st->momCd != 0.0)        // (the setter refuses a nonzero value beside a forced tape: kept for a state that gains another path to it)
+    if (!ft->quadratic && st->momCd != 0.0)      // (the setter refuses a nonzero value beside a plain forced tape: kept for a state that gains another path to it)
         return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "forced tape: no reverse mode through the quadratic bottom drag");
     const bool on = mom_vmix_on(st);
     if (on && dt < 0.0) return fail(st->ctx, MOKA_ERR_ARG, "vertical momentum mixing: dt must be >= 0 (the implicit solve is not reversible in time)");
-    const bool rec = on || ft->want != 0 || ft->wantF;
+    const bool rec = on || ft->want != 0 || ft->wantF || ft->wantCd;
     HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
     const size_t nEK = (size_t)p.K * p.nE, nCK = (size_t)p.K * p.nC;
     if (rec && !ft->unRec)
         if (int rc = ft->mem.alloc_all({{&ft->unRec, nEK * (size_t)ft->capacity}, {&ft->hnRec, nCK * (size_t)ft->capacity}, {&ft->hbar, nEK}, {&ft->scratch, 2 * nEK}}))
             return rc;
+    // the quadratic drag: sp of a step whose pass runs with Cd != 0 or whose density of Cd is wanted, u* of a step with Cd != 0 --
+    // allocated ahead of the step's first launch, by the first step that needs each (a plain tape has qd == wsp == false)
+    const bool qd = ft->quadratic && st->momCd != 0.0 && dt != 0.0, wsp = qd || (ft->wantCd && dt != 0.0);
+    if (wsp && !ft->spRec)
+        if (int rc = ft->mem.alloc(&ft->spRec, (size_t)p.nE * (size_t)ft->capacity)) return rc;
+    if (qd && !ft->usRec)
+        if (int rc = ft->mem.alloc_all({{&ft->usRec, nEK * (size_t)ft->capacity}, {&ft->M, (size_t)p.nE}})) return rc;
     // the viscosity field the step is about to run with: a copy of its own when the tape's newest one is of another generation,
     // allocated and taken ahead of the step's first launch (a step that fails afterwards leaves a copy the next step uses)
     const double *fld = on ? mom_vmix_field(st) : nullptr;
@@ -76,14 +99,23 @@ int moka_step_rk4_forced_taped(moka_forced_tape *ft, double dt)
         HIPCHK(st->ctx, hipMemcpyAsync(copy, fld, nEK * sizeof(double), hipMemcpyDeviceToDevice, s));
     }
     if (int rc = moka_step_rk4_taped(ft->inner, dt)) return rc;
+    const size_t i = ft->steps.size();
+    if (qd)                      // u*, before the pass overwrites it
+        HIPCHK(st->ctx, hipMemcpyAsync(ft->usRec + nEK * i, st->lev[1].u, nEK * sizeof(double), hipMemcpyDeviceToDevice, s));
+    else if (wsp)                // Cd == 0 and the density of Cd wanted: sp of u* straight into the record (no state memory is written)
+        HIPCHK(st->ctx, launch_momentum_bottom_speed(bottom_speed_args(st, st->lev[1].u, ft->spRec + (size_t)p.nE * i), s));
     if (on && dt != 0.0)         // the split step of moka_step_rk4, on the same two arrays (rk4_end has made them the current level)
         if (int rc = momentum_vmix(st, st->lev[1].u, st->lev[1].h, dt)) return rc;
-    const size_t i = ft->steps.size();
+    if (qd)                      // the sp the pass used
+        HIPCHK(st->ctx, hipMemcpyAsync(ft->spRec + (size_t)p.nE * i, st->momSpeed, (size_t)p.nE * sizeof(double), hipMemcpyDeviceToDevice, s));
     if (rec) {
         HIPCHK(st->ctx, hipMemcpyAsync(ft->unRec + nEK * i, st->lev[1].u, nEK * sizeof(double), hipMemcpyDeviceToDevice, s));
         HIPCHK(st->ctx, hipMemcpyAsync(ft->hnRec + nCK * i, st->lev[1].h, nCK * sizeof(double), hipMemcpyDeviceToDevice, s));
     }
-    ft->steps.push_back({rec, on, st->momTau && st->momTauOn, mom_vmix_nu(st), st->momDrag, fld ? (int32_t)ft->vfCopies.size() - 1 : -1});
+    ForcedStep fs{rec, on, st->momTau && st->momTauOn, mom_vmix_nu(st), st->momDrag, fld ? (int32_t)ft->vfCopies.size() - 1 : -1};
+    fs.cd = qd ? st->momCd : 0.0;
+    fs.sp = wsp;
+    ft->steps.push_back(fs);
     ++st->forcedSteps;
     return MOKA_OK;
 }
@@ -96,6 +128,7 @@ static int forced_zero_densities(moka_forced_tape *ft)
         const Plan &p = ft->st->mesh->plan;
         HIPCHK(ft->st->ctx, hipMemsetAsync(ft->densF, 0, (size_t)p.K * p.nE * sizeof(double), ft->st->ctx->stream));
     }
+    if (ft->densCd) HIPCHK(ft->st->ctx, hipMemsetAsync(ft->densCd, 0, (size_t)ft->st->mesh->plan.nE * sizeof(double), ft->st->ctx->stream));
     return MOKA_OK;
 }
 
@@ -154,9 +187,25 @@ int moka_forced_adjoint_sweep(moka_forced_tape *ft)
             a.Dr = (ft->want & MOKA_FORCED_GRAD_DRAG) ? ft->dens[2] : nullptr;
             a.fld = r.vf >= 0 ? ft->vfCopies[(size_t)r.vf] : nullptr;
             a.DF = ft->wantF ? ft->densF : nullptr;
-            const bool launched = ft->want != 0 || ft->wantF || (r.on && !(p.K < 2 && r.drag == 0.0 && !a.tau));
+            if (r.sp) {                 // a quadratic tape: the step's sp, its Cd, and the density of Cd while it is flagged
+                a.speed = ft->spRec + (size_t)p.nE * i; a.cd = r.cd;
+                a.Dcd = ft->wantCd ? ft->densCd : nullptr;
+                if (r.cd != 0.0) {      // M: 0.0 at the edges with no active level, which no lane writes
+                    a.M = ft->M;
+                    HIPCHK(st->ctx, hipMemsetAsync(ft->M, 0, (size_t)p.nE * sizeof(double), st->ctx->stream));
+                }
+            }
+            const bool launched = ft->want != 0 || ft->wantF || (a.speed && a.Dcd) || (r.on && !(p.K < 2 && r.drag == 0.0 && r.cd == 0.0 && !a.tau));
             HIPCHK(st->ctx, launch_momentum_vmix_adjoint(a, generic, st->ctx->stream));
             HIPCHK(st->ctx, launch_momentum_vmix_gather(a, st->ctx->stream));
+            if (r.cd != 0.0) {          // the transpose of the bottom-speed stencil, on the adjoint of u* the pass has just left
+                const MeshDev &d = st->mesh->dev;
+                MomSpeedAdjArgs g{};
+                g.nE = p.nE; g.K = p.K; g.ME = p.ME;
+                g.ehdr = d.ehdr; g.eoc = d.eoc; g.mltc = d.mltc; g.keCoef = d.keCoef; g.invArea = d.invArea;
+                g.M = ft->M; g.us = ft->usRec + nEK * i; g.xu = a.xu;
+                HIPCHK(st->ctx, launch_momentum_speed_adjoint(g, st->ctx->stream));
+            }
             if (launched) ft->path = momentum_vmix_adjoint_form(p.K, generic, a.fld != nullptr);
         }
         for (int sg = 4; sg >= 1; --sg)
@@ -242,17 +291,58 @@ int moka_forced_adjoint_viscosity_field_density_download(moka_forced_tape *ft, d
     return get_rows(ft->st->mesh, host, ft->densF, MOKA_EDGE, p.nE, p.K);
 }
 
+int moka_forced_adjoint_want_quadratic_drag_gradient(moka_forced_tape *ft, int on)
+{
+    if (!ft) return fail(nullptr, MOKA_ERR_ARG, "forced tape is NULL");
+    moka_state *st = ft->st;
+    if (!ft->quadratic) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "forced tape: the gradient of Cd needs a tape of moka_forced_tape_create_quadratic");
+    if (!ft->steps.empty()) return fail(st->ctx, MOKA_ERR_ARG, "forced tape: gradients are flagged while no step is recorded");
+    if (on && !ft->densCd) {
+        HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+        if (int rc = ensure_ke_coef(st->mesh)) return rc;       // a step with Cd == 0 launches the bottom speed for the record
+        if (int rc = ft->mem.alloc(&ft->densCd, (size_t)st->mesh->plan.nE)) return rc;
+        HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));
+    }
+    ft->wantCd = on != 0;
+    return MOKA_OK;
+}
+
+int moka_forced_adjoint_quadratic_drag_density_download(moka_forced_tape *ft, double *host)
+{
+    if (!ft || !host) return fail(ft ? ft->st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    if (!ft->wantCd) return fail(ft->st->ctx, MOKA_ERR_ARG, "forced tape: the gradient of Cd is not flagged");
+    HIPCHK(ft->st->ctx, hipSetDevice(ft->st->ctx->device));
+    return get_rows(ft->st->mesh, host, ft->densCd, MOKA_EDGE, ft->st->mesh->plan.nE, 1);
+}
+
+// the caller's edge numbering, ascending, one rounding at the end: independent of the plan's order
+static double host_sum(const std::vector<double> &w)
+{
+    long double sum = 0.0L;
+    for (double v : w) sum += (long double)v;
+    return (double)sum;
+}
+
+int moka_forced_adjoint_quadratic_drag_gradient(moka_forced_tape *ft, double *out)
+{
+    if (!ft || !out) return fail(ft ? ft->st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    std::vector<double> w((size_t)ft->st->mesh->plan.nE);
+    if (int rc = moka_forced_adjoint_quadratic_drag_density_download(ft, w.data())) return rc;
+    *out = host_sum(w);
+    return MOKA_OK;
+}
+
 int moka_forced_adjoint_gradient(moka_forced_tape *ft, int what, double *out)
 {
     if (!ft || !out) return fail(ft ? ft->st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
     std::vector<double> w((size_t)ft->st->mesh->plan.nE);
     if (int rc = moka_forced_adjoint_density_download(ft, what, w.data())) return rc;
-    long double sum = 0.0L;            // the caller's edge numbering, ascending, one rounding at the end: independent of the plan's order
-    for (double v : w) sum += (long double)v;
-    *out = (double)sum;
+    *out = host_sum(w);
     return MOKA_OK;
 }
 
 int moka_forced_tape_vmix_path(const moka_forced_tape *ft) { return ft ? ft->path : 0; }
+
+int64_t moka_forced_tape_device_arrays(const moka_forced_tape *ft) { return ft ? (int64_t)ft->mem.ptrs.size() : 0; }
 
 }  // extern "C"

@@ -480,8 +480,15 @@ void rk13_end(moka_state *st)
     st->lazyPu = st->lazyPh = nullptr; st->lazyOwner = nullptr;
 }
 
+// keCoef on the device: meshes with the nonlinear arrays upload it when they are created, the others when a state first asks
+int ensure_ke_coef(moka_mesh *m)
+{
+    if (m->dev.keCoef) return MOKA_OK;
+    return m->mem.upload(m->plan.keCoef, &m->dev.keCoef);
+}
+
 // the bottom-speed launch over the whole mesh: u a (K, nE) field, sp nE doubles (keCoef is on the device: ensure_ke_coef)
-static MomSpeedArgs bottom_speed_args(const moka_state *st, const double *u, double *sp)
+MomSpeedArgs bottom_speed_args(const moka_state *st, const double *u, double *sp)
 {
     const Plan &p = st->mesh->plan;
     const MeshDev &d = st->mesh->dev;
@@ -1235,13 +1242,6 @@ int moka_has_vertical_viscosity_field(const moka_state *st, int *out)
 }
 
 // ---- the quadratic bottom drag (include/moka_hip.h: the recipe; momentum_vmix.hip: k_mvmix_bottom_speed and the QD instances) ----
-// keCoef on the device: meshes with the nonlinear arrays upload it when they are created, the others when a state first asks
-static int ensure_ke_coef(moka_mesh *m)
-{
-    if (m->dev.keCoef) return MOKA_OK;
-    return m->mem.upload(m->plan.keCoef, &m->dev.keCoef);
-}
-
 int moka_set_quadratic_bottom_drag(moka_state *st, double cd)
 {
     if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
@@ -1249,7 +1249,7 @@ int moka_set_quadratic_bottom_drag(moka_state *st, double cd)
         return fail(st->ctx, MOKA_ERR_ARG, "vertical momentum mixing: the quadratic drag coefficient must be finite and >= 0");
     if (cd != 0.0) {
         if (int rc = mom_vmix_supported(st)) return rc;
-        if (st->forcedTapes > 0)
+        if (st->forcedPlainTapes > 0)     // (a tape of moka_forced_tape_create_quadratic carries Cd: it is counted in forcedTapes alone)
             return fail(st->ctx, MOKA_ERR_UNSUPPORTED,
                         "vertical momentum mixing: no quadratic drag while a moka_forced_tape of this state exists (reverse mode does not cover it)");
         HIPCHK(st->ctx, hipSetDevice(st->ctx->device));

@@ -391,10 +391,35 @@ struct MomVmixAdjArgs {
     double *Gtau, *Dnu, *Dr;
     const double *fld;            // the field the step ran with (nullptr: the scalar nu): the FIELD instances, five column sets a tile
     double *DF;                   // (K, nE) density of the field, rows k < n - 1 of a solved column (nullptr: not wanted)
+    // the quadratic drag (a quadratic moka_forced_tape): speed != nullptr selects the QD instances -- the recorded sp[e] (nE) of the
+    // step, q = dt * (drag + cd * speed[e]) per lane when cd != 0.0 (the forward's bits; the drag lines are then on whatever drag is)
+    // and the one q = dt * drag when cd == 0.0.  M (nE; needed when cd != 0.0): the lane's sp-bar / sp for launch_momentum_speed_adjoint;
+    // Dcd (nE; nullptr: not wanted): the density of Cd.  speed == nullptr: the instances without any of it.
+    const double *speed;
+    double cd;
+    double *M, *Dcd;
 };
 int momentum_vmix_adjoint_form(int K, bool generic, bool field);            // vmix_kernel(K, generic, field ? 5 : 4).form
 hipError_t launch_momentum_vmix_adjoint(const MomVmixAdjArgs &a, bool generic, hipStream_t s);
 hipError_t launch_momentum_vmix_gather(const MomVmixAdjArgs &a, hipStream_t s);
+
+// ---- the transpose of the bottom-speed stencil (a quadratic moka_forced_tape; momentum_vmix.hip: k_mvadj_bottom_speed) ----
+// Behind the transposed pass of a step with Cd != 0, one lane per edge e' with n' = min(maxLevelEdgeTop[e'], K) >= 1 (the recipe of
+// include/moka_hip.h): for every level k that is the bottom level kb_e = n_e - 1 < n' of an edge e in a slot of e''s two cells,
+//   a_j = (the sum, from 0.0, over the slots of cell c_j in slot order with kb_e == k, of M[e]);   g = a_1 * invArea[c1] + a_2 * invArea[c2]
+//   xu[k,e'] = xu[k,e'] + (keCoef[e'] * us[k,e']) * g
+// Rows k >= n' of xu and us are never touched; M and us of a slot that fails the test are not read.
+struct MomSpeedAdjArgs {
+    int nE, K, ME;
+    const int32_t *ehdr;          // (4, nE) c1, c2, -, maxLevelEdgeTop
+    const int32_t *eoc, *mltc;    // (ME, nC) edges of a cell, -1 = none; maxLevelEdgeTop of that edge, 0 = none
+    const double *keCoef;         // (nE)
+    const double *invArea;        // (nC)
+    const double *M;              // (nE) sp-bar[e] / sp[e] of the transposed pass, 0.0 where sp[e] == 0 and where n_e == 0
+    const double *us;             // (K, nE) the recorded u* of the step
+    double *xu;                   // (K, nE) the adjoint of u*, updated in place
+};
+hipError_t launch_momentum_speed_adjoint(const MomSpeedAdjArgs &a, hipStream_t s);
 
 // ---- reverse mode of one Forward-Euler step: gather form, the oracle's summation order ----
 struct AdjMesh {

@@ -2,7 +2,8 @@
 // moka_set_vertical_viscosity / moka_surface_stress_upload / moka_set_quadratic_bottom_drag, NOT in the reference): one tridiagonal
 // solve per edge column behind stage 4 of an RK4 step, on the new normalVelocity over the new layerThickness, the bottom speed of the
 // quadratic drag gathered by a launch in front of it.  Second half of the file: the transpose of that pass for
-// moka_forced_tape (reverse mode through the forced step), in the same two forms, and the cell gather of its thickness terms.
+// moka_forced_tape (reverse mode through the forced step), in the same two forms, the cell gather of its thickness terms, and the
+// transpose of the bottom-speed stencil for a tape that carries the quadratic drag.
 #include "kernels_common.hpp"
 #include "mvmix_index.hpp"
 
@@ -429,10 +430,31 @@ hipError_t launch_momentum_vmix(const MomVmixArgs &a, bool generic, hipStream_t 
 //     s(k)                   FIELD only: dt * f[k,e] of the recorded step's field, read in both sweeps (the tile keeps f in a set of its own)
 //     putDF(k, v)            GRAD with wdf only: DF[k,e] = DF[k,e] - v, v = dt * (de[k] / hm[k]), k <= n - 2, called once h(k + 1) is read
 // FIELD: s[k] = dt * f[k,e] in both places where w is formed; everything else as written.
+// QD (a step of a quadratic tape whose sp was recorded): q is the lane's own, and mvadj_speed_bar runs once at the end of the column;
+// an instance without it holds none of its operations.
 // ================================================================================================
-template <bool DRAG, bool STRESS, bool GRAD, bool FIELD, class C>
+// QD (a quadratic moka_forced_tape; the lane's q comes from the recorded sp[e], see mvadj_q): with t = z[n-1] * un[n-1], formed once
+// per column, q-bar = -t, hence sp-bar = dt * Cd * q-bar and, for the transpose of the bottom-speed stencil, M = sp-bar / sp -- 0.0 at
+// sp == 0, the kink of the square root -- and the density of Cd takes dt * sp * q-bar.  mo: M[e] (nullptr: the step ran with Cd == 0),
+// dc: Dcd[e] (nullptr: not wanted).
+__device__ __forceinline__ void mvadj_speed_bar(const double t, const double sp, const double dt, const double dtcd, double *const mo,
+                                                double *const dc)
+{
+    if (mo) *mo = sp > 0.0 ? (0.0 - dtcd * t) / sp : 0.0;
+    if (dc) *dc = *dc - (dt * t) * sp;
+}
+
+// the q of a lane in the QD instances: the forward's mvmix_q<true> expression on the recorded sp for a step with Cd != 0, the one
+// q = dt * drag for a step with Cd == 0 whose sp was recorded for the density alone
+__device__ __forceinline__ double mvadj_q(const MomVmixAdjArgs &a, const double sp)
+{
+    return a.cd != 0.0 ? a.dt * (a.drag + a.cd * sp) : a.dt * a.drag;
+}
+
+template <bool DRAG, bool STRESS, bool GRAD, bool FIELD, bool QD, class C>
 __device__ __forceinline__ void mvadj_column(C &c, const int n, const double s, const double q, const double b, const double dt,
-                                             double *const gt, double *const dn, double *const dr, const bool wdf)
+                                             double *const gt, double *const dn, double *const dr, const bool wdf, const double sp = 0.0,
+                                             const double dtcd = 0.0, double *const mo = nullptr, double *const dc = nullptr)
 {
     double hk = c.h(0);
     if (n == 1) {
@@ -447,6 +469,7 @@ __device__ __forceinline__ void mvadj_column(C &c, const int n, const double s, 
             if (gt) *gt = *gt + dt * z;
             if (dr) *dr = *dr - dt * (z * uk);
         }
+        if (QD) mvadj_speed_bar(z * uk, sp, dt, dtcd, mo, dc);
         return;
     }
     double hn = c.h(1);
@@ -518,6 +541,7 @@ __device__ __forceinline__ void mvadj_column(C &c, const int n, const double s, 
         if (dn) *dn = *dn - dt * sum;
         if (dr) *dr = *dr - dt * (zk * uk);         // row n - 1
     }
+    if (QD) mvadj_speed_bar(zk * uk, sp, dt, dtcd, mo, dc);
 }
 
 // the two depths of a column in a launch of the transpose: nw, the rows whose xu and hbar it writes -- the forward's mvmix_depth, 0
@@ -557,7 +581,7 @@ struct MvadjTileCol {
     __device__ __forceinline__ void putXU(int k, double v) { xs[k] = v; }
 };
 
-template <bool DRAG, bool STRESS, bool GRAD, bool FIELD>
+template <bool DRAG, bool STRESS, bool GRAD, bool FIELD, bool QD>
 __global__ __launch_bounds__(MV_NT) void k_mvadj_tile(const MomVmixAdjArgs a, const int te, const int cs, const unsigned magic)
 {
     extern __shared__ __align__(16) unsigned char mv_smem[];
@@ -568,7 +592,7 @@ __global__ __launch_bounds__(MV_NT) void k_mvadj_tile(const MomVmixAdjArgs a, co
     const int tid = threadIdx.x, K = a.K;
     const MvSpan sp = mv_span(blockIdx.x, te, a.nE, K);
     int n = 0;
-    double b = 0.0;
+    double b = 0.0, spd = 0.0;
     if (tid < te) {
         int4 r = make_int4(0, 0, 0, 0);
         if (tid < sp.ncol) {
@@ -576,6 +600,7 @@ __global__ __launch_bounds__(MV_NT) void k_mvadj_tile(const MomVmixAdjArgs a, co
             int nw;
             n = mvadj_depth<DRAG, STRESS, GRAD>(r.w, K, a.on, nw);
             if (STRESS && n > 0) b = a.dt * a.tau[sp.e0 + tid];
+            if (QD && n > 0) spd = a.speed[sp.e0 + tid];
             r.z = nw;
         }
         r.w = n;
@@ -591,8 +616,13 @@ __global__ __launch_bounds__(MV_NT) void k_mvadj_tile(const MomVmixAdjArgs a, co
         const size_t o = (size_t)tid * cs;
         const int e = sp.e0 + tid;
         MvadjTileCol col{H + o, X + o, Gs + o, U + o, FIELD ? Fs + o : nullptr, a.dt};
-        mvadj_column<DRAG, STRESS, GRAD, FIELD>(col, n, a.dt * a.nu, a.dt * a.drag, b, a.dt, GRAD && a.Gtau ? a.Gtau + e : nullptr,
-                                                GRAD && a.Dnu ? a.Dnu + e : nullptr, GRAD && a.Dr ? a.Dr + e : nullptr, GRAD && a.DF);
+        if (QD)
+            mvadj_column<DRAG, STRESS, GRAD, FIELD, true>(col, n, a.dt * a.nu, mvadj_q(a, spd), b, a.dt, GRAD && a.Gtau ? a.Gtau + e : nullptr,
+                                                          GRAD && a.Dnu ? a.Dnu + e : nullptr, GRAD && a.Dr ? a.Dr + e : nullptr, GRAD && a.DF, spd,
+                                                          a.dt * a.cd, a.cd != 0.0 ? a.M + e : nullptr, GRAD && a.Dcd ? a.Dcd + e : nullptr);
+        else
+            mvadj_column<DRAG, STRESS, GRAD, FIELD, false>(col, n, a.dt * a.nu, a.dt * a.drag, b, a.dt, GRAD && a.Gtau ? a.Gtau + e : nullptr,
+                                                           GRAD && a.Dnu ? a.Dnu + e : nullptr, GRAD && a.Dr ? a.Dr + e : nullptr, GRAD && a.DF);
     }
     __syncthreads();
     mv_store_span<true>(X, a.xu + sp.base, hd, sp.nEl, tid, magic, K, cs);
@@ -624,7 +654,7 @@ struct MvadjGlobalCol {
     __device__ __forceinline__ void putXU(int k, double v) { if (wr) xc[k] = v; }
 };
 
-template <bool DRAG, bool STRESS, bool GRAD, bool FIELD>
+template <bool DRAG, bool STRESS, bool GRAD, bool FIELD, bool QD>
 __global__ __launch_bounds__(BLOCK) void k_mvadj_column(const MomVmixAdjArgs a)
 {
     const int e = blockIdx.x * BLOCK + threadIdx.x;
@@ -636,9 +666,17 @@ __global__ __launch_bounds__(BLOCK) void k_mvadj_column(const MomVmixAdjArgs a)
     const size_t nEK = (size_t)a.nE * a.K, o = (size_t)e * a.K;
     MvadjGlobalCol col{a.hn + (size_t)r.x * a.K, a.hn + (size_t)r.y * a.K, a.un + o, a.xu + o, a.hbar + o, a.scratch + e, a.scratch + nEK + e,
                        (size_t)a.nE, nw > 0, FIELD ? a.fld + o : nullptr, GRAD && a.DF ? a.DF + o : nullptr, a.dt};
-    mvadj_column<DRAG, STRESS, GRAD, FIELD>(col, n, a.dt * a.nu, a.dt * a.drag, STRESS ? a.dt * a.tau[e] : 0.0, a.dt,
-                                            GRAD && a.Gtau ? a.Gtau + e : nullptr, GRAD && a.Dnu ? a.Dnu + e : nullptr,
-                                            GRAD && a.Dr ? a.Dr + e : nullptr, GRAD && a.DF);
+    if (QD) {
+        const double spd = a.speed[e];
+        mvadj_column<DRAG, STRESS, GRAD, FIELD, true>(col, n, a.dt * a.nu, mvadj_q(a, spd), STRESS ? a.dt * a.tau[e] : 0.0, a.dt,
+                                                      GRAD && a.Gtau ? a.Gtau + e : nullptr, GRAD && a.Dnu ? a.Dnu + e : nullptr,
+                                                      GRAD && a.Dr ? a.Dr + e : nullptr, GRAD && a.DF, spd, a.dt * a.cd,
+                                                      a.cd != 0.0 ? a.M + e : nullptr, GRAD && a.Dcd ? a.Dcd + e : nullptr);
+    } else {
+        mvadj_column<DRAG, STRESS, GRAD, FIELD, false>(col, n, a.dt * a.nu, a.dt * a.drag, STRESS ? a.dt * a.tau[e] : 0.0, a.dt,
+                                                       GRAD && a.Gtau ? a.Gtau + e : nullptr, GRAD && a.Dnu ? a.Dnu + e : nullptr,
+                                                       GRAD && a.Dr ? a.Dr + e : nullptr, GRAD && a.DF);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -667,27 +705,122 @@ __global__ __launch_bounds__(BLOCK) void k_mvadj_gather(const MomVmixAdjArgs a, 
     }
 }
 
-template <bool DRAG, bool STRESS, bool GRAD, bool FIELD>
+// ------------------------------------------------------------------------------------------------
+// The transpose of the bottom-speed stencil (a quadratic moka_forced_tape; the recipe of include/moka_hip.h), behind the transposed
+// pass of a step with Cd != 0 and in front of the four reverse RK stages.  k_mvmix_bottom_speed turned round: where its lane e gathers
+// u[kb_e,e'] over the slots e' of its two cells, the lane e' here gathers M[e] = sp-bar[e] / sp[e] over the same slots -- every edge
+// whose stencil holds e' shares a cell with it -- and adds (kc[e'] * us[k,e']) * g to the rows k of its own column of xu that are some
+// neighbour's bottom level kb_e < n_e'.  One lane per edge in device numbering; it loads its ehdr record, its two cells' eoc and
+// mltc rows (the neighbour's depth without a dependent read of its ehdr), invArea of both cells, kc[e'], then M[e] of every slot that
+// passes e >= 0, n_e >= 1, n_e - 1 < n_e', all in flight together; then us[k,e'] and xu[k,e'] of the distinct levels.  The grouping
+// by level is a predicate scan over the 2 * MS_ME slots in registers: a slot is the first of its level when no earlier passing slot
+// has its kb; the first slot of a level sums M over the slots of that level, cell by cell in slot order, and stores the one element.
+// Distinct levels are distinct elements of the lane's column: no atomics, no shuffles, no read-modify-write chain on an address,
+// one summation order.  The edge e' sits in both its cells' rows and is counted in both, as in the forward.  Rows k >= n_e' of xu and
+// us are never touched; M and us of a slot that fails the test are not read.  Any K, any maxEdges <= MS_ME, every kernel variant.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(BLOCK) void k_mvadj_bottom_speed(const MomSpeedAdjArgs a)
+{
+    const int e = blockIdx.x * BLOCK + threadIdx.x;
+    if (e >= a.nE) return;
+    const int4 r = *reinterpret_cast<const int4 *>(a.ehdr + (size_t)e * 4);
+    const int n = min(r.w, a.K);
+    if (n < 1) return;
+    int ee[2][MS_ME], kb[2][MS_ME];
+    bool ok[2][MS_ME], first[2][MS_ME];
+    double m[2][MS_ME], us[2][MS_ME], xo[2][MS_ME];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const size_t row = (size_t)(j ? r.y : r.x) * a.ME;
+#pragma unroll
+        for (int i = 0; i < MS_ME; ++i) {
+            ee[j][i] = i < a.ME ? a.eoc[row + i] : -1;
+            const int ml = i < a.ME ? min(a.mltc[row + i], a.K) : 0;
+            kb[j][i] = ml - 1;
+            ok[j][i] = i < a.ME && ee[j][i] >= 0 && ml >= 1 && ml - 1 < n;
+        }
+    }
+    const double inv0 = a.invArea[r.x], inv1 = a.invArea[r.y], kc = a.keCoef[e];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < MS_ME; ++i) m[j][i] = ok[j][i] ? a.M[ee[j][i]] : 0.0;
+    const size_t col = (size_t)e * a.K;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < MS_ME; ++i) {
+            bool f = ok[j][i];
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+                for (int ii = 0; ii < MS_ME; ++ii)
+                    if ((jj < j || (jj == j && ii < i)) && ok[jj][ii] && kb[jj][ii] == kb[j][i]) f = false;
+            first[j][i] = f;
+            us[j][i] = f ? a.us[col + kb[j][i]] : 0.0;
+            xo[j][i] = f ? a.xu[col + kb[j][i]] : 0.0;
+        }
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < MS_ME; ++i)
+            if (first[j][i]) {
+                const int k = kb[j][i];
+                double acc[2];
+#pragma unroll
+                for (int jj = 0; jj < 2; ++jj) {
+                    double s = 0.0;
+#pragma unroll
+                    for (int ii = 0; ii < MS_ME; ++ii)
+                        if (ok[jj][ii] && kb[jj][ii] == k) s = s + m[jj][ii];
+                    acc[jj] = s;
+                }
+                const double g = acc[0] * inv0 + acc[1] * inv1;
+                a.xu[col + k] = xo[j][i] + (kc * us[j][i]) * g;
+            }
+}
+
+hipError_t launch_momentum_speed_adjoint(const MomSpeedAdjArgs &a, hipStream_t s)
+{
+    if (a.nE <= 0 || a.K < 1) return hipSuccess;
+    if (a.ME > MS_ME || !a.ehdr || !a.eoc || !a.mltc || !a.keCoef || !a.invArea || !a.M || !a.us || !a.xu) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_mvadj_bottom_speed, dim3((a.nE + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+template <bool DRAG, bool STRESS, bool GRAD, bool FIELD, bool QD>
 static hipError_t launch_mvadj_with(const MomVmixAdjArgs &a, const VmixKernel &k, hipStream_t s)
 {
     if (k.form == 1) {
         const size_t lds = mv_tile_lds(FIELD ? 5 : 4, k.tc, a.K);        // k.lds + 12 * k.tc: the records take 16 bytes a column where vmix_kernel counts 4
         if (lds > 64 * 1024)
-            if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_mvadj_tile<DRAG, STRESS, GRAD, FIELD>)}, 80 * 1024); e != hipSuccess) return e;
-        hipLaunchKernelGGL((k_mvadj_tile<DRAG, STRESS, GRAD, FIELD>), dim3((a.nE + k.tc - 1) / k.tc), dim3(MV_NT), lds, s, a, k.tc, a.K | 1,
+            if (hipError_t e = raise_dyn_lds({reinterpret_cast<const void *>(k_mvadj_tile<DRAG, STRESS, GRAD, FIELD, QD>)}, 80 * 1024); e != hipSuccess) return e;
+        hipLaunchKernelGGL((k_mvadj_tile<DRAG, STRESS, GRAD, FIELD, QD>), dim3((a.nE + k.tc - 1) / k.tc), dim3(MV_NT), lds, s, a, k.tc, a.K | 1,
                            mv_magic((unsigned)a.K));
     } else {
-        hipLaunchKernelGGL((k_mvadj_column<DRAG, STRESS, GRAD, FIELD>), dim3((a.nE + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, a);
+        hipLaunchKernelGGL((k_mvadj_column<DRAG, STRESS, GRAD, FIELD, QD>), dim3((a.nE + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, a);
     }
     return hipGetLastError();
 }
 
+// the QD instances run when the step's sp is at hand and something reads it: Cd != 0 (q and M) or the density of Cd (then among the
+// gradient instances).  The drag lines are on with Cd != 0 whatever drag is, as in the forward; a step with Cd == 0 keeps the
+// switches it ran with.
+static bool mvadj_qd(const MomVmixAdjArgs &a) { return a.speed && (a.cd != 0.0 || a.Dcd); }
+static bool mvadj_drag(const MomVmixAdjArgs &a) { return a.drag != 0.0 || (a.speed && a.cd != 0.0); }
+
 template <bool GRAD, bool FIELD>
 static hipError_t launch_mvadj_grad(const MomVmixAdjArgs &a, const VmixKernel &k, hipStream_t s)
 {
-    const bool drag = a.drag != 0.0, stress = a.tau != nullptr;
-    return drag ? (stress ? launch_mvadj_with<true, true, GRAD, FIELD>(a, k, s) : launch_mvadj_with<true, false, GRAD, FIELD>(a, k, s))
-                : (stress ? launch_mvadj_with<false, true, GRAD, FIELD>(a, k, s) : launch_mvadj_with<false, false, GRAD, FIELD>(a, k, s));
+    const bool drag = mvadj_drag(a), stress = a.tau != nullptr;
+    if (mvadj_qd(a)) {
+        if (drag) return stress ? launch_mvadj_with<true, true, GRAD, FIELD, true>(a, k, s) : launch_mvadj_with<true, false, GRAD, FIELD, true>(a, k, s);
+        if constexpr (GRAD)         // Cd == 0 and no linear drag: the density of Cd alone, at zero
+            return stress ? launch_mvadj_with<false, true, true, FIELD, true>(a, k, s) : launch_mvadj_with<false, false, true, FIELD, true>(a, k, s);
+        return hipErrorInvalidValue;
+    }
+    return drag ? (stress ? launch_mvadj_with<true, true, GRAD, FIELD, false>(a, k, s) : launch_mvadj_with<true, false, GRAD, FIELD, false>(a, k, s))
+                : (stress ? launch_mvadj_with<false, true, GRAD, FIELD, false>(a, k, s) : launch_mvadj_with<false, false, GRAD, FIELD, false>(a, k, s));
 }
 
 // the one place that decides the kernel of a transposed pass: four column sets, five when the step ran with a field
@@ -696,10 +829,11 @@ int momentum_vmix_adjoint_form(int K, bool generic, bool field) { return mvadj_k
 
 hipError_t launch_momentum_vmix_adjoint(const MomVmixAdjArgs &a, bool generic, hipStream_t s)
 {
-    const bool drag = a.drag != 0.0, stress = a.tau != nullptr, grad = a.Gtau || a.Dnu || a.Dr || a.DF;
+    const bool drag = mvadj_drag(a), stress = a.tau != nullptr, grad = a.Gtau || a.Dnu || a.Dr || a.DF || (a.speed && a.Dcd);
     if (a.nE <= 0 || a.K < 1 || (!grad && (!a.on || (a.K < 2 && !drag && !stress)))) return hipSuccess;
     if ((uint64_t)a.K * 64u >= (1ull << 32)) return hipErrorInvalidValue;
     if (!a.xu || !a.un || !a.hn || !a.hbar) return hipErrorInvalidValue;
+    if (a.speed && a.cd != 0.0 && !a.M) return hipErrorInvalidValue;
     const VmixKernel k = mvadj_kernel(a.K, generic, a.fld != nullptr);
     if (k.form == 2 && !a.scratch) return hipErrorInvalidValue;
     if (a.fld) return grad ? launch_mvadj_grad<true, true>(a, k, s) : launch_mvadj_grad<false, true>(a, k, s);
@@ -708,7 +842,7 @@ hipError_t launch_momentum_vmix_adjoint(const MomVmixAdjArgs &a, bool generic, h
 
 hipError_t launch_momentum_vmix_gather(const MomVmixAdjArgs &a, hipStream_t s)
 {
-    const bool drag = a.drag != 0.0, stress = a.tau != nullptr;
+    const bool drag = mvadj_drag(a), stress = a.tau != nullptr;
     if (a.nC <= 0 || a.K < 1 || !a.on || (a.K < 2 && !drag && !stress)) return hipSuccess;
     int lpc = 1;
     while (lpc < a.K && lpc < 64) lpc *= 2;

@@ -274,6 +274,9 @@ struct moka_state {
     // vertical momentum pass keep working beside it) and the steps it holds (moka_surface_stress_upload refuses while there are any)
     int forcedTapes = 0;
     int64_t forcedSteps = 0;
+    // ... and how many of them are plain (moka_forced_tape_create, not moka_forced_tape_create_quadratic): moka_set_quadratic_bottom_drag
+    // refuses a nonzero Cd while this is nonzero
+    int forcedPlainTapes = 0;
     std::vector<moka_placement_trial> placementLog;   // what the last moka_state_optimize_placement tried
     int64_t placementLaunches = 0;                    // ... and how many stage launches it issued (measurement bookkeeping)
 };
@@ -348,6 +351,9 @@ void fe_end(moka_state *st, int flags, bool stageKernel, bool lean, bool prevMod
 // moka_step_rk4, and the same step recorded on `rec` (nullptr: not recorded); the vertical pass of the flow behind stage 4
 int step_rk4(moka_state *st, double dt, moka_tracer_tape *rec);
 int momentum_vmix(moka_state *st, double *u, const double *h, double dt);
+// keCoef on the device (uploaded when a state first asks); the bottom-speed launch over the whole mesh: u a (K, nE) field, sp nE doubles
+int ensure_ke_coef(moka_mesh *m);
+MomSpeedArgs bottom_speed_args(const moka_state *st, const double *u, double *sp);
 // api_tracers.hip: the tracer launch of RK4 stage s; the vertical pass, forwards and backwards; what it takes for tracer j
 hipError_t tracer_stage(moka_state *st, int s, const StageArgs &g);
 int tracer_vmix(moka_mesh *mm, moka_ctx *ctx, int nT, const double *h, double *x, const double *kv, const double *const *fld, double dt,

@@ -87,6 +87,8 @@ struct ForcedStep {
     bool rec, on, stress;        // u_new / h_new were recorded; the pass ran; with the stress
     double nu, drag;             // nu: what the pass took (0.0 under a field)
     int32_t vf;                  // the copy in moka_forced_tape.vfCopies of the field the step ran with, -1: the scalar nu
+    double cd = 0.0;             // a quadratic tape: the Cd the step ran with (its u* sits in usRec when it is nonzero) ...
+    bool sp = false;             // ... and whether the step's slot of spRec holds its bottom speed
 };
 
 struct moka_forced_tape {
@@ -103,6 +105,12 @@ struct moka_forced_tape {
     std::vector<double *> vfCopies;
     uint64_t vfGen = 0;
     int want = 0;                                    // MOKA_FORCED_GRAD_* bits
+    // the quadratic drag (moka_forced_tape_create_quadratic): spRec capacity x nE, the sp of every step with Cd != 0 or the flag;
+    // usRec capacity x (K, nE), u* of every step with Cd != 0, and M (nE), the transposed pass's sp-bar / sp -- each allocated by
+    // the first step that needs it; densCd (nE), the density of Cd, by its flag.  A plain tape never touches any of them.
+    bool quadratic = false, wantCd = false;
+    bool countedPlain = false;                       // st->forcedPlainTapes includes this tape
+    double *spRec = nullptr, *usRec = nullptr, *M = nullptr, *densCd = nullptr;
     std::vector<ForcedStep> steps;
     int path = 0;                                    // moka_forced_tape_vmix_path
     mk::DeviceAllocs mem;

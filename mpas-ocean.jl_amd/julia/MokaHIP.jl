@@ -815,11 +815,16 @@ mutable struct ForcedTape
     handle::Ptr{Cvoid}
     state::State
 end
-function ForcedTape(Prog::MProg, capacity::Integer)
+# quadratic_drag: a tape that carries the quadratic bottom drag Cd (moka_forced_tape_create_quadratic)
+function ForcedTape(Prog::MProg, capacity::Integer; quadratic_drag::Bool = false)
     s = Prog.ssh[end].state
     s === nothing && error("MokaHIP: the model is not on the device yet")
     ref = Ref{Ptr{Cvoid}}(C_NULL)
-    check(ccall((:moka_forced_tape_create, lib), Cint, (Ptr{Cvoid}, Int64, Ref{Ptr{Cvoid}}), s.handle, capacity, ref), s.backend.ctx)
+    if quadratic_drag
+        check(ccall((:moka_forced_tape_create_quadratic, lib), Cint, (Ptr{Cvoid}, Int64, Ref{Ptr{Cvoid}}), s.handle, capacity, ref), s.backend.ctx)
+    else
+        check(ccall((:moka_forced_tape_create, lib), Cint, (Ptr{Cvoid}, Int64, Ref{Ptr{Cvoid}}), s.handle, capacity, ref), s.backend.ctx)
+    end
     t = ForcedTape(ref[], s)           # holds the state (hence mesh and context count) alive
     retain!(s.backend)
     s.tapes += 1
@@ -865,6 +870,19 @@ function forced_viscosity_field_density!(out::Array{Float64}, t::ForcedTape)
     check(ccall((:moka_forced_adjoint_viscosity_field_density_download, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), t.handle, out), t.state.backend.ctx)
     out
 end
+# d J / d Cd of a tape made with quadratic_drag = true: flagged only while no step is recorded; the per-edge density and its host sum
+function want_quadratic_drag_gradient!(t::ForcedTape, on::Bool = true)
+    check(ccall((:moka_forced_adjoint_want_quadratic_drag_gradient, lib), Cint, (Ptr{Cvoid}, Cint), t.handle, on ? 1 : 0), t.state.backend.ctx)
+end
+function forced_quadratic_drag_density!(out::Array{Float64}, t::ForcedTape)
+    check(ccall((:moka_forced_adjoint_quadratic_drag_density_download, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), t.handle, out), t.state.backend.ctx)
+    out
+end
+function forced_quadratic_drag_gradient(t::ForcedTape)
+    out = Ref{Float64}(0.0)
+    check(ccall((:moka_forced_adjoint_quadratic_drag_gradient, lib), Cint, (Ptr{Cvoid}, Ref{Float64}), t.handle, out), t.state.backend.ctx)
+    out[]
+end
 # d J / d nuV (FORCED_GRAD_VISCOSITY) or d J / d r (FORCED_GRAD_DRAG): the host sum of the density
 function forced_gradient(t::ForcedTape, what::Integer)
     out = Ref{Float64}(0.0)
@@ -873,5 +891,7 @@ function forced_gradient(t::ForcedTape, what::Integer)
 end
 # 1 the tile form, 2 the column form of the last transposed vertical pass, 0 none yet
 forced_vmix_path(t::ForcedTape) = Int(ccall((:moka_forced_tape_vmix_path, lib), Cint, (Ptr{Cvoid},), t.handle))
+# the device arrays the tape owns itself (allocated lazily, by what the recorded steps need)
+forced_device_arrays(t::ForcedTape) = Int(ccall((:moka_forced_tape_device_arrays, lib), Int64, (Ptr{Cvoid},), t.handle))
 
 end # module

@@ -1098,15 +1098,17 @@ class ForcedAdjointTape:
 
     _BITS = {"surfaceStress": L.FORCED_GRAD_STRESS, "viscosity": L.FORCED_GRAD_VISCOSITY, "bottomDrag": L.FORCED_GRAD_DRAG}
 
-    def __init__(self, Prog: "PrognosticVars", capacity_steps: int):
+    def __init__(self, Prog: "PrognosticVars", capacity_steps: int, quadratic_drag: bool = False):
         self._state = Prog._state
         self._ctx = self._state.mesh.backend._h
         self._ushape = tuple(Prog.normalVelocity[-1].shape)
         self._hshape = tuple(Prog.layerThickness[-1].shape)
         self._want = 0
         self._want_field = False
+        self._want_cd = False
         self._h = C.c_void_p()
-        L.check(L.lib().moka_forced_tape_create(self._state._h, int(capacity_steps), C.byref(self._h)), self._ctx)
+        create = L.lib().moka_forced_tape_create_quadratic if quadratic_drag else L.lib().moka_forced_tape_create
+        L.check(create(self._state._h, int(capacity_steps), C.byref(self._h)), self._ctx)
         _own(self, L.lib().moka_forced_tape_destroy, self._h, self._state, self._state.mesh, self._state.mesh.backend)
         self._state._dependents.append(weakref.ref(self))
 
@@ -1114,9 +1116,11 @@ class ForcedAdjointTape:
         """One RK4 step of the model (bit for bit moka_step_rk4), recorded."""
         L.check(L.lib().moka_step_rk4_forced_taped(self._h, float(np.asarray(timestep).reshape(-1)[0])), self._ctx)
 
-    def want_gradient(self, stress: bool = False, viscosity: bool = False, drag: bool = False, viscosity_field: bool = False):
+    def want_gradient(self, stress: bool = False, viscosity: bool = False, drag: bool = False, viscosity_field: bool = False,
+                      quadratic_drag: bool = False):
         """The set of parameter gradients the following sweeps accumulate; only while no step is recorded.  `viscosity_field`: the
-        density d J / d f[k,e] of a viscosity per interface and edge, "viscosityField"."""
+        density d J / d f[k,e] of a viscosity per interface and edge, "viscosityField".  `quadratic_drag`: d J / d Cd, "quadraticDrag"
+        (a tape made with quadratic_drag=True only)."""
         want = (L.FORCED_GRAD_STRESS if stress else 0) | (L.FORCED_GRAD_VISCOSITY if viscosity else 0) | (L.FORCED_GRAD_DRAG if drag else 0)
         if want:
             L.check(L.lib().moka_forced_adjoint_want_gradient(self._h, want, 1), self._ctx)
@@ -1126,6 +1130,9 @@ class ForcedAdjointTape:
         if bool(viscosity_field) != self._want_field:
             L.check(L.lib().moka_forced_adjoint_want_viscosity_field_gradient(self._h, 1 if viscosity_field else 0), self._ctx)
             self._want_field = bool(viscosity_field)
+        if bool(quadratic_drag) != self._want_cd:
+            L.check(L.lib().moka_forced_adjoint_want_quadratic_drag_gradient(self._h, 1 if quadratic_drag else 0), self._ctx)
+            self._want_cd = bool(quadratic_drag)
 
     def seed(self, u, h):
         """X := (u, h), (nEdges, K) and (nCells, K) fields: the adjoint of the state after the last recorded step."""
@@ -1138,13 +1145,16 @@ class ForcedAdjointTape:
         L.check(L.lib().moka_forced_adjoint_sweep(self._h), self._ctx)
 
     def density(self, what: str) -> np.ndarray:
-        """The per-edge density of "surfaceStress" (d J / d tau_e itself), "viscosity" or "bottomDrag", caller's edge numbering;
+        """The per-edge density of "surfaceStress" (d J / d tau_e itself), "viscosity", "bottomDrag" or "quadraticDrag", caller's edge numbering;
         "viscosityField": (nEdges, nVertLevels), d J / d f[k,e], rows at and below an edge's deepest interface zero."""
         if what == "viscosityField":
             out = np.empty(self._ushape, dtype=np.float64)
             L.check(L.lib().moka_forced_adjoint_viscosity_field_density_download(self._h, L.f64(out)), self._ctx)
             return out
         out = np.empty(self._ushape[0], dtype=np.float64)
+        if what == "quadraticDrag":
+            L.check(L.lib().moka_forced_adjoint_quadratic_drag_density_download(self._h, L.f64(out)), self._ctx)
+            return out
         L.check(L.lib().moka_forced_adjoint_density_download(self._h, self._BITS[what], L.f64(out)), self._ctx)
         return out
 
@@ -1165,6 +1175,10 @@ class ForcedAdjointTape:
                 out[name] = float(v.value)
         if self._want_field:
             out["viscosityField"] = self.density("viscosityField")
+        if self._want_cd:
+            v = C.c_double()
+            L.check(lib.moka_forced_adjoint_quadratic_drag_gradient(self._h, C.byref(v)), self._ctx)
+            out["quadraticDrag"] = float(v.value)
         return out
 
     def gradient(self, seed=None) -> dict:
@@ -1180,6 +1194,10 @@ class ForcedAdjointTape:
     def vmix_path(self) -> int:
         """moka_forced_tape_vmix_path: 1 the tile form, 2 the column form of the last transposed pass, 0 none yet."""
         return int(L.lib().moka_forced_tape_vmix_path(self._h))
+
+    def device_arrays(self) -> int:
+        """moka_forced_tape_device_arrays: the device arrays the tape owns itself (allocated lazily, by what the steps need)."""
+        return int(L.lib().moka_forced_tape_device_arrays(self._h))
 
     def close(self):
         if self._h:

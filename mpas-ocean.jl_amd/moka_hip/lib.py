@@ -124,6 +124,9 @@ EXPORTS = [
     "moka_forced_adjoint_seed", "moka_forced_adjoint_sweep", "moka_forced_adjoint_download", "moka_forced_adjoint_want_gradient",
     "moka_forced_adjoint_density_download", "moka_forced_adjoint_gradient", "moka_forced_tape_vmix_path",
     "moka_forced_adjoint_want_viscosity_field_gradient", "moka_forced_adjoint_viscosity_field_density_download",
+    "moka_forced_tape_create_quadratic", "moka_forced_adjoint_want_quadratic_drag_gradient",
+    "moka_forced_adjoint_quadratic_drag_density_download", "moka_forced_adjoint_quadratic_drag_gradient",
+    "moka_forced_tape_device_arrays",
 ]
 
 
@@ -321,6 +324,12 @@ def lib():
     L.moka_forced_tape_vmix_path.argtypes = [vp]
     L.moka_forced_adjoint_want_viscosity_field_gradient.argtypes = [vp, C.c_int]
     L.moka_forced_adjoint_viscosity_field_density_download.argtypes = [vp, vp]
+    L.moka_forced_tape_create_quadratic.argtypes = [vp, C.c_int64, C.POINTER(vp)]
+    L.moka_forced_adjoint_want_quadratic_drag_gradient.argtypes = [vp, C.c_int]
+    L.moka_forced_adjoint_quadratic_drag_density_download.argtypes = [vp, vp]
+    L.moka_forced_adjoint_quadratic_drag_gradient.argtypes = [vp, C.POINTER(C.c_double)]
+    L.moka_forced_tape_device_arrays.argtypes = [vp]
+    L.moka_forced_tape_device_arrays.restype = C.c_int64
     L.moka_tape_create.argtypes = [vp, C.c_int64, C.POINTER(vp)]
     L.moka_tape_destroy.argtypes = [vp]
     L.moka_tape_destroy.restype = None

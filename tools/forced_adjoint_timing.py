@@ -5,11 +5,13 @@ per reversed step, in both of its forms, beside the forward pass measured in the
 Per round the legs alternate: kernel variant 0 (tile forms) and 3 (column forms), each with the pass off and on (nuV + drag + stress).
 A leg records `--steps` forced RK4 steps on a moka_forced_tape -- each between two moka_mark: the forward step -- seeds with
 d sum(ssh^2) and sweeps between two marks: the reverse sweep, divided by the steps.  The pass = on - off, forward and reverse alike;
-"grad": the on leg with all three gradients flagged.  Beside it the copy rate of moka_bw_probe and the byte-bound estimates at that
+"grad": the on leg with all three gradients flagged.  --quadratic adds, on a tape of moka_forced_tape_create_quadratic, the legs
+"qd" (on + Cd, with dt Cd sp / hm = 1/2 at the rms speed of the state: the QD instances and the transpose of the bottom-speed
+stencil) and "qdgrad" (qd with the three gradients and D_cd flagged), in both forms; every other leg keeps its plain tape.  Beside it the copy rate of moka_bw_probe and the byte-bound estimates at that
 rate: forward (2 nEdges + nCells) K 8 B (u in and out, the unique bytes of h_new); reverse (4 nEdges + 3 nCells) K 8 B (XU in and out,
 un in, hbar out; the unique bytes of h_new; XH in and out -- hbar read back by the gather is counted as L2 traffic, not HBM).
 
-    python3 tools/forced_adjoint_timing.py [--small] [--rounds R] [--steps N] [--out FILE]"""
+    python3 tools/forced_adjoint_timing.py [--small] [--quadratic] [--rounds R] [--steps N] [--out FILE]"""
 import argparse
 import datetime as dt
 import json
@@ -26,6 +28,7 @@ from moka_hip import meshgen as mg         # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--small", action="store_true")
+ap.add_argument("--quadratic", action="store_true")
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--steps", type=int, default=2)
 ap.add_argument("--out", default=None)
@@ -47,15 +50,25 @@ med = statistics.median
 ALL = {"viscosity": nu, "bottom_drag": drag, "surface_stress": tau}
 LEGS = (("off", 0, {}, False), ("on", 0, ALL, False), ("grad", 0, ALL, True),
         ("off3", 3, {}, False), ("on3", 3, ALL, False), ("grad3", 3, ALL, True))
+if args.quadratic:
+    QD = dict(ALL, quadratic_drag=drag / max(float(np.sqrt(np.mean(u ** 2))), 1e-30))
+    LEGS += (("qd", 0, QD, False), ("qdgrad", 0, QD, True), ("qd3", 3, QD, False), ("qdgrad3", 3, QD, True))
 fwd = {name: [] for name, *_ in LEGS}
 rev = {name: [] for name, *_ in LEGS}
 paths = {}
 for rnd in range(args.rounds + 1):          # round 0 warms up
     for name, variant, kw, grad in LEGS:
         b.set_kernel_variant(variant)
-        mk.set_vertical_mixing(Prog, **kw)
-        tape = mk.ForcedAdjointTape(Prog, args.steps)
-        tape.want_gradient(stress=grad, viscosity=grad, drag=grad)
+        quad = "quadratic_drag" in kw
+        if quad:                                # (a plain tape refuses a state with Cd != 0, and Cd a state with a plain tape)
+            mk.set_vertical_mixing(Prog)
+            tape = mk.ForcedAdjointTape(Prog, args.steps, quadratic_drag=True)
+            mk.set_vertical_mixing(Prog, **kw)
+            tape.want_gradient(stress=grad, viscosity=grad, drag=grad, quadratic_drag=grad)
+        else:
+            mk.set_vertical_mixing(Prog, **kw)
+            tape = mk.ForcedAdjointTape(Prog, args.steps)
+            tape.want_gradient(stress=grad, viscosity=grad, drag=grad)
         for _ in range(args.steps):
             b.synchronize(); b.marks_reset(); b.mark()
             tape.step(dts)
@@ -70,6 +83,8 @@ for rnd in range(args.rounds + 1):          # round 0 warms up
             rev[name].append(list(b.marks_read())[0] / args.steps)
         paths[name] = (mk.momentum_vmix_path(Prog), tape.vmix_path())
         tape.close()
+        if quad:
+            mk.set_vertical_mixing(Prog)
         Prog.normalVelocity[-1].set(u); Prog.layerThickness[-1].set(h); Prog.ssh[-1].set(ssh)      # every leg starts from the same state
         print(f"round {rnd} {name}: forward {fwd[name][-1:]}, reverse {rev[name][-1:]}", flush=True)
 b.set_kernel_variant(0)
@@ -80,13 +95,14 @@ rate = bw.get("copy_GBs") * 1e9
 bound_f = (2 * nE + nC) * K * 8 / rate * 1e3
 bound_r = (4 * nE + 3 * nC) * K * 8 / rate * 1e3
 rows = []
-for form, off, legs in (("tile", "off", ("on", "grad")), ("column", "off3", ("on3", "grad3"))):
+extra = ("qd", "qdgrad") if args.quadratic else ()
+for form, off, legs in (("tile", "off", ("on", "grad") + extra), ("column", "off3", ("on3", "grad3") + tuple(x + "3" for x in extra))):
     for leg in legs:
         pf, pr = med(fwd[leg]) - med(fwd[off]), med(rev[leg]) - med(rev[off])
         rows.append({"form": form, "paths": paths[leg], "leg": leg.rstrip("3"), "forward_pass_ms": pf, "reverse_pass_ms": pr,
                      "reverse_over_forward": pr / pf if pf > 0 else None, "byte_bound_over_reverse": bound_r / pr if pr > 0 else None,
                      "forward_step_off_on": (med(fwd[off]), med(fwd[leg])), "reverse_step_off_on": (med(rev[off]), med(rev[leg])),
-                     "reverse_on_min_max": (min(rev[leg]), max(rev[leg]))})
+                     "reverse_on_min_max": (min(rev[leg]), max(rev[leg])), "reverse_off_min_max": (min(rev[off]), max(rev[off]))})
 result = {"cells": nC, "edges": nE, "K": K, "rounds": args.rounds, "steps": args.steps, "copy_GBs": bw.get("copy_GBs"),
           "byte_bound_forward_ms": bound_f, "byte_bound_reverse_ms": bound_r, "rows": rows}
 print(json.dumps(result), flush=True)
