@@ -439,11 +439,25 @@ int moka_set_kernel_variant(moka_ctx *ctx, int variant);
  * tolerance against the reference form).  With the nonlinear terms on: the same where the stage launch is the default patch
  * kernel (even 34 <= nVertLevels <= 64; twin oracle_step_rk4_nonlinear_s13).  Distributed, taped and fp32-storage steps keep
  * the reference's form.  moka_state_rk4_streams tells which form the next moka_step_rk4 of a state takes.
- * Accepted values (anything else, and a key outside 1-9, is MOKA_ERR_ARG and changes nothing): key 1 a mask of modes 0-6, 10 and
- * 11; key 8 a mask of modes 0-3 and 7-9 plus bit 16 (test hook: small launches too); key 5 0-3; key 6 >= 0; keys 2, 3, 4, 7 and
- * 9 0 or 1.  moka_get_tuning returns the value last set (or the default). */
+ * key 12 (keys 10 and 11 do not exist): 1 (default) = RK4 stage 1 hands New to stage 2 as one checked byte per value instead of the
+ * value; 0 = New travels in full.  Stage 1 forms Provis' = C + a t and New = C + b t from one tendency, so stage 2 can rebuild New
+ * from the own rows of Curr and Provis it reads anyway, C + (P - C) * (b / a), corrected by the stored distance of the bit patterns;
+ * a value the byte cannot carry is an escape and travels in the New array as before.  Bit for bit the same step with 7/8 of a state
+ * stream less in each of the two stages; Float64 states in the 16-stream form without the nonlinear terms whose stage launches all
+ * run through the default stage kernel, whole and partitioned meshes, taped steps included.  The pair mask of key 8 applies to the
+ * two launches as to modes 1 and 2.
+ * Accepted values (anything else, and a key outside 1-9 and 12, is MOKA_ERR_ARG and changes nothing): key 1 a mask of modes 0-6, 10 and
+ * 11; key 8 a mask of modes 0-3 and 7-9 plus bit 16 (test hook: small launches too); key 5 0-3; key 6 >= 0; keys 2, 3, 4, 7, 9 and
+ * 12 0 or 1.  moka_get_tuning returns the value last set (or the default). */
 int moka_set_tuning(int key, int value);
 int moka_get_tuning(int key, int *value);
+/* The codec of key 12 as the host runs it, over n values (no GPU is touched; a test aid): code_out[i] is the byte stage 1 would
+ * store for New N[i] given Curr C[i], Provis' P[i] and rho = b / a (-128 = escape), decoded_out[i] what stage 2 would rebuild (an
+ * escape: N[i], which it reads from the New array). */
+int moka_rk_handoff_codec(const double *C, const double *P, const double *N, double rho, int64_t n, int8_t *code_out, double *decoded_out);
+/* How many escapes the codes of the last RK4 step hold, over all levels of the state's cells / edges (a test aid: copies the code
+ * arrays to the host).  MOKA_ERR_UNSUPPORTED when that step did not hand New over as codes. */
+int moka_state_rk_handoff_escapes(moka_state *st, int64_t *cells, int64_t *edges);
 /* 13 = the next moka_step_rk4 / moka_run of this state runs in the 13-stream form (key 7 set and the state qualifies), 16 = the
  * reference's running sum (time_integration.jl:134-135); 0 for NULL. */
 int moka_state_rk4_streams(const moka_state *st);

@@ -28,6 +28,7 @@ struct TuningEntry {
     int mask, max;
     std::atomic<int> value;
     TuningEntry(int def, int m, int x) : mask(m), max(x), value(def) {}
+    bool exists() const { return mask != 0 || max >= 0; }
     bool accepts(int v) const { return mask ? (v & ~mask) == 0 : v >= 0 && v <= max; }
 };
 static TuningEntry g_tuning[] = {
@@ -41,6 +42,9 @@ static TuningEntry g_tuning[] = {
     {0, 0, 1},                                               // 7 TUNE_RK13
     {1 << 0 | 1 << 1 | 1 << 7, 0xf | 7 << 7 | 1 << 16, 0},   // 8 TUNE_PAIR: pair instances 0-3, 7-9; bit 16 test hook (launch_rec2c_pair)
     {1, 0, 1},                                               // 9 TUNE_FE_LEAN_INST
+    {0, 0, -1},                                              // (no key 10)
+    {0, 0, -1},                                              // (no key 11)
+    {1, 0, 1},                                               // 12 TUNE_RK_HANDOFF
 };
 constexpr int N_TUNING = sizeof(g_tuning) / sizeof(g_tuning[0]);
 
@@ -404,7 +408,7 @@ int moka_bw_probe_gather_big(moka_ctx *ctx, int64_t bytes, int iters, double *gb
 
 int moka_set_tuning(int key, int value)
 {
-    if (key < 1 || key >= N_TUNING) return fail(nullptr, MOKA_ERR_ARG, "unknown tuning key");
+    if (key < 1 || key >= N_TUNING || !g_tuning[key].exists()) return fail(nullptr, MOKA_ERR_ARG, "unknown tuning key");
     if (!g_tuning[key].accepts(value)) return fail(nullptr, MOKA_ERR_ARG, "tuning key " + std::to_string(key) + ": value names no kernel instance");
     g_tuning[key].value.store(value);
     return MOKA_OK;
@@ -413,7 +417,7 @@ int moka_set_tuning(int key, int value)
 int moka_get_tuning(int key, int *value)
 {
     if (!value) return fail(nullptr, MOKA_ERR_ARG, "value is NULL");
-    if (key < 1 || key >= N_TUNING) return fail(nullptr, MOKA_ERR_ARG, "unknown tuning key");
+    if (key < 1 || key >= N_TUNING || !g_tuning[key].exists()) return fail(nullptr, MOKA_ERR_ARG, "unknown tuning key");
     *value = g_tuning[key].value.load();
     return MOKA_OK;
 }

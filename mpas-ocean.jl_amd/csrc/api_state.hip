@@ -12,6 +12,7 @@
 #include <utility>
 #include <vector>
 
+#include "kernels_common.hpp"
 #include "state.hpp"
 #include "tapes.hpp"
 
@@ -45,10 +46,17 @@ int ensure_rk_bufs(moka_state *st)
         if (rc == MOKA_OK) rc = st->mem.alloc(&r.h, (size_t)p.K * p.nC, sb);
         if (rc == MOKA_OK) rc = st->mem.alloc(&r.ssh, (size_t)p.nC, sb);
     }
+    // the code arrays of the stage 1 -> 2 hand-off (rk_handoff_usable) come with them, behind them: Float64 states only
+    signed char *codeU = nullptr, *codeH = nullptr;
+    if (!st->f32) {
+        if (rc == MOKA_OK) rc = st->mem.alloc(&codeU, (size_t)p.K * p.nE);
+        if (rc == MOKA_OK) rc = st->mem.alloc(&codeH, (size_t)p.K * p.nC);
+    }
     if (rc != MOKA_OK) {                     // free what a partial failure left behind: a later call starts over
         st->mem.rollback(mark);
         return rc;
     }
+    st->hoCodeU = codeU; st->hoCodeH = codeH;
     st->rk[0] = tmp[0]; st->rk[1] = tmp[1];
     st->phys[2] = tmp[0]; st->phys[3] = tmp[1];
     return MOKA_OK;
@@ -184,6 +192,7 @@ hipError_t run_stage(moka_state *st, const StageArgs &g_in, int pBegin, int pCou
         }
     }
     if (dev.nPatches <= 0) return hipSuccess;
+    if ((g.codeU || g.codeH) && (st->nonlinear || st->f32)) return hipErrorNotSupported;   // (rk_handoff_usable saw to it)
     if (st->nonlinear) {
         // vector-invariant form: potential vorticity at vertices -> edges, kinetic energy at cells, thickness flux at edges
         // (whole mesh: the stencil of the edge pass reaches two cells deep), then the generic stage kernel's nonlinear twin
@@ -227,6 +236,7 @@ hipError_t run_stage(moka_state *st, const StageArgs &g_in, int pBegin, int pCou
         hipError_t e = launch_stage_rec2c(dev, g, s);
         if (e != hipErrorNotSupported) return e;
     }
+    if (g.codeU || g.codeH) return hipErrorNotSupported;      // the hand-off exists in that kernel only (rk_handoff_usable saw to it)
     if (v != 3 && m->lpc == 64 && m->colOk) return launch_stage_col(dev, g, s);
     return launch_stage(dev, g, m->lpc, s);
 }
@@ -381,10 +391,16 @@ StageArgs rk4_stage_args(moka_state *st, int s, double dt, const double *ssh0)
     if (s == 1) {          // Provis == Curr == A;  New = Curr + b1*k1 -> B;  Provis' = Curr + a1*k1 -> R1
         g.pu = A.u; g.ph = A.h; g.ssh = ssh0;
         g.pu_out = R1.u; g.ph_out = R1.h; g.ssh_out = R1.ssh; g.a = a[0];
+        // New as one-byte codes beside B (escapes in B itself): every stage-1 launch of the step, and then its stage-2 launches
+        st->hoLive = st->hoRan = rk_handoff_usable(st);
+        st->hoRho = a[0] != 0.0 ? b[0] / a[0] : 0.0;
+        if (st->hoLive) { g.codeU = st->hoCodeU; g.codeH = st->hoCodeH; g.rho = st->hoRho; }
     } else if (s == 2) {   // Provis = R1 -> R2
         g.pu = R1.u; g.ph = R1.h; g.ssh = R1.ssh; g.cu = A.u; g.ch = A.h; g.nu_in = B.u; g.nh_in = B.h;
         g.pu_out = R2.u; g.ph_out = R2.h; g.ssh_out = R2.ssh; g.a = a[1];
+        if (st->hoLive) { g.codeU = st->hoCodeU; g.codeH = st->hoCodeH; g.rho = st->hoRho; }   // what stage 1 of this step stored
     } else if (s == 3) {   // Provis = R2 -> R1
+        st->hoLive = false;
         g.pu = R2.u; g.ph = R2.h; g.ssh = R2.ssh; g.cu = A.u; g.ch = A.h; g.nu_in = B.u; g.nh_in = B.h;
         g.pu_out = R1.u; g.ph_out = R1.h; g.ssh_out = R1.ssh; g.a = a[2];
     } else {               // Provis = R1; New += b4*k4; ssh of New
@@ -444,6 +460,23 @@ bool rk13_usable(const moka_state *st)
     if (st->nonlinear)             // nonlinear terms: k_stage_nl5 carries the form (StageArgs.rkMode 9), the plainer kernels do not
         return nl_stage_is_nl5(mm->dev, mm->lpc, mm->plan.ldsOk, nl_form(st->ctx));
     return default_stage_kernels(st) && rec2c_supported(launch_bounds(mm));
+}
+
+// ---- New from RK4 stage 1 to stage 2 as one-byte codes (moka_set_tuning key 12) -------------------------------------------------
+// Only stage 1 starts from Provis == Curr == New, so its two results P = C + a t and N = C + b t (time_integration.jl:124-125, 134-135)
+// determine each other up to a few units in the last place: stage 1 stores a checked signed byte per value instead of N (an escape
+// keeps N itself in the New array), stage 2 rebuilds N from the own rows of Curr and Provis it reads anyway (rk_handoff_* in
+// kernels_common.hpp; k_stage_rec2c modes 12 / 13) and stores New in full.  Bit for bit: 7/8 of a state stream less in each of the
+// two stages.  On only where BOTH stages run through launch_stage_rec2c, whole-mesh launches and patch ranges alike (own rows only):
+// a Float64 state, the reference's 16-stream form, no nonlinear terms, the default kernel choice, a mesh that kernel carries in
+// every launch shape.  Nothing reads New between the two stages: the tracer stage, the tapes' recording copies and the halo push
+// take Provis (New only behind stage 4).
+bool rk_handoff_usable(const moka_state *st)
+{
+    if (!tuning(TUNE_RK_HANDOFF) || st->f32 || st->nonlinear || !st->hoCodeU || !st->hoCodeH) return false;
+    if (rk13_usable(st)) return false;
+    const moka_mesh *mm = st->mesh;
+    return default_stage_kernels(st) && rec2c_supported(launch_bounds(mm)) && rec2c_supported(mm->dev);
 }
 
 StageArgs rk13_stage_args(moka_state *st, int s, double dt, const double *ssh0)
@@ -550,6 +583,7 @@ int step_rk4(moka_state *st, double dt, moka_tracer_tape *rec)
         return hipEventRecord(c->evPool[c->evUsed++], c->stream);
     };
     const bool s13 = rk13_usable(st);
+    if (s13) st->hoLive = st->hoRan = false;      // (no New travels through stages 1-3 of that form: nothing to hand over)
     for (int s = 1; s <= 4; ++s) {
         if (timed) HIPCHK(c, stamp());
         const StageArgs g = s13 ? rk13_stage_args(st, s, dt, ssh0) : rk4_stage_args(st, s, dt, ssh0);
@@ -823,6 +857,39 @@ int moka_step_fe(moka_state *st, double dt, int flags)
 int moka_fe_lazy_pending(const moka_state *st) { return st && st->feLazy ? 1 : 0; }
 
 int moka_state_rk4_streams(const moka_state *st) { return !st ? 0 : rk13_usable(st) ? 13 : 16; }
+
+// the host build of the codec the stage kernels run (kernels_common.hpp, under the library's -ffp-contract=off): no GPU is touched
+int moka_rk_handoff_codec(const double *C, const double *P, const double *N, double rho, int64_t n, int8_t *code_out, double *decoded_out)
+{
+    if (n < 0 || (n > 0 && (!C || !P || !N || !code_out || !decoded_out))) return fail(nullptr, MOKA_ERR_ARG, "moka_rk_handoff_codec: NULL argument");
+    for (int64_t i = 0; i < n; ++i) {
+        const int8_t c = moka::rk_handoff_encode(C[i], P[i], N[i], rho);
+        code_out[i] = c;
+        decoded_out[i] = c == (int8_t)moka::RK_HANDOFF_ESCAPE ? N[i] : moka::rk_handoff_decode(C[i], P[i], (int)c, rho);
+    }
+    return MOKA_OK;
+}
+
+// a test aid, off the step path: the code arrays of the last hand-off step, copied to the host and counted
+int moka_state_rk_handoff_escapes(moka_state *st, int64_t *cells, int64_t *edges)
+{
+    if (!st || !cells || !edges) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    *cells = *edges = 0;
+    if (!st->hoRan || !st->hoCodeU || !st->hoCodeH)
+        return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "the last RK4 step of this state did not hand New over as codes (moka_set_tuning key 12)");
+    HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
+    const Plan &p = st->mesh->plan;
+    std::vector<signed char> host;
+    auto count = [&](const signed char *dev, size_t n, int64_t *out) -> int {
+        host.resize(n);
+        HIPCHK(st->ctx, hipMemcpyAsync(host.data(), dev, n, hipMemcpyDeviceToHost, st->ctx->stream));
+        HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));
+        *out = (int64_t)std::count(host.begin(), host.end(), (signed char)moka::RK_HANDOFF_ESCAPE);
+        return MOKA_OK;
+    };
+    if (int rc = count(st->hoCodeH, (size_t)p.K * p.nC, cells)) return rc;
+    return count(st->hoCodeU, (size_t)p.K * p.nE, edges);
+}
 
 int moka_step_rk4(moka_state *st, double dt)
 {

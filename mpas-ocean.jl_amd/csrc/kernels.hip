@@ -33,9 +33,15 @@ namespace moka {
 // ------------------------------------------------------------------------------------------------
 // (MODE 7 / 8 / 9, the 13-stream RK4 form: rk13_combine in kernels_common.hpp -- the nonlinear stage kernel uses the same expression)
 
-template <int ME, int ME2, int MODE, int NT = BLOCK>
+// MODE_ 12 / 13: RK4 stages 1 / 2 (modes 1 / 2) with New handed over as one-byte codes (rk_handoff_* in kernels_common.hpp).  12 stores
+// a lane's two codes (2 bytes at row * K + 2 l of a.codeH / a.codeU) instead of its 16 bytes of New, which go to their ordinary place
+// only where a code is an escape; 13 loads the codes instead of the own row of New, rebuilds it from the own rows of Curr and Provis
+// it holds anyway, and loads New only for the escaped lanes of a wave that has any.  Everything else is modes 1 / 2; no LDS is added.
+template <int ME, int ME2, int MODE_, int NT = BLOCK>
 __global__ __launch_bounds__(NT) void k_stage_rec2c(const ColMesh m, const StageArgs a, int maxOwnE, int maxOwnC)
 {
+    constexpr bool HO1 = MODE_ == 12, HO2 = MODE_ == 13;
+    constexpr int MODE = HO1 ? 1 : HO2 ? 2 : MODE_;
     extern __shared__ __align__(16) unsigned char smem[];
     const int pl_ = patch_of_block(m.nPatches);
     if (pl_ >= m.nPatches) return;
@@ -176,15 +182,41 @@ __global__ __launch_bounds__(NT) void k_stage_rec2c(const ColMesh m, const Stage
     double pS = 0.0;
     // `pend` is false only in a group's first iteration; the loops carry `#pragma nounroll` so that the compiler does not peel
     // a copy of the whole loop body for it (a third more code, more registers)
-    uint32_t pOff = 0;
+    uint32_t pOff = 0, pCode = 0;
     int pC = 0;
     bool pend = false;
+    // the hand-off's loads and stores: a lane's two codes are the 2 bytes at (16-byte offset of its values) / 8
+    auto code_store = [&](signed char *base, uint32_t off, uint32_t code) {
+        *reinterpret_cast<uint16_t *>(base + (off >> 3)) = (uint16_t)code;
+    };
+    auto code_load = [&](const signed char *base, uint32_t off) -> uint32_t {
+        return *reinterpret_cast<const uint16_t *>(base + (off >> 3));
+    };
+    // stage 1: the codes of (N.x, N.y) given the own values of Curr and of the new provisional state
+    auto encode2 = [&](double2 C, double2 P, double2 N) -> uint32_t {
+        return rk_handoff_pack(rk_handoff_encode(C.x, P.x, N.x, a.rho), rk_handoff_encode(C.y, P.y, N.y, a.rho));
+    };
+    // stage 2: New from the codes; escaped lanes (if the wave has any) load it from its ordinary place
+    auto decode2 = [&](uint32_t code, double2 C, double2 P, const double *nin, uint32_t own) -> double2 {
+        const bool esc = act && (code & 0xffu) == 0x80u;
+        double2 n = make_double2(rk_handoff_decode(C.x, P.x, (int)(int8_t)(code & 0xffu), a.rho),
+                                 rk_handoff_decode(C.y, P.y, (int)(int8_t)((code >> 8) & 0xffu), a.rho));
+        if (__builtin_amdgcn_ballot_w64(esc) != 0) {
+            if (esc) n = gload2(nin, own);
+        }
+        return n;
+    };
     auto flush_cell = [&]() {
         if (act) {
             if constexpr (MODE == 0) gstore2o(a.tendH, pOff, pA);
             if constexpr (MODE == 1 || MODE == 2) {
                 gstore2o(a.ph_out, pOff, pA);
-                gstore2o(a.nh_out, pOff, pB);
+                if constexpr (HO1) {
+                    if (pCode == 0x8080u) gstore2o(a.nh_out, pOff, pB);
+                    code_store(a.codeH, pOff, pCode);
+                } else {
+                    gstore2o(a.nh_out, pOff, pB);
+                }
             }
             if constexpr (MODE == 3 || MODE == 9) gstore2o(a.nh_out, pOff, pB);
             if constexpr (MODE == 7 || MODE == 8) gstore2o(a.ph_out, pOff, pA);
@@ -208,6 +240,7 @@ __global__ __launch_bounds__(NT) void k_stage_rec2c(const ColMesh m, const Stage
         const double invA = L.invA[ci];
         const uint32_t own = (uint32_t)c * rowB + voff;
         double2 hc = make_double2(0.0, 0.0), uv[ME], hv[ME], cur = hc, nin = hc, hpc = hc, q3 = hc;
+        uint32_t ncode = 0;
         if (act) {
             bool cached[ME];
             uint32_t ad[ME], goff[ME];
@@ -229,12 +262,14 @@ __global__ __launch_bounds__(NT) void k_stage_rec2c(const ColMesh m, const Stage
                 if (!cached[i]) uv[i] = glb_row2(puG + goff[i]);
             }
             if constexpr (MODE == 2 || MODE == 8 || MODE == 9) cur = gload2(a.ch, own);
-            if constexpr (MODE == 2 || MODE == 3 || MODE == 9) nin = gload2(a.nh_in, own);     // (9: the own row of P2)
+            if constexpr (HO2) ncode = code_load(a.codeH, own);
+            else if constexpr (MODE == 2 || MODE == 3 || MODE == 9) nin = gload2(a.nh_in, own);     // (9: the own row of P2)
             if constexpr (MODE == 9) q3 = gload2(a.q3h, own);                                   // ... and of P3
         }
         double area = 1.0;
         if constexpr (FE && !LEAN) if (a.div) area = a.areaCell[c];
         __builtin_amdgcn_s_waitcnt(0x0F70);                            // vmcnt(0): this iteration's loads (needed next anyway) ...
+        if constexpr (HO2) nin = decode2(ncode, cur, hc, a.nh_in, own);   // (the own row of Provis is hc)
         if (pend) flush_cell();                                        // ... so that the stores queue up behind them, not ahead
         double2 t = make_double2(0.0, 0.0);
         // regular entity (every slot valid, every level active) in BOTH half-waves: no per-slot masks (wave-uniform branch)
@@ -283,6 +318,7 @@ __global__ __launch_bounds__(NT) void k_stage_rec2c(const ColMesh m, const Stage
                 hs = make_double2(hcur.x + a.a * t.x, hcur.y + a.a * t.y);                    // time_integration.jl:125
                 pA = hs;
                 pB = make_double2(nb.x + a.b * t.x, nb.y + a.b * t.y);                        // :135
+                if constexpr (HO1) pCode = encode2(hc, pA, pB);
             }
             if constexpr (MODE == 3) {
                 hs = make_double2(nin.x + a.b * t.x, nin.y + a.b * t.y);
@@ -325,7 +361,12 @@ __global__ __launch_bounds__(NT) void k_stage_rec2c(const ColMesh m, const Stage
             if constexpr (MODE == 0) gstore2o(a.tendU, pOff, pA);
             if constexpr (MODE == 1 || MODE == 2) {
                 gstore2o(a.pu_out, pOff, pA);
-                gstore2o(a.nu_out, pOff, pB);
+                if constexpr (HO1) {
+                    if (pCode == 0x8080u) gstore2o(a.nu_out, pOff, pB);
+                    code_store(a.codeU, pOff, pCode);
+                } else {
+                    gstore2o(a.nu_out, pOff, pB);
+                }
             }
             if constexpr (MODE == 3 || MODE == 9) gstore2o(a.nu_out, pOff, pB);
             if constexpr (MODE == 7 || MODE == 8) gstore2o(a.pu_out, pOff, pA);
@@ -352,6 +393,7 @@ __global__ __launch_bounds__(NT) void k_stage_rec2c(const ColMesh m, const Stage
         const uint32_t own = (uint32_t)e * rowB + voff;
         double sv = 0.0;
         double2 uv[ME2], cur = make_double2(0.0, 0.0), nin = cur, hx = cur, hy = cur, hEo = cur, q3 = cur;
+        uint32_t ncode = 0;
         if (act) {
             bool cached[ME2];
             uint32_t ad[ME2], goff[ME2];
@@ -370,7 +412,8 @@ __global__ __launch_bounds__(NT) void k_stage_rec2c(const ColMesh m, const Stage
                 if (!cached[i]) uv[i] = glb_row2(puG + goff[i]);
             }
             if constexpr (MODE == 2 || MODE == 8 || MODE == 9) cur = gload2(a.cu, own);
-            if constexpr (MODE == 2 || MODE == 3 || MODE == 9) nin = gload2(a.nu_in, own);
+            if constexpr (HO2) ncode = code_load(a.codeU, own);
+            else if constexpr (MODE == 2 || MODE == 3 || MODE == 9) nin = gload2(a.nu_in, own);
             if constexpr (MODE == 9) q3 = gload2(a.q3u, own);
             if constexpr (FE && !LEAN) {
                 // the edge's own diagnostics: loaded for only when they are stored (a lean step stores neither)
@@ -389,6 +432,7 @@ __global__ __launch_bounds__(NT) void k_stage_rec2c(const ColMesh m, const Stage
         }
         if (l < 2) sv = a.ssh[r[ME2 + l]];                             // ssh of cellsOnEdge[l]: after the gathers in the queue
         __builtin_amdgcn_s_waitcnt(0x0F70);                            // vmcnt(0): this iteration's loads (needed next anyway) ...
+        if constexpr (HO2) nin = decode2(ncode, cur, ubuf2[(size_t)ei * K2 + (act ? l : 0)], a.nu_in, own);   // (the own row of Provis is in the cache)
         if (pend) flush_edge();                                        // ... so that the stores queue up behind them, not ahead
         const double ds = __shfl(sv, 1, 32) - __shfl(sv, 0, 32);       // ssh[c2] - ssh[c1]
         const bool plain = __builtin_amdgcn_ballot_w64(!(mask == (1u << ME2) - 1u && mlt >= K)) == 0;   // wave-uniform
@@ -419,6 +463,7 @@ __global__ __launch_bounds__(NT) void k_stage_rec2c(const ColMesh m, const Stage
                 const double2 up = ubuf2[(size_t)ei * K2 + l];          // own row is in the cache
                 pA = make_double2(up.x + a.a * t.x, up.y + a.a * t.y);  // time_integration.jl:124
                 pB = make_double2(up.x + a.b * t.x, up.y + a.b * t.y);  // :134
+                if constexpr (HO1) pCode = encode2(up, pA, pB);
             }
             if constexpr (MODE == 2) {
                 pA = make_double2(cur.x + a.a * t.x, cur.y + a.a * t.y);
@@ -1511,6 +1556,8 @@ static bool launch_rec2c_nt(const ColMesh &m, const StageArgs &a, int mode, dim3
         case 9: hipLaunchKernelGGL((k_stage_rec2c<ME, ME2, 9, NT>), g, b, lds, s, m, a, mE, mC); return true;
         case 10: hipLaunchKernelGGL((k_stage_rec2c<ME, ME2, 10, NT>), g, b, lds, s, m, a, mE, mC); return true;
         case 11: hipLaunchKernelGGL((k_stage_rec2c<ME, ME2, 11, NT>), g, b, lds, s, m, a, mE, mC); return true;
+        case 12: hipLaunchKernelGGL((k_stage_rec2c<ME, ME2, 12, NT>), g, b, lds, s, m, a, mE, mC); return true;
+        case 13: hipLaunchKernelGGL((k_stage_rec2c<ME, ME2, 13, NT>), g, b, lds, s, m, a, mE, mC); return true;
     }
     return false;
 }
@@ -1557,7 +1604,7 @@ static hipError_t launch_rec2c_pair(const ColMesh &m, const StageArgs &a, int mo
         hipLaunchKernelGGL((k_stage_rec2c<ME, ME2, M, 512>), g, b, lds, s, m, a, mE, mC);                               \
         return hipGetLastError();
     switch (mode) {
-        PAIR_CASE(0) PAIR_CASE(1) PAIR_CASE(2) PAIR_CASE(3) PAIR_CASE(7) PAIR_CASE(8) PAIR_CASE(9)
+        PAIR_CASE(0) PAIR_CASE(1) PAIR_CASE(2) PAIR_CASE(3) PAIR_CASE(7) PAIR_CASE(8) PAIR_CASE(9) PAIR_CASE(12) PAIR_CASE(13)
     }
 #undef PAIR_CASE
     return hipErrorNotSupported;
@@ -1617,7 +1664,8 @@ hipError_t launch_stage_rec2c(const MeshDev &md, const StageArgs &a, hipStream_t
     // without a tail patch, and when two such workgroups fit a CU's LDS (two per CU = the 16 waves of four small workgroups).
     // (bit 16 of the mask is a test hook: small launches too)
     const int pair = tuning(TUNE_PAIR);
-    if (((pair >> mode) & 1) && md.tailPatch < 0 && (md.nPatches >= 4096 || ((pair >> 16) & 1)) && md.nPatches >= 2 &&
+    const int pairBit = mode == 12 ? 1 : mode == 13 ? 2 : mode;     // the hand-off instances pair where modes 1 / 2 do
+    if (((pair >> pairBit) & 1) && md.tailPatch < 0 && (md.nPatches >= 4096 || ((pair >> 16) & 1)) && md.nPatches >= 2 &&
         md.ME == 6 && md.ME2 == 10) {
         MeshDev two = md;
         two.maxOwnE = 2 * md.maxOwnE; two.maxOwnC = 2 * md.maxOwnC;

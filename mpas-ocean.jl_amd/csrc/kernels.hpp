@@ -40,6 +40,11 @@ struct StageArgs {
     // nu_in/nh_in: every entity reads its own row of P2 before it writes there), ssh_out = ssh of New, b = dt/6
     int rkMode;
     const double *q3u, *q3h;
+    // RK4 stage 1 -> stage 2 hand-off of New as one-byte codes (k_stage_rec2c modes 12 / 13; rk_handoff_* in kernels_common.hpp;
+    // mk::rk_handoff_usable): (K, nE) / (K, nC) bytes beside New, NULL = New travels in full.  rho = b1 / a1 of the step, the same
+    // double in both launches.
+    signed char *codeU, *codeH;
+    double rho;
 };
 
 // the slice of MeshDev the column kernel reads (kept small: kernel arguments live in SGPRs)
@@ -114,6 +119,7 @@ enum TuningKey : int {
     TUNE_RK13 = 7,           // 1 = RK4 steps in the 13-stream form where mk::rk13_usable (NOT result-neutral)
     TUNE_PAIR = 8,           // bit mask: modes of the Float64 stage kernel that take two patches per 512-thread workgroup
     TUNE_FE_LEAN_INST = 9,   // 0 = lean Forward-Euler launches through the general instances (modes 5 / 6) instead of 10 / 11
+    TUNE_RK_HANDOFF = 12,    // 1 = RK4 stage 1 hands New to stage 2 as one-byte codes where mk::rk_handoff_usable (10, 11: no such keys)
 };
 int tuning(TuningKey key);
 

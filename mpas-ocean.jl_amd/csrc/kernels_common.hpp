@@ -257,8 +257,9 @@ inline int colp_mode(const StageArgs &a)
     const bool outs = a.pu_out || a.ph_out || a.nu_out || a.nh_out;
     if (a.tendU && a.tendH && !outs && !a.ssh_out) return 0;
     if (a.tendU || a.tendH) return -1;
-    if (!a.cu && !a.ch && !a.nu_in && !a.nh_in && a.pu_out && a.ph_out && a.nu_out && a.nh_out && a.ssh_out) return 1;
-    if (a.cu && a.ch && a.nu_in && a.nh_in && a.pu_out && a.ph_out && a.nu_out && a.nh_out && a.ssh_out) return 2;
+    const bool ho = a.codeU && a.codeH;      // New of stage 1 travels to stage 2 as codes: modes 12 / 13 (k_stage_rec2c only)
+    if (!a.cu && !a.ch && !a.nu_in && !a.nh_in && a.pu_out && a.ph_out && a.nu_out && a.nh_out && a.ssh_out) return ho ? 12 : 1;
+    if (a.cu && a.ch && a.nu_in && a.nh_in && a.pu_out && a.ph_out && a.nu_out && a.nh_out && a.ssh_out) return ho ? 13 : 2;
     if (a.nu_in && a.nh_in && !a.pu_out && !a.ph_out && a.nu_out && a.nh_out && a.ssh_out) return 3;
     return -1;
 }
@@ -287,6 +288,41 @@ __device__ __forceinline__ double rk13_combine(double c, double p2, double p3, d
     const double d2 = p2 - c, d3 = p3 - c, d4 = p4 - c;
     const double acc = (d2 + (d3 + d3)) + d4;
     return (c + acc * (1.0 / 3.0)) + b4 * t;
+}
+
+// ---- RK4 stage 1 -> stage 2 hand-off of New (k_stage_rec2c modes 12 / 13; the host build: moka_rk_handoff_codec) ----
+// Stage 1 forms P = C + a t and N = C + b t from one tendency; stage 2 holds C and P anyway, and C + (P - C) * (b / a) lands within a
+// few units in the last place of N.  What travels is the distance of the two bit patterns as a signed byte, or RK_HANDOFF_ESCAPE:
+// the value itself then sits at its place in the New array.  The encoder decodes its own code and escapes unless that gives N
+// back bit for bit (and when the prediction is a NaN, whose payload is the one thing two launches might form differently), so
+// nothing here rests on a claim about rounding: cancellation, dt = 0 (rho = 0), infinities and subnormals round-trip or escape.
+constexpr int RK_HANDOFF_ESCAPE = -128;
+
+__host__ __device__ __forceinline__ double rk_handoff_predict(double C, double P, double rho)
+{
+    return C + (P - C) * rho;
+}
+
+__host__ __device__ __forceinline__ double rk_handoff_decode(double C, double P, int code, double rho)
+{
+    const double pred = rk_handoff_predict(C, P, rho);
+    return __builtin_bit_cast(double, (uint64_t)(__builtin_bit_cast(uint64_t, pred) + (uint64_t)(int64_t)code));
+}
+
+__host__ __device__ __forceinline__ int8_t rk_handoff_encode(double C, double P, double N, double rho)
+{
+    const double pred = rk_handoff_predict(C, P, rho);
+    const int64_t r = (int64_t)(__builtin_bit_cast(uint64_t, N) - __builtin_bit_cast(uint64_t, pred));
+    if (pred != pred || r < -127 || r > 127) return (int8_t)RK_HANDOFF_ESCAPE;
+    const double back = rk_handoff_decode(C, P, (int)r, rho);
+    return __builtin_bit_cast(uint64_t, back) == __builtin_bit_cast(uint64_t, N) ? (int8_t)r : (int8_t)RK_HANDOFF_ESCAPE;
+}
+
+// a lane's two codes as the 2 bytes it stores (level k0 in the low byte); one escape makes both escapes
+__host__ __device__ __forceinline__ uint32_t rk_handoff_pack(int cx, int cy)
+{
+    if (cx == RK_HANDOFF_ESCAPE || cy == RK_HANDOFF_ESCAPE) return 0x8080u;
+    return ((uint32_t)cx & 0xffu) | (((uint32_t)cy & 0xffu) << 8);
 }
 
 // lanes-per-column dispatch of the generic column kernels (LPC = smallest power of two >= nVertLevels, capped at 64)

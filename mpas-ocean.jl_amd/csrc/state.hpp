@@ -159,6 +159,13 @@ struct moka_state {
     double *hEdge[2] = {nullptr, nullptr};   // [0] is Diag.layerThicknessEdge, [1] the write target of the next step
     double *F = nullptr, *div = nullptr, *vort = nullptr, *tendU = nullptr, *tendH = nullptr;
     LevelBufs rk[2];                  // RK4 provisional states (lazily allocated)
+    // RK4 stage 1 -> stage 2 hand-off of New as one-byte codes (mk::rk_handoff_usable; Float64 states): (K, nE) and (K, nC) bytes,
+    // allocated with rk[].  hoLive: the stage-1 launches of the step under way stored codes, formed with hoRho (b1 / a1 of that step),
+    // and its stage-2 launches read them; cleared when stage 3 begins.  hoRan: the same of the last step begun, kept for
+    // moka_state_rk_handoff_escapes.
+    signed char *hoCodeU = nullptr, *hoCodeH = nullptr;
+    bool hoLive = false, hoRan = false;
+    double hoRho = 0.0;
     LevelBufs spare;                  // third time-level set of the tuned Forward-Euler step (lazily allocated): the step writes
                                       // the new level here, so the PREVIOUS level's layerThickness stays readable while it runs
                                       // (k_stage_rec2c mode 6), and the three sets rotate: prev <- cur <- new <- old prev
@@ -338,6 +345,7 @@ LevelBufs &rk4_stage_output(moka_state *st, int s);
 int rk4_begin(moka_state *st, const double **ssh0);
 void rk4_end(moka_state *st);
 bool rk13_usable(const moka_state *st);       // the 13-stream RK4 form (moka_set_tuning key 7), see api_state.hip
+bool rk_handoff_usable(const moka_state *st); // New from RK4 stage 1 to stage 2 as one-byte codes (moka_set_tuning key 12), see api_state.hip
 StageArgs rk13_stage_args(moka_state *st, int s, double dt, const double *ssh0);
 void rk13_end(moka_state *st);
 FeArgs fe_args(moka_state *st, int ops, int flags, double dt);

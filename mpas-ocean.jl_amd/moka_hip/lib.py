@@ -127,6 +127,7 @@ EXPORTS = [
     "moka_forced_tape_create_quadratic", "moka_forced_adjoint_want_quadratic_drag_gradient",
     "moka_forced_adjoint_quadratic_drag_density_download", "moka_forced_adjoint_quadratic_drag_gradient",
     "moka_forced_tape_device_arrays",
+    "moka_rk_handoff_codec", "moka_state_rk_handoff_escapes",
 ]
 
 
@@ -192,6 +193,8 @@ def lib():
     L.moka_state_optimize_placement.argtypes = [vp, C.c_int, _f64p, _f64p]
     L.moka_state_placement_launches.argtypes = [vp]
     L.moka_state_rk4_streams.argtypes = [vp]
+    L.moka_rk_handoff_codec.argtypes = [_f64p, _f64p, _f64p, C.c_double, C.c_int64, C.POINTER(C.c_int8), _f64p]
+    L.moka_state_rk_handoff_escapes.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.moka_state_placement_launches.restype = C.c_int64
     L.moka_state_placement_log.argtypes = [vp, C.c_int32, C.POINTER(PlacementTrial), _i32p]
     L.moka_state_array_address.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
