@@ -604,6 +604,8 @@ int  moka_state_del4_path(const moka_state *st);
  * to kappa_j and kappa4_j: moka_tracer_tape_* below), time-dependent sources, point-source convenience calls, the 13-stream form, YAML keys and NetCDF I/O of tracers, and fusing the tracer sum into the dycore's stage
  * kernels. */
 int  moka_set_tracers(moka_state *st, int32_t nTracers);
+/* *out = the number of tracers as it stands (0: none); MOKA_ERR_ARG for a NULL out */
+int  moka_tracer_count(const moka_state *st, int32_t *out);
 /* tracer j (0-based) at time_level 0 (previous) / 1 (current): (nVertLevels, nCells) doubles in the caller's cell numbering, like
  * layerThickness */
 int  moka_tracer_upload(moka_state *st, int32_t j, int time_level, const double *host);
@@ -741,8 +743,8 @@ int  moka_state_tracer_vmix_path(const moka_state *st);
  * newest copy of it -- so that the reverse pass and the gradient instances of a recorded step use the field of that step.  The copies
  * are released when a sweep has emptied the tape and when the tape is destroyed.  A tape whose steps never saw a field allocates,
  * records and launches what it did before.
- * Out of scope: a field shared across tracers (upload the same array per tracer), closures that would compute the field
- * (Richardson number, KPP), vertical mixing of momentum, and everything listed above. */
+ * Out of scope: a field shared across tracers (upload the same array per tracer; the Richardson-number closure further down computes
+ * one field for a set of tracers), KPP, vertical mixing of momentum, and everything listed above. */
 int  moka_tracer_vertical_field_upload(moka_state *st, int32_t j, const double *host);
 /* the diffusivity field of tracer j into host (zeros when tracer j has none); MOKA_ERR_ARG for j out of range or a NULL host */
 int  moka_tracer_vertical_field_download(moka_state *st, int32_t j, double *host);
@@ -792,7 +794,7 @@ int  moka_tracer_has_vertical_field(const moka_state *st, int32_t j, int *out);
  * MOKA_ERR_UNSUPPORTED.  The first call that turns the pass on allocates the column form's scratch of 2 * nVertLevels * nEdges doubles;
  * no step allocates anything.  moka_state_optimize_placement neither times nor moves the new arrays.
  * Out of scope: reverse mode through the pass by a moka_tape handle (the operator depends on h_new, so the flow adjoint gains thickness
- * terms; the moka_forced_tape handle, below, carries them), closures (Richardson number, KPP), Forward Euler, fp32
+ * terms; the moka_forced_tape handle, below, carries them), closures other than the Richardson-number one further down (KPP), Forward Euler, fp32
  * storage, partitioned meshes, YAML keys and NetCDF I/O, a time-dependent stress other than by a new upload between steps. */
 int  moka_set_vertical_viscosity(moka_state *st, double nuV, double bottomDrag);
 /* the two scalars as they stand; MOKA_ERR_ARG for a NULL out-pointer */
@@ -836,7 +838,7 @@ int  moka_state_momentum_vmix_path(const moka_state *st);
  * the stream before it replaces an array a launch may still read, and takes effect with the next RK4 step or moka_run -- a moka_run
  * after the call never replays launches captured before it.  A field costs nVertLevels * nEdges doubles of device memory; the upload
  * that turns the pass on allocates the column form's scratch.
- * Out of scope: closures that would compute the field (Richardson number, KPP), fp32 storage, partitioned meshes, YAML keys and NetCDF
+ * Out of scope: closures that would compute the field other than the Richardson-number one further down (KPP), fp32 storage, partitioned meshes, YAML keys and NetCDF
  * I/O, and everything listed above. */
 int  moka_vertical_viscosity_field_upload(moka_state *st, const double *host);
 /* the field into host, (nEdges, nVertLevels) doubles (zeros when there is none); MOKA_ERR_ARG for a NULL host */
@@ -894,6 +896,88 @@ int  moka_bottom_speed_download(moka_state *st, double *host);
  * Float64 state on a whole mesh, whatever Cd is; MOKA_ERR_UNSUPPORTED for fp32 storage, a halo or a partitioned mesh; MOKA_ERR_ARG for
  * another time level or a NULL host. */
 int  moka_bottom_speed(moka_state *st, int time_level, double *host);
+/* The Richardson-number closure (default: off; MPAS-Ocean's config_use_rich_visc / config_use_rich_diff, the Pacanowski-Philander
+ * form): the coefficients of both vertical passes computed on the device, behind stage 4 of every RK4 step, from the state the step
+ * has just formed, and handed to the passes through the field operands above -- F (nVertLevels, nEdges) is the viscosity field of the
+ * momentum pass, G (nVertLevels, nCells) the diffusivity field of the tracer pass; row k is the interface between levels k and k+1.
+ * One tracer jb of the state is designated as buoyancy b (m/s^2, b = -g (rho - rho0) / rho0: a larger b above means stable).
+ * Parameters, all >= 0: nu0 (m^2/s; config_rich_mix, 0.005), alpha (5), nuBackground nuB (m^2/s; 1e-4), kappaBackground kB (m^2/s;
+ * 1e-5), convective conv (m^2/s; 1.0), added to both coefficients where the column is statically unstable; tracerMask: nTracers flags,
+ * nonzero = the tracer takes the closure's diffusivity (NULL: every tracer).  EPS = 1e-20 is a constant of the recipe.
+ * Arithmetic.  Every operation below rounded once, nothing contracted.  The inputs are those of the new level as stage 4 and the
+ * tracers' stage 4 left them, before either vertical pass runs: u = u*, h = h_new, b = phi*_jb.  kc, invArea, nLev and the
+ * maxLevelEdgeTop of a cell's slots are the ones the bottom-speed kernel and the vertical passes use.
+ * Edge e, n = min(maxLevelEdgeTop[e], nVertLevels), (c1, c2) = cellsOnEdge[e], for the interfaces k = 0 .. n-2:
+ *   hE[k]  = 0.5 * (h[k,c1] + h[k,c2])                                (the hE of the momentum recipe)
+ *   hm     = 0.5 * (hE[k] + hE[k+1])
+ *   db     = 0.5 * ((b[k,c1] - b[k+1,c1]) + (b[k,c2] - b[k+1,c2]))
+ *   du     = u[k,e] - u[k+1,e]
+ *   Ri     = (db * hm) / (du * du + EPS)
+ *   Ri > 0 :  t = 1.0 + alpha * Ri;  m = nu0 / (t * t);   F[k,e] = nuB + m
+ *   else   :  F[k,e] = nuB + nu0;    if db < 0:  F[k,e] = F[k,e] + conv
+ * Cell c, n = nLev[c], for k = 0 .. n-2:
+ *   hm  = 0.5 * (h[k,c] + h[k+1,c]);   db = b[k,c] - b[k+1,c]
+ *   acc = 0.0;  for slot i of edgesOnCell[:,c] in slot order, e' = edgesOnCell[i,c]:
+ *                  if min(maxLevelEdgeTop[e'], nVertLevels) > k+1:    (else the slot is omitted and NEITHER level of u[.,e'] is read)
+ *                      du = u[k,e'] - u[k+1,e'];   acc = acc + (kc[e'] * du) * du
+ *   S2  = 2.0 * (acc * invArea[c])
+ *   Ri  = (db * hm) / (S2 + EPS)
+ *   Ri > 0 :  t = 1.0 + alpha * Ri;  m = nu0 / (t * t);   G[k,c] = kB + (nuB + m) / t
+ *   else   :  G[k,c] = kB + (nuB + nu0);   if db < 0:  G[k,c] = G[k,c] + conv
+ * Rows k >= n-1 of F and G are never written: they stay 0.0 from allocation and are never read.  Levels that no active element reads
+ * -- u at k >= n_e, b and h at k >= nLev[c] -- may hold anything, NaN included, and never reach F or G (nLev[c] is the largest n_e of
+ * the cell's edges, so the edge recipe reads b[k+1,c] only for k+1 <= n_e - 1 < nLev[c]).
+ * While the closure is on the momentum pass runs its FIELD instances with F where it would take the uploaded field or nuV, and every
+ * tracer of the set runs the field instances of the tracer pass with G where it would take its own field or kappaV_j.  The caller's
+ * nuV, viscosity field, kappaV_j and per-tracer fields are kept: they are set aside and act again when the closure is switched off,
+ * and their setters and uploads keep working, with their own validation, meanwhile.  Drag, quadratic drag and stress are untouched;
+ * tracers outside the set keep their own coefficient.  Both passes count as on whenever the closure is on (an all-zero F or G is
+ * legitimate: it decouples the columns, as f == 0 does above); dt < 0 is MOKA_ERR_ARG before any launch; with dt == 0.0 or
+ * nVertLevels < 2 the closure launches nothing, like the passes, and the momentum pass of a one-level state is the one it was.
+ * Hence: a buoyancy that is constant over every column gives db == 0, Ri == 0, F = nuB + nu0 and G = kB + (nuB + nu0) everywhere, and
+ * such a step has the bits of a step with the scalars nuV = fl(nuB + nu0) and kappaV_j = fl(kB + fl(nuB + nu0)); alpha == 0 gives the
+ * same where db >= 0.  nuB <= F <= (nuB + nu0) + conv, and kB <= G <= (kB + (nuB + nu0)) + conv.  The sign of db decides the branch
+ * exactly (a difference of doubles is zero only for equal operands; the edge's db is a sum of two of them and its sign is that of the
+ * rounded sum).  No operation cancels after the differences du and db, so F and G carry a small counted multiple of 2^-53 of relative
+ * error against exact arithmetic on the same du and db.  The unit tracer stays exactly 1.0, the column content is conserved and the
+ * momentum budget holds as stated for the passes: F >= 0 and G >= 0 are all they ask.
+ * Kernels (csrc/vmix_closure.hip): k_rich_edge and k_rich_cell, two launches in front of the tracer pass and the momentum pass, the
+ * lanes along k so that loads and stores are contiguous, the k+1 operand a second load of the same lines, the cell's sum in slot
+ * order in registers; no atomics, no LDS, any nVertLevels, every kernel variant.  The same launches over every dycore, in the 16-stream
+ * form of the step: the 13-stream form never carries tracers, and the closure needs one, so a state with the closure on takes the
+ * 16-stream step whatever moka_set_tuning key 7 says.  The step issues launches only: F, G, kc, nLev, both column forms' scratch and the table the tracer pass reads
+ * are allocated by the call that switches the closure on (nVertLevels * (nEdges + nCells) doubles, plus the scratch where the passes
+ * had none), nothing is allocated, synchronised or read back inside a step, and moka_run's graph replays the closure; a moka_run after
+ * a switch never replays launches captured before it.  A state that never switches the closure on launches, allocates and records
+ * exactly what it did before.
+ * p == NULL switches the closure off and frees F and G.  MOKA_ERR_ARG, with nothing changed, for a negative, NaN or infinite
+ * parameter, buoyancyTracer out of range, a state without tracers, NULL out-pointers and another time level.  MOKA_ERR_UNSUPPORTED
+ * where moka_set_vertical_viscosity returns it for a nonzero value (fp32 storage, a halo, a partitioned mesh, an existing moka_tape)
+ * and while a moka_forced_tape of either kind or a moka_tracer_tape of this state exists: the closure makes the step nonlinear in the
+ * buoyancy tracer and the coefficients depend on the flow, so the tapes' transposes would no longer be exact.  While the closure is on
+ * moka_tape_create, moka_forced_tape_create, moka_forced_tape_create_quadratic, moka_tracer_tape_create, moka_halo_create, the
+ * moka_rk4_dist_* calls, moka_step_fe and moka_run(MOKA_FORWARD_EULER) return MOKA_ERR_UNSUPPORTED with a message that names the
+ * closure.  moka_set_tracers (any count) switches the closure off and frees G.
+ * Out of scope: KPP and any non-local closure, an equation of state (the caller supplies buoyancy as a tracer), reverse mode of the flow
+ * or of the tracers through or beside the closure, Forward Euler, fp32 storage, partitioned meshes, YAML keys and NetCDF I/O, smoothing of Ri in space or time, and
+ * fusion into the pass kernels. */
+typedef struct {
+    int32_t buoyancyTracer;
+    double nu0, alpha, nuBackground, kappaBackground, convective;
+    const int32_t *tracerMask;      /* (opt) nTracers flags; NULL = every tracer */
+} moka_richardson_params;
+int  moka_set_richardson_mixing(moka_state *st, const moka_richardson_params *p);
+/* *on = 1 while the closure is on, else 0; *out the parameters as they stand (zeros while it is off; tracerMask is always NULL);
+ * maskOut (opt): nTracers flags, nTracers by moka_tracer_count */
+int  moka_richardson_mixing(const moka_state *st, int *on, moka_richardson_params *out, int32_t *maskOut);
+/* F and G the last step of this state computed, (nEdges, nVertLevels) and (nCells, nVertLevels) doubles in the caller's numbering;
+ * zeros when that step ran without the closure or launched nothing; either may be NULL */
+int  moka_richardson_fields_download(moka_state *st, double *viscEdge, double *diffCell);
+/* Ri, F and G of the recipe from normalVelocity, layerThickness and the buoyancy tracer of time level 0 (previous) or 1 (current),
+ * synchronously and without a step, by the kernels the step launches (their instances that also store Ri): any of the four outputs may
+ * be NULL; rows no interface reaches come back 0.0.  MOKA_ERR_UNSUPPORTED while the closure is off (it names the buoyancy tracer and
+ * the parameters). */
+int  moka_richardson_diagnose(moka_state *st, int time_level, double *riEdge, double *riCell, double *viscEdge, double *diffCell);
 
 /* ---- reverse mode of passive tracer transport over a frozen flow (extension) ---------------------------------------
  * Once the flow is given the tracer step above is linear in phi, so d J(phi_N) / d phi_0 is the exact transpose of a linear map.  It

@@ -545,6 +545,7 @@ int momentum_vmix(moka_state *st, double *u, const double *h, double dt)
     a.tau = st->momTau && st->momTauOn ? st->momTau : nullptr;
     a.dt = dt; a.nu = mom_vmix_nu(st); a.drag = st->momDrag; a.scratch = st->momScratch;
     a.fld = mom_vmix_field(st);
+    if (st->rich && p.K >= 2) { a.nu = 0.0; a.fld = st->richF; }      // the Richardson closure: F of this step, the caller's nuV and field set aside
     const bool qd = st->momCd != 0.0;
     if (p.K < 2 && a.drag == 0.0 && !qd && !a.tau) return MOKA_OK;      // one level and the viscosity alone: no column has anything to do
     const bool generic = st->ctx->variant == 3;
@@ -563,7 +564,9 @@ int momentum_vmix(moka_state *st, double *u, const double *h, double dt)
 int step_rk4(moka_state *st, double dt, moka_tracer_tape *rec)
 {
     HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
-    const bool vmix = st->nTracers > 0 && st->trKappaVDev != nullptr;      // (non-null exactly while some kappaV != 0 or some diffusivity field is on)
+    const bool rich = st->rich;             // the Richardson closure: both vertical passes are on and take the coefficients it computes
+    if (rich && dt < 0.0) return fail(st->ctx, MOKA_ERR_ARG, "Richardson closure: dt must be >= 0 (the implicit solves are not reversible in time)");
+    const bool vmix = st->nTracers > 0 && (rich || st->trKappaVDev != nullptr);      // (non-null exactly while some kappaV != 0 or some diffusivity field is on)
     if (vmix && dt < 0.0) return fail(st->ctx, MOKA_ERR_ARG, "vertical tracer diffusion: dt must be >= 0 (the implicit solve is not reversible in time)");
     const bool mvmix = mom_vmix_on(st);
     if (mvmix && dt < 0.0) return fail(st->ctx, MOKA_ERR_ARG, "vertical momentum mixing: dt must be >= 0 (the implicit solve is not reversible in time)");
@@ -589,8 +592,14 @@ int step_rk4(moka_state *st, double dt, moka_tracer_tape *rec)
         const StageArgs g = s13 ? rk13_stage_args(st, s, dt, ssh0) : rk4_stage_args(st, s, dt, ssh0);
         HIPCHK(c, run_stage(st, g));
         if (st->nTracers > 0) HIPCHK(c, tracer_stage(st, s, g));
+        if (s == 4) {       // the closure: F and G from the new level as stage 4 and the tracers' stage 4 left it, in front of both passes
+            st->richRan = rich && st->mesh->plan.K >= 2 && dt != 0.0;
+            if (st->richRan)
+                HIPCHK(c, launch_richardson(rich_args(st, g.nu_out, g.nh_out, st->trPhi[0] + (size_t)st->mesh->plan.K * st->mesh->plan.nC * st->richP.buoyancyTracer), c->stream));
+        }
         if (s == 4 && vmix && st->mesh->plan.K >= 2 && dt != 0.0)       // the split step: the new tracers (still in the previous level's array) over the new thickness
-            if ((rc = tracer_vmix(st->mesh, c, st->nTracers, g.nh_out, st->trPhi[0], st->trKappaVDev, st->trVfDev, dt, st->trVmixScratch, false, &st->vmixPath))) return rc;
+            if ((rc = tracer_vmix(st->mesh, c, st->nTracers, g.nh_out, st->trPhi[0], rich ? st->richKvDev : st->trKappaVDev, rich ? st->richVfDev : st->trVfDev, dt,
+                                  st->trVmixScratch, false, &st->vmixPath))) return rc;
         if (s == 4 && mvmix && dt != 0.0)       // the split step of the flow: the new normalVelocity over the new thickness (the tracers' stage 4 has read the provisional flow)
             if ((rc = momentum_vmix(st, g.nu_out, g.nh_out, dt))) return rc;
         if (rec) {
@@ -796,6 +805,7 @@ int moka_tendencies(moka_state *st)
 int moka_step_fe(moka_state *st, double dt, int flags)
 {
     if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
+    if (st->rich) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "Richardson closure: applied by RK4 steps only (no Forward Euler)");
     if (st->nonlinear) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "nonlinear terms: moka_tendencies / RK4 only");
     if (st->nTracers > 0) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "tracers: transported by RK4 steps only (no Forward Euler)");
     if (mom_vmix_on(st)) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "vertical momentum mixing: applied by RK4 steps only (no Forward Euler)");
@@ -931,6 +941,10 @@ int moka_run(moka_state *st, int integrator, double dt, int64_t nsteps, int flag
     if (!st) return fail(nullptr, MOKA_ERR_ARG, "state is NULL");
     if (nsteps < 0) return fail(st->ctx, MOKA_ERR_ARG, "nsteps must be >= 0");
     if (integrator != MOKA_FORWARD_EULER && integrator != MOKA_RUNGE_KUTTA_4) return fail(st->ctx, MOKA_ERR_ARG, "unknown integrator");
+    if (integrator == MOKA_RUNGE_KUTTA_4 && dt < 0.0 && st->rich)
+        return fail(st->ctx, MOKA_ERR_ARG, "Richardson closure: dt must be >= 0 (the implicit solves are not reversible in time)");
+    if (integrator == MOKA_FORWARD_EULER && st->rich)
+        return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "Richardson closure: applied by RK4 steps only (no Forward Euler)");
     if (integrator == MOKA_RUNGE_KUTTA_4 && dt < 0.0 && st->nTracers > 0 && st->trKappaVDev)
         return fail(st->ctx, MOKA_ERR_ARG, "vertical tracer diffusion: dt must be >= 0 (the implicit solve is not reversible in time)");
     if (integrator == MOKA_RUNGE_KUTTA_4 && dt < 0.0 && mom_vmix_on(st))

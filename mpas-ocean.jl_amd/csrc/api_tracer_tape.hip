@@ -23,6 +23,8 @@ int moka_tracer_tape_create(moka_state *st, int64_t capacity_steps, moka_tracer_
     if (!st || !out || capacity_steps < 0) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "bad argument");
     *out = nullptr;
     if (st->nTracers == 0) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "tracer reverse mode: the state has no tracers (moka_set_tracers)");
+    if (st->rich)      // (the step is no longer linear in the buoyancy tracer, and the diffusivity depends on the flow)
+        return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "Richardson closure: no reverse mode through or beside it (moka_set_richardson_mixing(st, NULL) first)");
     const Plan &p = st->mesh->plan;
     HIPCHK(st->ctx, hipSetDevice(st->ctx->device));
     moka_tracer_tape *t = new (std::nothrow) moka_tracer_tape();

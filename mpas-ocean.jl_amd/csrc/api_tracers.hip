@@ -174,6 +174,7 @@ int moka_set_tracers(moka_state *st, int32_t nTracers)
     double **arr[9] = {&st->trPhi[0], &st->trPhi[1], &st->trProv[0], &st->trProv[1], &st->trKappaDev, &st->trKappa4Dev, &st->trLap,
                        &st->trKappaVDev, &st->trVmixScratch};
     auto release = [&]() {
+        rich_drop(st);                   // the Richardson closure reads a tracer: off, and G (and F) freed
         drop_sources(st);                // every source goes with the tracers
         drop_vfields(st);                // ... and every diffusivity field
         for (double **q : arr) st->mem.release(*q);
@@ -195,6 +196,13 @@ int moka_set_tracers(moka_state *st, int32_t nTracers)
         }
     HIPCHK(st->ctx, hipStreamSynchronize(st->ctx->stream));
     st->nTracers = nTracers;
+    return MOKA_OK;
+}
+
+int moka_tracer_count(const moka_state *st, int32_t *out)
+{
+    if (!st || !out) return fail(st ? st->ctx : nullptr, MOKA_ERR_ARG, "NULL argument");
+    *out = st->nTracers;
     return MOKA_OK;
 }
 
@@ -324,7 +332,8 @@ static int vmix_commit(moka_state *st, std::vector<double> kv)
     if (!anyField) st->mem.release(st->trVfDev);
     if (!any) {
         st->mem.release(st->trKappaVDev);
-        st->mem.release(st->trVmixScratch);
+        if (!st->rich) st->mem.release(st->trVmixScratch);      // (the Richardson closure runs the pass too and keeps the scratch)
+        if (int rc = rich_commit(st, kv)) return rc;
         st->trKappaV = std::move(kv);
         return MOKA_OK;
     }
@@ -344,6 +353,7 @@ static int vmix_commit(moka_state *st, std::vector<double> kv)
     if (int rc = h2d(st->ctx, st->trKappaVDev, eff.data(), (size_t)nT * sizeof(double))) return rc;
     if (anyField)
         if (int rc = h2d(st->ctx, st->trVfDev, tab.data(), (size_t)nT * sizeof(double *))) return rc;
+    if (int rc = rich_commit(st, kv)) return rc;      // what the pass takes while the Richardson closure is on follows the set-aside values
     st->trKappaV = std::move(kv);
     return MOKA_OK;
 }

@@ -339,6 +339,7 @@ int moka_halo_create(moka_state *st, int32_t nNeighbors, const int32_t *sendCell
     const Plan &p = st->mesh->plan;
     if (st->viscDel4 != 0.0)
         return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "Del4 mixing: not on a state with a halo (its stencil reaches three cell rings, the nonlinear halo two)");
+    if (st->rich) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "Richardson closure: whole meshes only (no halo; moka_set_richardson_mixing(st, NULL) first)");
     if (st->nTracers > 0) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "tracers: whole meshes only (no halo; moka_set_tracers(st, 0) first)");
     if (mom_vmix_on(st)) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "vertical momentum mixing: whole meshes only (no halo; switch the pass off first)");
     if (st->forcedTapes > 0) return fail(st->ctx, MOKA_ERR_UNSUPPORTED, "a moka_forced_tape of this state exists: whole meshes only (no halo)");
@@ -864,6 +865,7 @@ int moka_rk4_dist_begin(moka_halo *h, double dt)
 {
     if (!h) return fail(nullptr, MOKA_ERR_ARG, "halo is NULL");
     moka_state *st = h->st;
+    if (st->rich) return hfail(h, MOKA_ERR_UNSUPPORTED, "Richardson closure: whole meshes only (no distributed RK4 step)");
     if (st->viscDel4 != 0.0) return hfail(h, MOKA_ERR_UNSUPPORTED, "Del4 mixing: whole meshes only (no distributed RK4 step)");
     if (st->nTracers > 0) return hfail(h, MOKA_ERR_UNSUPPORTED, "tracers: whole meshes only (no distributed RK4 step)");
     if (mom_vmix_on(st)) return hfail(h, MOKA_ERR_UNSUPPORTED, "vertical momentum mixing: whole meshes only (no distributed RK4 step)");
@@ -891,6 +893,7 @@ int moka_rk4_dist_stage(moka_halo *h, int stage, int part)
     if (!h) return fail(nullptr, MOKA_ERR_ARG, "halo is NULL");
     if (stage < 1 || stage > 4 || part < 0 || part > 4) return hfail(h, MOKA_ERR_ARG, "stage must be 1..4, part 0..4");
     moka_state *st = h->st;
+    if (st->rich) return hfail(h, MOKA_ERR_UNSUPPORTED, "Richardson closure: whole meshes only (no distributed RK4 step)");
     if (st->viscDel4 != 0.0) return hfail(h, MOKA_ERR_UNSUPPORTED, "Del4 mixing: whole meshes only (no distributed RK4 step)");
     if (st->nTracers > 0) return hfail(h, MOKA_ERR_UNSUPPORTED, "tracers: whole meshes only (no distributed RK4 step)");
     if (mom_vmix_on(st)) return hfail(h, MOKA_ERR_UNSUPPORTED, "vertical momentum mixing: whole meshes only (no distributed RK4 step)");
@@ -946,6 +949,7 @@ int moka_rk4_dist_parts_available(const moka_halo *h)
 int moka_rk4_dist_stage_launch(moka_halo *h, int stage)
 {
     if (!h) return fail(nullptr, MOKA_ERR_ARG, "halo is NULL");
+    if (h->st->rich) return hfail(h, MOKA_ERR_UNSUPPORTED, "Richardson closure: whole meshes only (no distributed RK4 step)");
     if (h->st->viscDel4 != 0.0) return hfail(h, MOKA_ERR_UNSUPPORTED, "Del4 mixing: whole meshes only (no distributed RK4 step)");
     if (h->st->nTracers > 0) return hfail(h, MOKA_ERR_UNSUPPORTED, "tracers: whole meshes only (no distributed RK4 step)");
     if (mom_vmix_on(h->st)) return hfail(h, MOKA_ERR_UNSUPPORTED, "vertical momentum mixing: whole meshes only (no distributed RK4 step)");

@@ -378,6 +378,27 @@ struct MomSpeedArgs {
 };
 hipError_t launch_momentum_bottom_speed(const MomSpeedArgs &a, hipStream_t s);
 
+// ---- the Richardson-number closure of the two vertical passes (moka_set_richardson_mixing; vmix_closure.hip) ----
+// Two launches behind stage 4 of an RK4 step and the tracers' stage 4, in front of both vertical passes: k_rich_edge writes the
+// viscosity F[k,e] of the interfaces k < min(maxLevelEdgeTop[e], K) - 1, k_rich_cell the diffusivity G[k,c] of the interfaces
+// k < nLev[c] - 1 (the recipe of include/moka_hip.h).  LPC lanes run along the contiguous column of an edge / a cell.  Rows at and
+// below those bounds are never written; u, h and b at levels no active element reads are never loaded.
+struct RichArgs {
+    int nE, nC, K, ME;
+    const int32_t *ehdr;          // (4, nE) c1, c2, -, maxLevelEdgeTop
+    const int32_t *eoc, *mltc;    // (ME, nC) edges of a cell, -1 = none; maxLevelEdgeTop of that edge, 0 = none
+    const int32_t *nLev;          // (nC) active depth of a cell (Plan.nLev)
+    const double *keCoef;         // (nE) 0.25 * dcEdge * dvEdge
+    const double *invArea;        // (nC)
+    const double *u, *h, *b;      // (K, nE) normalVelocity, (K, nC) layerThickness, (K, nC) the buoyancy tracer
+    double nu0, alpha, nuB, kB, conv;
+    double *F, *G;                // (K, nE), (K, nC)
+    // the diagnostic instances (moka_richardson_diagnose): Ri of the edge / the cell recipe, (K, nE) / (K, nC).  With either non-null
+    // F and G are optional too, and a kernel none of whose outputs is wanted is not launched.  Both nullptr: the step's instances.
+    double *riE, *riC;
+};
+hipError_t launch_richardson(const RichArgs &a, hipStream_t s);
+
 // ---- the transposed pass (moka_forced_tape; momentum_vmix.hip) ----
 // At the head of a reversed step, per edge column the forward pass computed with these switches (the recipe of include/moka_hip.h):
 // z = Solve_A(xu), xu = h o z in place, hbar to its own (K, nE) array, active levels only; then launch_momentum_vmix_gather adds

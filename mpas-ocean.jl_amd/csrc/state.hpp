@@ -272,6 +272,18 @@ struct moka_state {
     double momCd = 0.0;
     double *momSpeed = nullptr;
     bool momSpeedUsed = false;
+    // the Richardson-number closure (moka_set_richardson_mixing): on or off, the parameters (tracerMask is not kept: richMask holds
+    // nTracers flags), F (K, nE) and G (K, nC) in device numbering, and what the tracer pass takes while the closure is on in the place
+    // of trKappaVDev / trVfDev -- richKvDev: nTracers coefficients, 0.0 for a tracer of the set, else vmix_coefficient; richVfDev:
+    // nTracers pointers, G for a tracer of the set, else its own field that is on, else nullptr.  All of it is allocated when the
+    // closure is switched on (never by a step), brought in line by rich_commit whenever a set-aside coefficient changes, and freed when
+    // it is switched off.  richRan: the last step launched the closure (moka_richardson_fields_download hands out zeros otherwise).
+    bool rich = false;
+    moka_richardson_params richP{};
+    std::vector<int32_t> richMask;
+    double *richF = nullptr, *richG = nullptr, *richKvDev = nullptr;
+    double **richVfDev = nullptr;
+    bool richRan = false;
     mk::DeviceAllocs mem;
     // objects that hold or have exported the addresses of this state's arrays (halos, tapes): while any exists the arrays stay
     // where they are (moka_state_optimize_placement refuses)
@@ -315,10 +327,10 @@ inline MeshDev launch_bounds(const moka_mesh *mm)
     return dev;
 }
 // is the vertical momentum pass on: some coefficient nonzero, Cd included (a field sets nuV aside and counts when an active entry is nonzero), or a
-// stress with a nonzero entry at an edge that has an active level
+// stress with a nonzero entry at an edge that has an active level; or the Richardson closure, which supplies the viscosity field
 inline bool mom_vmix_on(const moka_state *st)
 {
-    return (st->momVf ? st->momVfOn : st->momNuV != 0.0) || st->momDrag != 0.0 || st->momCd != 0.0 || (st->momTau && st->momTauOn);
+    return st->rich || (st->momVf ? st->momVfOn : st->momNuV != 0.0) || st->momDrag != 0.0 || st->momCd != 0.0 || (st->momTau && st->momTauOn);
 }
 // what the pass takes for the viscosity: the field that is on, else the scalar -- 0.0 under a field whose active entries are all zero
 inline const double *mom_vmix_field(const moka_state *st) { return st->momVf && st->momVfOn ? st->momVf : nullptr; }
@@ -368,5 +380,11 @@ int tracer_vmix(moka_mesh *mm, moka_ctx *ctx, int nT, const double *h, double *x
                 double *scratch, bool reverse, int *path, const int32_t *gslot = nullptr, const double *p_new = nullptr, double *D = nullptr);
 bool vfield_on(const moka_state *st, int j);
 double vmix_coefficient(const moka_state *st, const std::vector<double> &kv, int j);
+// api_closure.hip: the Richardson closure.  rich_commit brings richKvDev / richVfDev in line with the mask, the scalars kv and the
+// fields as they stand (the caller has synchronised the stream; a no-op while the closure is off); rich_drop switches the closure off
+// and frees what it owns (likewise synchronised); rich_args: the launch over the whole mesh from u (K, nE), h and b (K, nC)
+int rich_commit(moka_state *st, const std::vector<double> &kv);
+void rich_drop(moka_state *st);
+RichArgs rich_args(const moka_state *st, const double *u, const double *h, const double *b);
 
 }  // namespace mk

@@ -642,6 +642,64 @@ function last_bottom_speed(Prog::MProg)
     check(ccall((:moka_bottom_speed_download, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), s.handle, sp), s.backend.ctx)
     sp
 end
+# The Richardson-number closure of both vertical passes (moka_set_richardson_mixing; include/moka_hip.h states the recipe): behind stage 4
+# of every RK4 step the viscosity per interface and edge and the diffusivity per interface and cell are computed on the device and handed
+# to the momentum pass and the tracer pass.  `buoyancy`: the 0-based index of the tracer that carries b = -g (rho - rho0) / rho0, or
+# nothing to switch the closure off; `tracers`: nothing (every tracer) or one flag per tracer, nonzero = it takes the closure's
+# diffusivity.  The coefficients set elsewhere are kept and act again when the closure is switched off.
+struct RichardsonParams             # moka_richardson_params
+    buoyancyTracer::Int32
+    nu0::Float64
+    alpha::Float64
+    nuBackground::Float64
+    kappaBackground::Float64
+    convective::Float64
+    tracerMask::Ptr{Int32}
+end
+function set_richardson_mixing!(Prog::MProg, buoyancy::Union{Integer, Nothing}; nu0::Real = 0.005, alpha::Real = 5.0, background_viscosity::Real = 1e-4,
+                                background_diffusivity::Real = 1e-5, convective::Real = 1.0, tracers::Union{Vector{Int32}, Nothing} = nothing)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    if buoyancy === nothing
+        check(ccall((:moka_set_richardson_mixing, lib), Cint, (Ptr{Cvoid}, Ptr{RichardsonParams}), s.handle, C_NULL), s.backend.ctx)
+        return
+    end
+    m = tracers === nothing ? Ptr{Int32}(C_NULL) : pointer(tracers)
+    p = Ref(RichardsonParams(buoyancy, nu0, alpha, background_viscosity, background_diffusivity, convective, m))
+    GC.@preserve tracers check(ccall((:moka_set_richardson_mixing, lib), Cint, (Ptr{Cvoid}, Ptr{RichardsonParams}), s.handle, p), s.backend.ctx)
+end
+# the closure as it stands: nothing while it is off, else (parameters, flags) with one flag per tracer (moka_tracer_count of them)
+function richardson_mixing(Prog::MProg)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    nt = Ref{Int32}(0)
+    check(ccall((:moka_tracer_count, lib), Cint, (Ptr{Cvoid}, Ref{Int32}), s.handle, nt), s.backend.ctx)
+    ntracers = Int(nt[])
+    on = Ref{Cint}(0)
+    p = Ref(RichardsonParams(0, 0.0, 0.0, 0.0, 0.0, 0.0, C_NULL))
+    mask = zeros(Int32, max(ntracers, 1))
+    check(ccall((:moka_richardson_mixing, lib), Cint, (Ptr{Cvoid}, Ref{Cint}, Ptr{RichardsonParams}, Ptr{Int32}), s.handle, on, p, mask), s.backend.ctx)
+    on[] == 0 ? nothing : (p[], mask[1:ntracers])
+end
+# (F, G) the last RK4 step computed, (nVertLevels, nEdges) and (nVertLevels, nCells); zeros when that step ran without the closure
+function richardson_fields(Prog::MProg)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    F = Matrix{Float64}(undef, size(Prog.normalVelocity[end])...)
+    G = Matrix{Float64}(undef, size(Prog.layerThickness[end])...)
+    check(ccall((:moka_richardson_fields_download, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), s.handle, F, G), s.backend.ctx)
+    (F, G)
+end
+# (RiEdge, RiCell) of the closure's recipe from a time level (1 current, 0 previous), without a step; the closure must be on
+function richardson_number(Prog::MProg; time_level::Integer = 1)
+    s = Prog.ssh[end].state
+    s === nothing && error("MokaHIP: the model is not on the device yet")
+    rE = Matrix{Float64}(undef, size(Prog.normalVelocity[end])...)
+    rC = Matrix{Float64}(undef, size(Prog.layerThickness[end])...)
+    check(ccall((:moka_richardson_diagnose, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                s.handle, time_level, rE, rC, C_NULL, C_NULL), s.backend.ctx)
+    (rE, rC)
+end
 # 1 the tile form, 2 the column form of the momentum pass served the last step, 0 none yet
 function momentum_vmix_path(Prog::MProg)
     s = Prog.ssh[end].state

@@ -33,6 +33,7 @@ __all__ = [
     "set_tracers", "Tracers", "TracerAdjointTape", "ForcedAdjointTape",
     "set_vertical_mixing", "vertical_mixing", "vertical_viscosity_field", "momentum_vmix_path",
     "quadratic_drag", "bottom_speed", "last_bottom_speed",
+    "set_richardson_mixing", "richardson_mixing", "richardson_fields", "richardson_number",
 ]
 
 MokaError = L.MokaError
@@ -675,6 +676,81 @@ def last_bottom_speed(Prog: "PrognosticVars"):
     sp = np.empty(st.mesh.HorzMesh.data.nEdges, dtype=np.float64)
     L.check(L.lib().moka_bottom_speed_download(st._h, L.f64(sp)), st.mesh.backend._h)
     return sp
+
+
+def _tracer_count(st) -> int:
+    """moka_tracer_count: the state's own count (a raw moka_set_tracers call changes it behind every Python object)."""
+    n = C.c_int32(0)
+    L.check(L.lib().moka_tracer_count(st._h, C.byref(n)), st.mesh.backend._h)
+    return int(n.value)
+
+
+def set_richardson_mixing(Prog: "PrognosticVars", buoyancy, nu0: float = 0.005, alpha: float = 5.0, background_viscosity: float = 1e-4,
+                          background_diffusivity: float = 1e-5, convective: float = 1.0, tracers=None):
+    """The Richardson-number closure of both vertical passes (moka_set_richardson_mixing; an extension, default off;
+    include/moka_hip.h states the recipe): behind stage 4 of every RK4 step the viscosity per interface and edge and the diffusivity
+    per interface and cell are computed on the device from the new level and handed to the momentum pass and the tracer pass.
+    `buoyancy`: the index of the tracer that carries b = -g (rho - rho0) / rho0 in m/s^2, or None to switch the closure off; `nu0`,
+    `alpha`, `background_viscosity`, `background_diffusivity`, `convective`: the Pacanowski-Philander parameters, all >= 0 (the
+    defaults are MPAS-Ocean's); `tracers`: the indices of the tracers that take the closure's diffusivity (None: every tracer).
+    The viscosity, viscosity field, vertical diffusivities and diffusivity fields set elsewhere are kept and act again when the
+    closure is switched off.  Takes effect with the next RK4 step or run_steps."""
+    st = Prog._state
+    h = st.mesh.backend._h
+    if buoyancy is None:
+        L.check(L.lib().moka_set_richardson_mixing(st._h, None), h)
+        return
+    n = _tracer_count(st)
+    mask = None
+    if tracers is not None:
+        mask = np.zeros(n, dtype=np.int32)
+        for j in tracers:
+            if not 0 <= int(j) < n:
+                raise ValueError(f"tracers: index {j} for {n} tracers")
+            mask[int(j)] = 1
+    p = L.RichardsonParams(int(buoyancy), float(nu0), float(alpha), float(background_viscosity), float(background_diffusivity),
+                           float(convective), None if mask is None else mask.ctypes.data)
+    L.check(L.lib().moka_set_richardson_mixing(st._h, C.byref(p)), h)
+
+
+def richardson_mixing(Prog: "PrognosticVars"):
+    """The closure as it stands (moka_richardson_mixing): None while it is off, else a dict with the keyword names of
+    set_richardson_mixing (`tracers`: the sorted indices of the set)."""
+    st = Prog._state
+    on, p = C.c_int(0), L.RichardsonParams()
+    n = _tracer_count(st)
+    mask = np.zeros(max(n, 1), dtype=np.int32)
+    L.check(L.lib().moka_richardson_mixing(st._h, C.byref(on), C.byref(p), mask.ctypes.data), st.mesh.backend._h)
+    if not on.value:
+        return None
+    return {"buoyancy": int(p.buoyancyTracer), "nu0": p.nu0, "alpha": p.alpha, "background_viscosity": p.nuBackground,
+            "background_diffusivity": p.kappaBackground, "convective": p.convective, "tracers": [j for j in range(n) if mask[j]]}
+
+
+def _richardson_shapes(Prog):
+    eshape = tuple(Prog.normalVelocity[-1].shape)
+    return eshape, tuple(Prog.layerThickness[-1].shape)
+
+
+def richardson_fields(Prog: "PrognosticVars"):
+    """(F, G) the last RK4 step computed (moka_richardson_fields_download): the viscosity, (nEdges, nVertLevels), and the
+    diffusivity, (nCells, nVertLevels); row k is the interface between levels k and k + 1.  Zeros when that step ran without the
+    closure."""
+    st = Prog._state
+    eshape, cshape = _richardson_shapes(Prog)
+    F, G = np.empty(eshape, dtype=np.float64), np.empty(cshape, dtype=np.float64)
+    L.check(L.lib().moka_richardson_fields_download(st._h, L.f64(F), L.f64(G)), st.mesh.backend._h)
+    return F, G
+
+
+def richardson_number(Prog: "PrognosticVars", time_level: int = 1):
+    """(RiEdge, RiCell) of the closure's recipe from time level `time_level` (1 current, 0 previous), computed on the device without
+    a step (moka_richardson_diagnose); the closure must be on: it names the buoyancy tracer."""
+    st = Prog._state
+    eshape, cshape = _richardson_shapes(Prog)
+    rE, rC = np.empty(eshape, dtype=np.float64), np.empty(cshape, dtype=np.float64)
+    L.check(L.lib().moka_richardson_diagnose(st._h, int(time_level), L.f64(rE), L.f64(rC), None, None), st.mesh.backend._h)
+    return rE, rC
 
 
 def momentum_vmix_path(Prog: "PrognosticVars") -> int:

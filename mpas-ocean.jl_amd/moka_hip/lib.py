@@ -63,6 +63,11 @@ class PlacementTrial(C.Structure):     # moka_placement_trial
     _fields_ = [("field", C.c_int32), ("ms_old", C.c_double), ("ms_new", C.c_double), ("kept", C.c_int32)]
 
 
+class RichardsonParams(C.Structure):   # moka_richardson_params
+    _fields_ = [("buoyancyTracer", C.c_int32), ("nu0", C.c_double), ("alpha", C.c_double), ("nuBackground", C.c_double),
+                ("kappaBackground", C.c_double), ("convective", C.c_double), ("tracerMask", C.c_void_p)]
+
+
 class MeshInfo(C.Structure):
     _fields_ = [
         ("nCells", C.c_int32), ("nEdges", C.c_int32), ("nVertices", C.c_int32), ("nVertLevels", C.c_int32),
@@ -113,6 +118,7 @@ EXPORTS = [
     "moka_has_surface_stress", "moka_state_momentum_vmix_path",
     "moka_vertical_viscosity_field_upload", "moka_vertical_viscosity_field_download", "moka_has_vertical_viscosity_field",
     "moka_set_quadratic_bottom_drag", "moka_quadratic_bottom_drag", "moka_bottom_speed_download", "moka_bottom_speed",
+    "moka_tracer_count", "moka_set_richardson_mixing", "moka_richardson_mixing", "moka_richardson_fields_download", "moka_richardson_diagnose",
     "moka_tracer_adjoint_want_source_gradient", "moka_tracer_adjoint_source_download",
     "moka_tracer_adjoint_want_diffusivity_gradient", "moka_tracer_adjoint_diffusivity_gradient",
     "moka_tracer_adjoint_diffusivity_density_download",
@@ -305,6 +311,11 @@ def lib():
     L.moka_quadratic_bottom_drag.argtypes = [vp, C.POINTER(C.c_double)]
     L.moka_bottom_speed_download.argtypes = [vp, vp]
     L.moka_bottom_speed.argtypes = [vp, C.c_int, vp]
+    L.moka_tracer_count.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.moka_set_richardson_mixing.argtypes = [vp, C.POINTER(RichardsonParams)]
+    L.moka_richardson_mixing.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(RichardsonParams), vp]
+    L.moka_richardson_fields_download.argtypes = [vp, vp, vp]
+    L.moka_richardson_diagnose.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.moka_tracer_adjoint_want_source_gradient.argtypes = [vp, C.c_int32, C.c_int]
     L.moka_tracer_adjoint_source_download.argtypes = [vp, C.c_int32, vp]
     L.moka_tracer_adjoint_want_diffusivity_gradient.argtypes = [vp, C.c_int32, C.c_int, C.c_int]
